@@ -1,5 +1,6 @@
 # FETCH_SIZE calibration for streaming reads and 64-byte gathers (bench_tools/fetch_calib.hip) -> gpurun_out/fetch_calib.json
-cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
+cd /tmp && export TMPDIR=/tmp; cd "$HERE"
 rm -rf gpurun_out/fetch_calib; mkdir -p gpurun_out/fetch_calib
 hipcc -O3 -std=c++17 --offload-arch=gfx950 bench_tools/fetch_calib.hip -o gpurun_out/fetch_calib/fetch_calib || exit 1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/fetch_calib/out -- gpurun_out/fetch_calib/fetch_calib > gpurun_out/fetch_calib/known.json 2> gpurun_out/fetch_calib/err.txt

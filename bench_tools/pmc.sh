@@ -1,7 +1,8 @@
 #!/bin/bash
 # quick SQ counters: bash bench_tools/pmc.sh <tag> [bench args]
 TAG=${1:-t}; shift || true
-cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
+cd /tmp && export TMPDIR=/tmp; cd "$HERE"
 OUT=gpurun_out/pmc_$TAG; mkdir -p $OUT
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $OUT -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.txt
 python - <<PY

@@ -2,7 +2,8 @@
 # What bounds the cross term: memory-side and SQ counters of r1cs_cross_term_kernel in isolation (bench_tools/fold_bench.py), one pass per group.
 # bash bench_tools/pmc_cross.sh [rc]
 RC=${1:-100}
-cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
+cd /tmp && export TMPDIR=/tmp; cd "$HERE"
 OUT=gpurun_out/pmc_cross; rm -rf $OUT; mkdir -p $OUT
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum" \

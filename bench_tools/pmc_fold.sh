@@ -1,6 +1,7 @@
 #!/bin/bash
 # HBM/L2 counters of the fold kernels in isolation: bash bench_tools/pmc_fold.sh
-cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
+cd /tmp && export TMPDIR=/tmp; cd "$HERE"
 OUT=gpurun_out/pmc_fold; rm -rf $OUT; mkdir -p $OUT
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -- python bench_tools/fold_bench.py > $OUT/log_fetch.txt 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -- python bench_tools/fold_bench.py > $OUT/log_write.txt 2>&1

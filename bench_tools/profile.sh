@@ -4,8 +4,9 @@
 # Usage (through gpurun): bash bench_tools/profile.sh <tag> [bench.py args...]
 set -u
 TAG=${1:-r01}; shift || true
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
 cd /tmp && export TMPDIR=/tmp
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$HERE"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 ARGS="--steps 5 --warmup 1 --no-cpu-baseline --pmc off --no-plain-leg --sub-records off $*"   # --pmc off: bench.py must not start its own rocprofv3 passes under this one;

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Round measurement sweep (through gpurun): one JSON line per configuration into gpurun_out/sweep_<tag>.jsonl
 TAG=${1:-r01}
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
+cd "$HERE"
 OUT=gpurun_out/sweep_$TAG.jsonl; : > $OUT
 run() { python bench.py "$@" 2>/dev/null | tail -1 >> $OUT; }
 run --steps 20 --warmup 5                                         # headline as the driver runs it: 2^22 table, 3 in flight (+ live PMC traffic, plain leg, one-shot leg, cpu baseline)

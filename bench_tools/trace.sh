@@ -1,7 +1,8 @@
 #!/bin/bash
 # quick kernel-trace only: bash bench_tools/trace.sh <tag> [bench args]
 TAG=${1:-t}; shift || true
-cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
+cd /tmp && export TMPDIR=/tmp; cd "$HERE"
 OUT=gpurun_out/trace_$TAG; mkdir -p $OUT
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.txt
 python - <<PY

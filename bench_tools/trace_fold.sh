@@ -1,4 +1,5 @@
-cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
+cd /tmp && export TMPDIR=/tmp; cd "$HERE"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/trace_foldb -- python bench_tools/fold_bench.py > /dev/null 2>&1
 python - <<PY
 import csv,glob

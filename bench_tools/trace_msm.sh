@@ -1,6 +1,7 @@
 # kernel timeline of the pipelined MSM bench (args: extra bench.py flags) -> gpurun_out/trace_msm/timeline.txt (everything but the
 # short planes/plan kernels) + per-kernel stats
-cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
+cd /tmp && export TMPDIR=/tmp; cd "$HERE"
 rm -rf gpurun_out/trace_msm; mkdir -p gpurun_out/trace_msm
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/trace_msm -- python bench.py --steps 12 --warmup 3 --no-cpu-baseline --pmc off --no-plain-leg "$@" > gpurun_out/trace_msm/bench.json 2> gpurun_out/trace_msm/err.txt
 f=$(ls gpurun_out/trace_msm/*/*_kernel_trace.csv | head -1)

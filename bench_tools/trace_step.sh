@@ -3,7 +3,8 @@
 # queue, stream, share of the duration overlapped by kernels of other queues, kernel.  NOTE: under rocprofv3 every launch call costs
 # the host more (a commitment's ~45 launches block the submitting thread for > 1 ms), so the host-side gaps are wider than in a plain run;
 # the device-side order and the kernel durations are what this is for.
-cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
+HERE=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, resolved before any cd
+cd /tmp && export TMPDIR=/tmp; cd "$HERE"
 rm -rf gpurun_out/trace_step
 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace_step -- python bench.py --workload fold_step --steps 6 --warmup 3 --no-cpu-baseline --secondary 0 "$@" > gpurun_out/trace_step.log 2>&1
 f=$(ls gpurun_out/trace_step/*/*_kernel_trace.csv | head -1)

@@ -17,6 +17,66 @@ def kernel_profile(lib, prefix):
     return tot.value, cnt.value
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 16  # a larger output is dumped as this many rows at fixed, seeded positions
+
+
+def field_limbs(values):
+    """Field elements (ints < 2^256) -> float64 array (len, 8) of their 32-bit little-endian limbs (exact: every limb < 2^53)."""
+    import numpy as np
+
+    return np.array([[(int(v) >> (32 * k)) & 0xFFFFFFFF for k in range(8)] for v in values], dtype=np.float64).reshape(-1, 8)
+
+
+def point_limbs(curve, jac):
+    """A 96-byte Jacobian point -> (2, 8) float64: canonical affine x and y as 32-bit limbs (the identity is (0, 0)).  The Jacobian
+    Z depends on the order of the additions, the point does not."""
+    import lurk_beta_amd as L
+
+    return field_limbs(L.point_to_affine(curve, jac))
+
+
+def ints_flat(v):
+    """A value made of field elements and affine points (ints, (x, y) tuples, None for the identity point, nested lists) -> flat list of ints"""
+    if v is None:
+        return [0, 0]
+    if hasattr(v, "tolist"):  # numpy scalars and arrays
+        v = v.tolist()
+    if isinstance(v, (list, tuple)):
+        return [x for e in v for x in ints_flat(e)]
+    return [int(v)]
+
+
+def limb_rows(name, rows):
+    """(m, 4) uint64 field elements (a torch tensor or numpy array) -> {name: (m, 8) float64 32-bit limbs}; above DUMP_SAMPLE_ROWS rows,
+    the rows at DUMP_SAMPLE_ROWS fixed positions (seed 0, sorted) and those positions as {name}_index."""
+    import numpy as np
+
+    if hasattr(rows, "cpu"):
+        rows = rows.cpu().numpy()
+    rows = np.ascontiguousarray(rows).view(np.uint64).reshape(-1, 4)
+    out = {}
+    if len(rows) > DUMP_SAMPLE_ROWS:
+        idx = np.sort(np.random.default_rng(0).choice(len(rows), DUMP_SAMPLE_ROWS, replace=False))
+        rows = rows[idx]
+        out[name + "_index"] = idx.astype(np.float64)
+    out[name] = rows.view(np.uint32).reshape(-1, 8).astype(np.float64)
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs DIR`: write every {name: float32 / float64 array} to DIR/<name>.npy (at most DUMP_LIMIT_BYTES in all)."""
+    import numpy as np
+
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def cpu_quota_cores():
     """CPUs the cgroup lets this container use (cpu.max / cfs quota), or None."""
     try:

@@ -7,7 +7,7 @@ import os
 import sys
 import time
 
-from .common import BENCH, ROOT
+from .common import BENCH, ROOT, dump_outputs, field_limbs, ints_flat
 
 
 def compress_workload(args, lib, world, rank):
@@ -92,6 +92,9 @@ def compress_workload(args, lib, world, rank):
     elapsed = time.perf_counter() - t0
     gc.enable()
     lib.lurk_hip_profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        # the last proof, one file per field: its field elements and affine points (x, y; the identity as (0, 0)) as 32-bit limbs
+        dump_outputs(args.dump_outputs, {"proof_" + k: field_limbs(ints_flat(v)) for k, v in sorted(proof.items())})
 
     def kernel_ms(name):
         tot, cnt = ctypes.c_double(), ctypes.c_uint64()

@@ -7,7 +7,7 @@ import os
 import sys
 import time
 
-from .common import BENCH, ROOT, cpu_leg_threads
+from .common import BENCH, ROOT, cpu_leg_threads, dump_outputs, limb_rows, point_limbs
 
 
 def _frame_structured_columns(rng, row_of_entry, num_cons, num_vars, num_io):
@@ -287,10 +287,14 @@ def fold_step_workload(args, lib, world, rank):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last = step()
         # (the folds are ordered on the context's own stream; torch.cuda.synchronize() is device-wide)
         torch.cuda.synchronize()
         region_ms.append((time.perf_counter() - t0) / args.steps * 1e3)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: comm(W2), comm(T) and the challenge r (Montgomery limbs); the loops below step again
+        dump_outputs(args.dump_outputs, {"comm_W2": point_limbs(L.CURVE_PALLAS, last[0]), "comm_T": point_limbs(L.CURVE_PALLAS, last[1]),
+                                         **limb_rows("challenge", last_r[0])})
     elapsed = sorted(region_ms)[len(region_ms) // 2] * 1e-3 * args.steps
     lib.lurk_hip_profile_enable(0)
     phase_primary = dict(phase)  # (the both-curve loops below run step() again)

@@ -8,7 +8,7 @@ from __future__ import annotations
 import json
 import time
 
-from .common import kernel_profile
+from .common import dump_outputs, kernel_profile, limb_rows, point_limbs
 
 
 def fold_step_from_files(args, lib, world, rank):
@@ -68,7 +68,7 @@ def fold_step_from_files(args, lib, world, rank):
         cw, ct = ctx.begin(d_w2, x2, stream=stream)
         r = ctx.challenge()
         ctx.finish(r)
-        return cw, ct
+        return cw, ct, r
 
     for _ in range(args.warmup):
         step()
@@ -77,10 +77,12 @@ def fold_step_from_files(args, lib, world, rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        cw, ct, r = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     lib.lurk_hip_profile_enable(0)
+    if args.dump_outputs and rank == 0:  # what the last timed step handed its caller: comm(W2), comm(T), r (Montgomery limbs)
+        dump_outputs(args.dump_outputs, {"comm_W2": point_limbs(curve, cw), "comm_T": point_limbs(curve, ct), **limb_rows("challenge", r)})
     verified = None
     if args.verify and rank == 0:
         assert curve == L.CURVE_PALLAS, "--verify of a dumped step: the oracle leg is written for the primary (Pallas) curve"

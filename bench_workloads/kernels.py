@@ -7,7 +7,7 @@ import os
 import sys
 import time
 
-from .common import BENCH, ROOT, cpu_leg_omp, cpu_leg_threads
+from .common import BENCH, ROOT, cpu_leg_omp, cpu_leg_threads, dump_outputs, limb_rows
 
 
 def poseidon_mads_per_hash(arity):
@@ -125,6 +125,14 @@ def other_workloads(args, lib, world, rank):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left in HBM: the vector it transformed in place, or the tree's internal nodes and its root
+        if args.workload == "ntt":
+            dump_outputs(args.dump_outputs, limb_rows("ntt", d_data))
+        elif world == 1:
+            dump_outputs(args.dump_outputs, {**limb_rows("tree_nodes", d_levels), **limb_rows("tree_root", d_levels[-1:])})
+        else:
+            dump_outputs(args.dump_outputs, limb_rows("tree_root", d_root))
     verified, cpu_full = None, None
     if args.verify and args.workload == "poseidon_tree" and rank == 0:
         # the whole tree again on the CPU (oracle/oracle.c, every core): the root must be the same 32 bytes.  2^24 leaves are

@@ -8,7 +8,7 @@ import sys
 import time
 
 from .common import BENCH, ROOT
-from .common import cpu_quota_cores, kernel_profile
+from .common import cpu_quota_cores, dump_outputs, kernel_profile, point_limbs
 from .predict import msm_predicted_value
 
 
@@ -375,6 +375,8 @@ def msm_workload(args, lib, world, rank):
         result = run_steps(args.steps)
         sync()
         regions.append(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"commitment": point_limbs(L.CURVE_PALLAS, result)})  # the last timed step's commitment
     # what ran inside the regions: with commitments in flight the accumulation is the PERSISTENT kernel on the slots' low-priority streams
     timed_acc = {k: kernel_profile(lib, k) for k in ("msm_accumulate_persistent", "msm_accumulate")}
     # per-kernel durations (HIP events on the launch stream) come from synchronous commitments so that

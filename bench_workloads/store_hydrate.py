@@ -7,7 +7,7 @@ import os
 import sys
 import time
 
-from .common import BENCH, ROOT, cpu_leg_omp, cpu_leg_threads
+from .common import BENCH, ROOT, cpu_leg_omp, cpu_leg_threads, dump_outputs, limb_rows
 
 
 def store_hydrate_workload(args, lib, world, rank):
@@ -22,7 +22,7 @@ def store_hydrate_workload(args, lib, world, rank):
     from oracle import coracle as C
 
     F = 1
-    out = None
+    out, dumps = None, {}
     cpu_threads, cpu_info = cpu_leg_threads()
     cpu_leg_omp(cpu_threads)  # the CPU leg below runs with the thread count it reports
     for name, dag in (("deep", SH.list_dag(400)), ("wide", SH.wide_dag(12000))):
@@ -34,6 +34,7 @@ def store_hydrate_workload(args, lib, world, rank):
         for _ in range(args.steps):
             got, levels = SH.hydrate_records(F, rec, vals)
         ms = (time.perf_counter() - t0) / args.steps * 1e3
+        dumps.update(limb_rows("digests_" + name, got))  # the last timed hydration's digests
         r = {"ms_per_hydration": round(ms, 3), "nodes": len(dag), "hashed_nodes": hashed, "levels": levels,
              "value": round(hashed / ms / 1e3, 4), "unit": "M hashed nodes/s"}
         want = None
@@ -63,5 +64,7 @@ def store_hydrate_workload(args, lib, world, rank):
             out["wide"] = r
     if "cpu_baseline" in out["deep"]:
         out["cpu_baseline"] = out["deep"]["cpu_baseline"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dumps)
     if rank == 0:
         print(json.dumps(out), flush=True)
