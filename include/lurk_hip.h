@@ -369,7 +369,9 @@ int lurk_hip_witness_blocks_dev(void* d_w, size_t first, size_t stride, const vo
 
 /* ---- NTT ---------------------------------------------------------------------------------
  * No reference counterpart: radix-2 NTT over a Pasta field, natural order in
- * and out, omega = 5^((p-1)/2^32)^(2^(32-log_n)); inverse includes the 1/n scaling. */
+ * and out, omega = 5^((p-1)/2^32)^(2^(32-log_n)); inverse includes the 1/n scaling.  log_n <= 28; field_id 0 or 1.
+ * Input: n canonical field elements (< p, 4 x u64 little-endian each); other values give unspecified results.  Output: n
+ * canonical field elements.  A refused call (log_n, field, null buffer) returns an error before any launch or copy. */
 int lurk_hip_ntt(int field_id, void* inout, unsigned log_n, int inverse);
 int lurk_hip_ntt_dev(int field_id, void* d_inout, unsigned log_n, int inverse, void* stream);
 

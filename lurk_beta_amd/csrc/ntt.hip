@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "curve29.cuh"
+#include "ntt29.cuh"
 #include "poseidon29.cuh"
 
 namespace lurk {
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(NTT_PASS_BLOCK) void ntt_pass_kernel(const Fe<F>* _
 // nine-limb value and 4 exchanges per lane-stage - 673 v_cndmask (4.1 issue cycles each on gfx950) and 216 ds_bpermute (24 cycles of
 // the LDS pipeline each) per pass and lane, 10 % of a pass that runs at its instruction-issue bound.  An odd
 // ns ends with a radix-2 round on bit ns - 1 (its second free bit is bit 7, a column bit).
-// Twiddles of the stages come from a per-workgroup LDS table of omega_{2^ns}^j (radix-2^29 records), the twist between passes
+// Twiddles of the stages come from a per-workgroup LDS table of omega_{2^ns}^j (canonical radix-2^29 records), the twist between passes
 // from the global omega^i table.  The first pass reads the caller's natural-order, canonical input through the bit-reversed
 // tile addressing (no separate permutation pass) and converts on the fly; between passes values are stored as the packed
 // 256-bit image of the lazily reduced Montgomery-2^261 residue (no conversion products); the last pass multiplies by 1 (or
@@ -171,35 +172,7 @@ __device__ __forceinline__ F29<F> f29_select(bool c, const F29<F>& a, const F29<
     for (int i = 0; i < 9; i++) r.l[i] = c ? a.l[i] : b.l[i];
     return r;
 }
-// 4p with its limbs re-balanced like f29_bias (limb_i += 2^30, limb_{i+1} -= 2): subtracting a TIGHT value below 2^256 limb-wise
-// never underflows.  The butterflies' subtrahend is always a fresh product (< 2^255 + p), so this small bias replaces the
-// general 64p one and a value grows by < 2^256.1 per stage: eight stages stay below 2^259.3 with no reduction in between.
-template <class F>
-LURK_HD constexpr uint32_t ntt_bias4(int i) {
-    uint64_t carry = 0;
-    uint32_t limb = 0;
-    for (int k = 0; k <= i; k++) {
-        uint64_t x = (uint64_t)f29_mod<F>(k) * 4u + carry;
-        limb = (uint32_t)(x & F29_MASK);
-        carry = x >> 29;
-        if (k == 8) limb = (uint32_t)x;
-    }
-    uint32_t v = limb;
-    if (i < 8) v += 1u << 30;
-    if (i > 0) v -= 2u;
-    return v;
-}
-// (u, v) <- (u + w v, u - w v): u tight-limbed on entry (value < 2^260), v tight; both results carried (tight limbs), lazily
-// reduced: each grows by < 2^256.1
-template <class F>
-__device__ __forceinline__ void ntt_bfly(F29<F>& u, F29<F>& v, const F29<F>& w) {
-    const F29<F> x = f29_mul<F>(v, w);  // tight, < 2^255 + p
-    F29<F> d;
-#pragma unroll
-    for (int i = 0; i < 9; i++) d.l[i] = u.l[i] + (ntt_bias4<F>(i) - x.l[i]);
-    v = f29_carry<F>(d);
-    u = f29_carry<F>(f29_add<F>(u, x));
-}
+// the butterfly (ntt_bias4, ntt_bfly) and its bounds: ntt29.cuh
 
 // zero bits inserted at positions p < q of a 6-bit lane id: the 8-bit slot of the lane's element 0 in the round that pairs bits p and q
 __device__ __forceinline__ unsigned ntt_ins2(unsigned lane, unsigned p, unsigned q) {
@@ -231,7 +204,7 @@ __global__ __launch_bounds__(NTT_W_BLOCK) void ntt_wave_pass_kernel(const Fe<F>*
         tbase = (blockIdx.x % groups) << cbits;
     }
     for (unsigned j = tid; j < rows / 2; j += NTT_W_BLOCK) {
-        const F29<F> w = f29_from_mont256<F>(tw[(size_t)j << (log_n - ns)]);
+        const F29<F> w = ntt_twiddle29<F>(tw[(size_t)j << (log_n - ns)]);  // canonical: keeps w v below the 4p bias (ntt29.cuh)
 #pragma unroll
         for (int i = 0; i < 9; i++) lt[j * P29_STRIDE + i] = w.l[i];
     }
@@ -343,7 +316,7 @@ __global__ __launch_bounds__(NTT_W_BLOCK) void ntt_wave_pass_kernel(const Fe<F>*
             F29<F> c;
 #pragma unroll
             for (int i = 0; i < 9; i++) c.l[i] = cst.out_c[i];
-            const F29<F> u = f29_mul<F>(e[k], c);  // value / 2^261 (times n^-1): tight, < p + 1
+            const F29<F> u = f29_mul<F>(e[k], c);  // value / 2^261 (times n^-1): tight, <= p (forward) / < 2p (inverse)
             f29_pack<F>(u, x);
             fe_cond_sub<F>(x);
         } else {

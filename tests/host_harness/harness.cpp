@@ -479,3 +479,99 @@ extern "C" int hh_keyfold_plan(const uint64_t* weights, size_t T, size_t m, int 
     return 0;
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// The NTT's wave-resident passes (ntt.hip: ntt_device, log_n >= 12) as a plain radix-2 decimation-in-time with the kernel's value
+// sequence and pass plan, every bound of ntt29.cuh asserted: the first pass converts with in_c = 2^522 mod p, a pass runs ns lazy
+// ntt_bfly stages with the table's twiddles in canonical form (ntt_twiddle29), values leave a pass through f29_reduce + f29_pack (< 2^255.1), a later pass
+// begins with the twist product (negated when idx & n/2), the last multiplies by out_c (1 or n^-1) and leaves through fe_cond_sub.
+// The lane / tile layout is not modelled (the GPU tests cover it).  data: n canonical 8 x 32 values, transformed in place.
+#include "../../lurk_beta_amd/csrc/ntt29.cuh"
+template <class F>
+static void ntt_wave_host(uint32_t* data, unsigned log_n, bool inverse) {
+    const size_t n = (size_t)1 << log_n, half_n = n / 2;
+    Fe<F> omega;
+    for (int i = 0; i < 8; i++) omega.l[i] = F::w32(i);
+    for (unsigned i = log_n; i < 32; i++) omega = fe_sqr<F>(omega);
+    if (inverse) omega = fe_inv<F>(omega);
+    std::vector<Fe<F>> tw(half_n);  // omega^i, Montgomery(2^256) (ntt_twiddle_kernel)
+    tw[0] = fe_one<F>();
+    for (size_t i = 1; i < half_n; i++) tw[i] = fe_mul<F>(tw[i - 1], omega);
+    Fe<F> v = fe_one<F>();
+    for (int d = 0; d < 522 - 256; d++) v = fe_add<F>(v, v);
+    const F29<F> in_c = f29_from_plain<F>(v.l);
+    const Fe<F> o = fe_from_mont<F>(inverse ? fe_inv<F>(fe_from_u64<F>((uint64_t)n)) : fe_one<F>());
+    const F29<F> out_c = f29_from_plain<F>(o.l);
+    std::vector<uint32_t> a(n * 8);  // the working array between passes (bit-reversed order, packed 8 x 32)
+    for (size_t i = 0; i < n; i++) {
+        size_t r = 0;
+        for (unsigned b = 0; b < log_n; b++) r |= ((i >> b) & 1) << (log_n - 1 - b);
+        for (int k = 0; k < 8; k++) a[8 * r + k] = data[8 * i + k];
+    }
+    const unsigned passes = (log_n + 7) / 8;
+    unsigned s0 = 0;
+    for (unsigned p = 0; p < passes; p++) {
+        const unsigned ns = (log_n - s0 + (passes - p) - 1) / (passes - p);
+        const bool first = p == 0, last = p + 1 == passes;
+        const unsigned rows = 1u << ns;
+        std::vector<F29<F>> lt(rows / 2);
+        for (unsigned j = 0; j < rows / 2; j++) lt[j] = ntt_twiddle29<F>(tw[(size_t)j << (log_n - ns)]);
+        std::vector<F29<F>> e(rows);
+        for (size_t H = 0; H < (n >> (s0 + ns)); H++)
+            for (size_t t = 0; t < ((size_t)1 << s0); t++) {
+                for (unsigned l = 0; l < rows; l++) {
+                    const uint32_t* x = &a[8 * ((H << (s0 + ns)) | ((size_t)l << s0) | t)];
+                    if (first) {
+                        e[l] = f29_mul<F>(f29_from_plain<F>(x), in_c);
+                    } else {
+                        size_t rl = 0;
+                        for (unsigned b = 0; b < ns; b++) rl |= ((l >> b) & 1u) << (ns - 1 - b);
+                        const size_t idx = (t * rl) << (log_n - s0 - ns);
+                        Fe<F> w = tw[idx & (half_n - 1)];
+                        if (idx & half_n) w = fe_neg<F>(w);
+                        e[l] = f29_mul<F>(f29_from_plain<F>(x), f29_from_mont256<F>(w));
+                    }
+                }
+                for (unsigned st = 0; st < ns; st++)
+                    for (unsigned l0 = 0; l0 < rows; l0++)
+                        if (!((l0 >> st) & 1u)) ntt_bfly<F>(e[l0], e[l0 | (1u << st)], lt[(l0 & ((1u << st) - 1u)) << (ns - st - 1)]);
+                for (unsigned l = 0; l < rows; l++) {
+                    uint32_t* x = &a[8 * ((H << (s0 + ns)) | ((size_t)l << s0) | t)];
+                    if (last) {
+                        const F29<F> u = f29_mul<F>(e[l], out_c);
+                        // one conditional subtraction has to reach a canonical value: u < 2p (u <= p when out_c = 1)
+                        F29_ASSERT(u.l[8] < (1u << 27), "ntt last pass: product >= 2^259");
+                        f29_pack<F>(u, x);
+                        uint32_t d[8], borrow = 0, b2 = 0;
+                        for (int k = 0; k < 8; k++) d[k] = subb32(x[k], F::mod(k), borrow);
+                        for (int k = 0; k < 8; k++) subb32(d[k], F::mod(k), b2);
+                        F29_ASSERT(borrow || b2, "ntt last pass: product >= 2p, one conditional subtraction is not enough");
+                        fe_cond_sub<F>(x);
+                    } else {
+                        const F29<F> r = f29_reduce<F>(e[l]);
+                        F29_ASSERT_LIMBS(r, 29, "ntt between passes");
+                        f29_pack<F>(r, x);
+                        F29_ASSERT(x[7] < 0x892fdf71u, "ntt between passes: packed value >= 2^255.1");
+                    }
+                }
+            }
+        s0 += ns;
+    }
+    for (size_t i = 0; i < n * 8; i++) data[i] = a[i];
+}
+extern "C" void hh_ntt_wave(int field, uint32_t* data, unsigned log_n, int inverse) {
+    if (field == 0) ntt_wave_host<PallasFp>(data, log_n, inverse != 0);
+    else ntt_wave_host<PallasFq>(data, log_n, inverse != 0);
+}
+// ntt_bfly's add / subtract half on chosen operands, `stages` times on the same u (u <- u + x, v = u - x): u9, x9 as raw limbs;
+// out: the final u and v, 9 limbs each
+extern "C" void hh_ntt_bfly_x(int field, const uint32_t* u9, const uint32_t* x9, int stages, uint32_t* out_u9, uint32_t* out_v9) {
+#define NTT_BFLY_CASE(F)                                                              \
+    {                                                                                 \
+        F29<F> u, v, x;                                                               \
+        for (int k = 0; k < 9; k++) { u.l[k] = u9[k]; x.l[k] = x9[k]; v.l[k] = 0; }   \
+        for (int s = 0; s < stages; s++) ntt_bfly_x<F>(u, v, x);                      \
+        for (int k = 0; k < 9; k++) { out_u9[k] = u.l[k]; out_v9[k] = v.l[k]; }       \
+    }
+    if (field == 0) NTT_BFLY_CASE(PallasFp) else NTT_BFLY_CASE(PallasFq)
+}

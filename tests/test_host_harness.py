@@ -461,3 +461,80 @@ def test_key_fold_plan_digits_recombine_to_the_weights(kb, Wt, log_t, m):
                              ctypes.byref(ctypes.c_int()), ctypes.byref(ctypes.c_int()), off, wd, digits.ctypes.data_as(ctypes.c_void_p))
     assert rc == (1 if kb * Wt == 256 else 0)
 
+
+
+def _ntt_wave(f, a, log_n, inverse=False):
+    b = np.ascontiguousarray(a, dtype=np.uint64).copy()
+    H.lib().hh_ntt_wave(f, vp(b), log_n, int(inverse))
+    return b
+
+
+@pytest.mark.parametrize("f", [0, 1])
+@pytest.mark.parametrize("log_n", range(12, 19))
+def test_ntt_wave_pass_arithmetic_under_bound_assertions(f, log_n):
+    """ntt29.cuh (ntt_bfly: the 4p bias, eight lazy stages below 2^260, tight outputs) and the passes' value sequence (2^522 mod p
+    in, f29_reduce + f29_pack < 2^255.1 between passes, the twist, out_c and fe_cond_sub out) with every bound asserted: the host
+    model of the wave-resident plans of 2^12..2^18 (two and three passes, ns 5..8) = the oracle, forward and inverse, on random
+    inputs; the structured and extreme inputs of the GPU tests at one size per plan family."""
+    from tests import ntt_cases as NC
+
+    L = H.lib()
+    L.hh_f29_checks_active.restype = ctypes.c_int
+    assert L.hh_f29_checks_active() == 1
+    n = 1 << log_n
+    a = C.synth_scalars(f, 3, 0, n)
+    assert np.array_equal(_ntt_wave(f, a, log_n), C.ntt(f, a))
+    assert np.array_equal(_ntt_wave(f, a, log_n, True), C.ntt(f, a, True))
+    if log_n in (12, 15, 17):
+        cases = [(name, make()) for name, make in NC.extreme_inputs(f, log_n).items()]
+        cases += [(name, NC.structured_array(n, kind, v)) for name, kind, v in NC.structured_specs(f, log_n)]
+        rnd = C.synth_scalars(f, 4, 0, n)
+        for bit in (0, log_n - 1, 7):  # one side of a last stage zero, the other random: a small u against a large w v
+            z = rnd.copy()
+            z[(np.arange(n) >> bit) & 1 == 0] = 0
+            cases.append((f"zero_where_bit_{bit}_clear", z))
+        for name, x in cases:
+            assert np.array_equal(_ntt_wave(f, x, log_n), C.ntt(f, x)), name
+            assert np.array_equal(_ntt_wave(f, x, log_n, True), C.ntt(f, x, True)), name
+
+
+@pytest.mark.parametrize("f", [0, 1])
+def test_ntt_butterfly_worst_operands(f):
+    """ntt_bfly's add / subtract half fed its claimed worst operands under the bound assertions: a product just below 2^255 + p with
+    every limb below the top at 2^29 - 1, against a u already at the eight-stage bound (and against u = 0); the results are the
+    integers u + x and u + 4p - x (so the 4p bias never underflows) with tight limbs.  And a product whose top limb exceeds the
+    bias's - what a lazily reduced twiddle produced - is refused."""
+    import subprocess
+    import sys
+
+    p = R.modulus(f)
+    M = (1 << 29) - 1
+    low = (1 << 232) - 1                                  # limbs 0..7 all ones
+    x = (((1 << 255) + p - 1 - low) >> 232 << 232) | low  # just below 2^255 + p
+    assert x < (1 << 255) + p and (x >> 232) > 0
+    limbs = lambda v: np.array([(v >> (29 * i)) & M if i < 8 else v >> 232 for i in range(9)], dtype=np.uint32)  # noqa: E731
+    value = lambda l: sum(int(w) << (29 * i) for i, w in enumerate(l))  # noqa: E731
+    # the largest u eight stages can leave: the first pass's product < 2^255 + p, then + 4p per stage (u + 4p - x with x ~ 0)
+    u_hi = (1 << 255) + p - 1 + 7 * 4 * p
+    u_hi = ((u_hi >> 232) << 232) | low
+    assert u_hi < 1 << 260
+    for u in (u_hi, 0, (1 << 254) + 12345):
+        ou, ov = np.zeros(9, dtype=np.uint32), np.zeros(9, dtype=np.uint32)
+        H.lib().hh_ntt_bfly_x(f, vp(limbs(u)), vp(limbs(x)), 1, vp(ou), vp(ov))
+        assert value(ou) == u + x and value(ov) == u + 4 * p - x, hex(u)
+        assert all(w <= M for w in ou) and all(w <= M for w in ov)
+    # eight stages on the same u with the largest product each time: u grows by x per stage and stays below 2^260
+    ou, ov = np.zeros(9, dtype=np.uint32), np.zeros(9, dtype=np.uint32)
+    u0 = (1 << 255) + p - 1
+    H.lib().hh_ntt_bfly_x(f, vp(limbs(u0)), vp(limbs(x)), 8, vp(ou), vp(ov))
+    assert value(ou) == u0 + 8 * x and value(ov) == u0 + 7 * x + 4 * p - x
+    # a product above the bias's top limb (3 * 2^255, tight limbs) aborts the harness build (in a child process: abort() ends it)
+    bad = limbs(3 << 255)
+    code = ("import ctypes, numpy as np; from tests import host_harness as H; L = H.lib(); o = np.zeros(9, dtype=np.uint32); "
+            f"u = np.zeros(9, dtype=np.uint32); x = np.array({bad.tolist()}, dtype=np.uint32); "
+            f"L.hh_ntt_bfly_x({f}, u.ctypes.data_as(ctypes.c_void_p), x.ctypes.data_as(ctypes.c_void_p), 1, o.ctypes.data_as(ctypes.c_void_p), "
+            "o.ctypes.data_as(ctypes.c_void_p))")
+    import os
+
+    r = subprocess.run([sys.executable, "-c", code], cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), capture_output=True, text=True)
+    assert r.returncode == -6, (r.returncode, r.stdout, r.stderr)  # SIGABRT from F29_ASSERT (its message is lost in stdio's buffer)
