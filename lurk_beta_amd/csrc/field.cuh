@@ -158,6 +158,30 @@ LURK_HD uint32_t subb32(uint32_t a, uint32_t b, uint32_t& borrow) {
 #endif
 }
 
+// LURK_FE_CHECK (host builds of the test harness only): fe_mul, fe_add and fe_sub abort on an operand >= p.  Every caller owes
+// them canonical operands: fe_mul_asm's raw output is < 2p only for a, b < p (one conditional subtraction follows), and fe_add /
+// fe_sub reduce with a single conditional subtraction / addition of p.
+#if defined(LURK_FE_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+#define FE_CHECKS_ACTIVE 1
+}  // namespace lurk
+#include <cstdio>
+#include <cstdlib>
+namespace lurk {
+template <class P>
+inline void fe_assert_canonical(const uint32_t* v, const char* what) {
+    for (int i = 7; i >= 0; i--) {
+        if (v[i] < P::mod(i)) return;
+        if (v[i] > P::mod(i)) break;
+    }
+    fprintf(stderr, "Fe contract violated: %s operand >= p\n", what);
+    abort();
+}
+#define FE_ASSERT_CANONICAL(P, x, what) fe_assert_canonical<P>((x).l, what)
+#else
+#define FE_CHECKS_ACTIVE 0
+#define FE_ASSERT_CANONICAL(P, x, what) ((void)0)
+#endif
+
 // r = a - MOD if a >= MOD (a < 2*MOD)
 template <class P>
 LURK_HD void fe_cond_sub(uint32_t* t) {
@@ -171,6 +195,8 @@ LURK_HD void fe_cond_sub(uint32_t* t) {
 
 template <class P>
 LURK_HD Fe<P> fe_add(const Fe<P>& a, const Fe<P>& b) {
+    FE_ASSERT_CANONICAL(P, a, "fe_add");
+    FE_ASSERT_CANONICAL(P, b, "fe_add");
     Fe<P> r;
     uint32_t c = 0;
 #pragma unroll
@@ -180,6 +206,8 @@ LURK_HD Fe<P> fe_add(const Fe<P>& a, const Fe<P>& b) {
 }
 template <class P>
 LURK_HD Fe<P> fe_sub(const Fe<P>& a, const Fe<P>& b) {
+    FE_ASSERT_CANONICAL(P, a, "fe_sub");
+    FE_ASSERT_CANONICAL(P, b, "fe_sub");
     Fe<P> r;
     uint32_t borrow = 0;
 #pragma unroll
@@ -401,6 +429,8 @@ __device__ __attribute__((noinline)) Fe<P> fe_mul_call(Fe<P> a, Fe<P> b) {
 #endif
 template <class P>
 LURK_HD Fe<P> fe_mul(const Fe<P>& a, const Fe<P>& b) {
+    FE_ASSERT_CANONICAL(P, a, "fe_mul");
+    FE_ASSERT_CANONICAL(P, b, "fe_mul");
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(LURK_MUL_FORCE_INLINE)
     return fe_mul_call<P>(a, b);
 #else

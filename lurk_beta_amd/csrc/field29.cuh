@@ -10,7 +10,8 @@
 //   "tight"  every limb < 2^29   (products' outputs, f29_carry outputs, converted inputs)
 //   "loose"  every limb < 2^31   (limb-wise sums / differences of tight values)
 // f29_mul needs one operand tight and the other loose (or both with limbs < 2^30): 9 * 2^60 + 9 * 2^58
-// + carry < 2^64.  Nothing at the C ABI changes: values cross into this layer with f29_from_mont256
+// + carry < 2^64.  Its output value is a*b / 2^261 + (< p): limbs 0..7 are always tight, the top limb is tight when
+// a*b < 2^261 (2^261 - p), e.g. both operands < 2^261 and one < 2^260 (two all-ones tight operands give a top limb >= 2^29).  Nothing at the C ABI changes: values cross into this layer with f29_from_mont256
 // (x * 2^256 -> x * 2^261 is a 5-bit shift, folded into the limb repacking) and leave it with
 // f29_to_mont256 (one product with 2^256, then a canonical reduction).
 #pragma once
@@ -99,7 +100,8 @@ LURK_HD F29<P> f29_add(const F29<P>& a, const F29<P>& b) {
 }
 // BIAS = 64p with its limbs re-balanced so that limbs 0..7 lie in [2^30, 2^30 + 2^29) and the top limb is
 // ~2^28: limb_i += 2^30 and limb_{i+1} -= 2 (2^30 * 2^(29 i) = 2 * 2^(29 (i+1))).  Subtracting limb-wise any
-// b with limbs < 2^30 and value < 2^260 then never underflows.
+// b whose limbs are at most the bias's never underflows: limbs 0..7 <= 2^30 - 2, and the top limb at most 2^28 - 2 (Pasta) or
+// 0xc19139a (BN254), e.g. b tight with value < 2^259.5.
 template <class P>
 LURK_HD constexpr uint32_t f29_bias(int i) {
     uint64_t carry = 0;
@@ -115,8 +117,8 @@ LURK_HD constexpr uint32_t f29_bias(int i) {
     if (i > 0) v -= 2u;        // ... what limb i-1 borrowed from it
     return v;
 }
-// a - b (mod p, lazily).  Contract: limbs(b) < 2^30, b < 2^260; a arbitrary with limbs < 2^29 (tight) or
-// < 2^30: result limbs < 2^31 (loose), value < a + 2^260.
+// a - b (mod p, lazily).  Contract: every limb of b at most the matching bias limb (above; asserted under LURK_F29_CHECK);
+// a tight: result limbs < 2^31 (loose); a with limbs < 2^30: limbs < 2^31 + 2^29.  Value a - b + 64p <= a + 64p.
 template <class P>
 LURK_HD F29<P> f29_sub(const F29<P>& a, const F29<P>& b) {
     F29<P> r;
@@ -189,7 +191,8 @@ LURK_HD F29<P> f29_sqr(const F29<P>& a) {
 #endif
 }
 
-// a^(p-2): the inverse in the Montgomery(2^261) domain (0 -> 0).  a tight; result tight.  Square-and-multiply over the bits of
+// a^(p-2): the inverse in the Montgomery(2^261) domain (0 -> 0).  a tight with value < 2^260 (the squarings then stay below
+// 2^259 + p; from about 2^261 on they grow without bound); result tight.  Square-and-multiply over the bits of
 // p - 2, the same in every lane: 254 squarings and one product per set bit (the Pasta primes are 2^254 + a 126-bit tail, so ~65).
 // On a lane this is ~0.15 ms where the 8 x 32 fe_inv takes ~0.6 (one wave per SIMD, dependent products).
 template <class P>

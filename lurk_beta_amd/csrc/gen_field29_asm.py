@@ -8,7 +8,8 @@ r01_microbench_instr_rates.txt).  With 29-bit limbs a column of <= 9 + 6 partial
 104 mad+fold pairs for the Pasta moduli, and additions/subtractions become limb-wise (no carry chains,
 values kept lazily in [0, 2^261)).
 
-Emitted per field: one asm block  t = a*b / 2^261 mod p  (t limbs < 2^29, value < 2p+).
+Emitted per field: one asm block  t = a*b / 2^261 mod p, value a*b / 2^261 + (< p): limbs 0..7 < 2^29, the top limb takes the rest
+(< 2^29 when a*b < 2^261 (2^261 - p)).
 Contract: every limb of a and b < 2^30 (so a value may be the limb-wise sum of two normalised ones).
 """
 import sys
@@ -85,7 +86,7 @@ def gen_mul(modulus, square=False):
             L.append(f"v_and_b32 {T(k - 9)}, v{MASK_VGPR}, v{ACC_LO}")
         if k < 16:
             L.append(f"v_lshrrev_b64 v[{ACC_LO}:{ACC_HI}], {W}, v[{ACC_LO}:{ACC_HI}]")
-    # the top output limb takes everything that is left (value < 2^261 => fits)
+    # the top output limb takes everything that is left (< 2^32 for operands within the column contract)
     L.append(f"v_lshrrev_b64 v[{ACC_LO}:{ACC_HI}], {W}, v[{ACC_LO}:{ACC_HI}]")
     L.append(f"v_mov_b32 {T(8)}, v{ACC_LO}")
     return L, p, inv

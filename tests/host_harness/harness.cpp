@@ -4,6 +4,8 @@
 // every limb / accumulator bound the radix-2^29 layer relies on is asserted at run time in this host build: the switch has to
 // precede the FIRST inclusion of field29.cuh (poseidon29.cuh pulls it in)
 #define LURK_F29_CHECK 1
+// and every fe_mul / fe_add / fe_sub operand must be canonical (< p)
+#define LURK_FE_CHECK 1
 #include <stddef.h>
 #include <vector>
 #include "../../lurk_beta_amd/csrc/field.cuh"
@@ -56,7 +58,8 @@ static void fe_inv_both(const uint32_t* a, uint32_t* o_host, uint32_t* o_pow, si
     for (size_t i = 0; i < n; i++) {
         Fe<F> x;
         for (int k = 0; k < 8; k++) x.l[k] = a[8 * i + k];
-        const Fe<F> h = fe_inv<F>(x), q = fe_inv_pow<F>(x);
+        // the exponentiation owes its fe_mul canonical operands: a raw non-canonical pattern only goes to the host inverse
+        const Fe<F> h = fe_inv<F>(x), q = fe_canonical_ge_mod<F>(x.l) ? fe_zero<F>() : fe_inv_pow<F>(x);
         for (int k = 0; k < 8; k++) { o_host[8 * i + k] = h.l[k]; o_pow[8 * i + k] = q.l[k]; }
     }
 }
@@ -272,6 +275,7 @@ extern "C" void hh_curve_tree(int curve, const uint32_t* bases, const uint32_t* 
 // 1 when the bound assertions of field29.cuh / curve29.cuh are compiled in (they silently were not while another header pulled
 // field29.cuh in ahead of the switch)
 extern "C" int hh_f29_checks_active() { return F29_CHECKS_ACTIVE; }
+extern "C" int hh_fe_checks_active() { return FE_CHECKS_ACTIVE; }
 extern "C" void hh_curve_sum(int curve, int mode, const uint32_t* bases, const uint32_t* signs, size_t n, uint32_t* out) {
     if (curve == 0) curve_sum<PallasFp>(mode, bases, signs, n, out);
     else curve_sum<PallasFq>(mode, bases, signs, n, out);

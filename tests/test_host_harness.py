@@ -1,6 +1,7 @@
 """CPU-only: the library's host/device arithmetic headers (compiled with g++ by tests/host_harness)
 and its host-side Poseidon parameter generation, against the oracle."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -538,3 +539,26 @@ def test_ntt_butterfly_worst_operands(f):
 
     r = subprocess.run([sys.executable, "-c", code], cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), capture_output=True, text=True)
     assert r.returncode == -6, (r.returncode, r.stdout, r.stderr)  # SIGABRT from F29_ASSERT (its message is lost in stdio's buffer)
+
+
+def test_fe_contract_check_is_compiled_in_and_fires():
+    """LURK_FE_CHECK: in the harness build fe_mul, fe_add and fe_sub abort on an operand >= p, so every harness mode above runs its
+    callers (curve group law, sumcheck_host.hpp, keyfold_plan.hpp, ...) with the 8 x 32 input contract asserted."""
+    import subprocess
+    import sys
+
+    L = H.lib()
+    L.hh_fe_checks_active.restype = ctypes.c_int
+    assert L.hh_fe_checks_active() == 1
+    prog = ("import ctypes, numpy as np; from oracle import coracle as C; from oracle import pyref as R; from tests import host_harness as H;"
+            "vp = lambda a: a.ctypes.data_as(ctypes.c_void_p); f, op, x = {f}, {op}, {x};"
+            "A = C.ints_to_limbs([1, x]); B = C.ints_to_limbs([1, 1]); O = np.zeros_like(A);"
+            "H.lib().hh_fe_op(f, op, vp(A), vp(B), vp(O), ctypes.c_size_t(2))")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for f in (0, 2):
+        p = R.modulus(f)
+        for op, x, fires in ((0, p, True), (1, p, True), (2, p + 1, True), (0, p - 1, False)):  # fe_mul, fe_add, fe_sub
+            r = subprocess.run([sys.executable, "-c", prog.format(f=f, op=op, x=x)], cwd=root, capture_output=True, text=True, timeout=120)
+            assert r.returncode == (-6 if fires else 0), (f, op, r.returncode, r.stderr[-500:])
+            if fires:
+                assert "Fe contract violated" in r.stderr, r.stderr[-500:]
