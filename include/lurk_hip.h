@@ -53,10 +53,12 @@ int lurk_hip_device_count(void);
 const char* lurk_hip_last_error(void);
 const char* lurk_hip_version(void);
 /* The ABI revision this header describes; lurk_hip_abi_version() is what the loaded library was built from (a binding compares the
- * two at start-up).  2 (round 6): lurk_hip_msm_ctx_info's *precomputed is a boolean (the key's form comes from lurk_hip_msm_ctx_form),
+ * two at start-up).  A revision that only adds entry points raises the number too: a binding built against revision n runs on any library
+ * that reports >= n until a revision says otherwise.  3: lurk_hip_slot_constraints_size / lurk_hip_slot_constraints,
+ * lurk_hip_frames_r1cs_create, lurk_hip_r1cs_is_sat_dev (additions only).  2 (round 6): lurk_hip_msm_ctx_info's *precomputed is a boolean (the key's form comes from lurk_hip_msm_ctx_form),
  * LURK_MSM_SLOTS is 6, LURK_MSM_SUBMIT_FOLLOW, the parameter blocks lurk_hip_ro_params / lurk_hip_ck_params, lurk_hip_scratch_trim.
  * 1: rounds 1-4 (*precomputed returned the form 0 / 1 / 2, four slots). */
-#define LURK_HIP_ABI_VERSION 2
+#define LURK_HIP_ABI_VERSION 3
 int lurk_hip_abi_version(void);
 /* Prover scratch (the compressing SNARK's sum-check tables, eq tables, opening-argument halves) comes from one stack arena per
  * (device, stream) that grows by blocks of >= 256 MiB and is KEPT between proofs: about 2 GB per stream that has run a 2^20-row proof,
@@ -367,6 +369,33 @@ int lurk_hip_frames_witness_dev(int field_id, size_t num_frames, const size_t* c
 int lurk_hip_witness_blocks_dev(void* d_w, size_t first, size_t stride, const void* src, int src_on_host, size_t n_blocks,
                                 size_t block_len, void* stream);
 
+/* The constraint rows of one slot: what neptune's circuit2::poseidon_hash_allocated (three rows per S-box - l * l = l2, l2 * l2 = l4,
+ * l4 * l = l5k - key, the S-box inputs being linear combinations carried through the linear layers - and the digest's ensure_allocated
+ * row) and bellpepper's to_bits_le_strict (a boolean row per bit, the AND chains, the unpacking row) enforce on the block
+ * lurk_hip_slot_witness* writes, as three CSR matrices {indptr (num_cons + 1), indices, data (32 B Montgomery)} like lurk_hip_r1cs_create
+ * takes.  Local column k < size is element k of the slot's block, local column `size` (lurk_hip_slot_witness_size) is the constant
+ * ONE.  Rows in the gadget's emission order, columns ascending within a row, no coefficient that reduces to zero; an empty linear
+ * combination (the boolean rows' C) is an empty CSR row.  Host-only like lurk_hip_slot_witness_size; every output is required. */
+int lurk_hip_slot_constraints_size(int field_id, int slot_type, size_t* num_cons, size_t* nnz_a, size_t* nnz_b, size_t* nnz_c);
+int lurk_hip_slot_constraints(int field_id, int slot_type, uint64_t* a_indptr, uint64_t* a_indices, void* a_data, uint64_t* b_indptr,
+                              uint64_t* b_indices, void* b_data, uint64_t* c_indptr, uint64_t* c_indices, void* c_data);
+/* A resident shape (as lurk_hip_r1cs_create makes) of every slot row of a MultiFrame at the layout lurk_hip_frames_witness_dev writes:
+ * rows frame-major, within a frame the slots in that call's order (hash4, hash6, hash8, commitment, bit_decomp; counts5 per frame), each
+ * slot's rows relocated to its block (first + f * frame_len + the slot's offset); ONE maps to column num_vars - the u position of
+ * z = [W | u | X], so constants relax with u as in Nova.  The caller's extra_cons further rows (the non-slot body of the circuit, which
+ * CPU synthesis still produces; nine CSR pointers over the num_vars + 1 + num_io columns, all NULL when extra_cons == 0) are appended
+ * unchanged after the slot rows.  The result is an ordinary lurk_hip_r1cs: multiply_vec, cross_term, cross_term_cached, is_sat,
+ * lurk_hip_fold_ctx_create and lurk_hip_spartan_prove_dev take it as they take any shape; destroy it with lurk_hip_r1cs_destroy.
+ * Refused before any allocation: a block that would reach past num_vars, a count that overflows, an unknown field.
+ * The ORDER of the slot rows relative to the rest of lurk-beta's real circuit is unpinned: the reference holds no vector for it (as
+ * for the aux order of the slot blocks).  The call is for checking a traced W, for benchmarking on the slot gadgets' real row mix and
+ * for cross-checking a host's own shape; it does not replace the host's R1CSShape. */
+typedef struct lurk_hip_r1cs lurk_hip_r1cs;
+int lurk_hip_frames_r1cs_create(lurk_hip_r1cs** shape, int field_id, size_t num_frames, const size_t* counts5, size_t first,
+                                size_t frame_len, size_t num_vars, size_t num_io, size_t extra_cons, const uint64_t* xa_indptr,
+                                const uint64_t* xa_indices, const void* xa_data, const uint64_t* xb_indptr, const uint64_t* xb_indices,
+                                const void* xb_data, const uint64_t* xc_indptr, const uint64_t* xc_indices, const void* xc_data);
+
 /* ---- NTT ---------------------------------------------------------------------------------
  * No reference counterpart: radix-2 NTT over a Pasta field, natural order in
  * and out, omega = 5^((p-1)/2^32)^(2^(32-log_n)); inverse includes the 1/n scaling.  log_n <= 28; field_id 0 or 1.
@@ -384,7 +413,6 @@ int lurk_hip_ntt_dev(int field_id, void* d_inout, unsigned log_n, int inverse, v
  * indptr (num_cons + 1) x usize, indices nnz x usize (column into z = [W | u | X], i.e.
  * num_vars + 1 + num_io columns), data nnz x 32 B Montgomery.  Copied to the device at creation
  * (coefficients de-duplicated into a dictionary); the host arrays are only borrowed for the call. */
-typedef struct lurk_hip_r1cs lurk_hip_r1cs;
 int lurk_hip_r1cs_create(lurk_hip_r1cs** shape, int field_id, size_t num_cons, size_t num_vars,
                          size_t num_io, const uint64_t* a_indptr, const uint64_t* a_indices,
                          const void* a_data, const uint64_t* b_indptr, const uint64_t* b_indices,
@@ -412,6 +440,15 @@ int lurk_hip_r1cs_cross_term_dev(lurk_hip_r1cs* shape, const void* d_z1, const v
 int lurk_hip_r1cs_cross_term_cached_dev(lurk_hip_r1cs* shape, const void* d_z2, void* d_az1, void* d_bz1, void* d_cz1, const void* u1_32_mont,
                                         const void* d_az2_prev, const void* d_bz2_prev, const void* d_cz2_prev, const void* r_prev32_mont, void* d_t,
                                         void* d_az2, void* d_bz2, void* d_cz2, void* stream);
+/* R1CSShape::is_sat / is_sat_relaxed on the device: A z o B z == u * C z + E row by row, u = z[num_vars]; d_e == NULL means E = 0 (plain
+ * is_sat when u = 1).  n_unsat: rows that fail; first_unsat: the lowest failing row index (num_cons when none).  Host outputs; the call
+ * synchronises `stream`.  The three inner products of a row are formed and compared canonically in one pass - nothing is written per
+ * row, so a host no longer pulls 3 x num_cons x 32 B of lurk_hip_r1cs_multiply_vec_dev's output back to check an instance.  Rows are
+ * classed by length once per shape, on the first call (one lane per short row, a sub-wave group per mid-length row, 16 lanes per long
+ * row); checks of ONE shape run one after the other.  The shape must be resident on the calling thread's current device (d_z and d_e
+ * are that device's pointers): otherwise the call is refused with nothing launched. */
+int lurk_hip_r1cs_is_sat_dev(const lurk_hip_r1cs* shape, const void* d_z, const void* d_e, uint64_t* n_unsat, uint64_t* first_unsat,
+                             void* stream);
 /* RelaxedR1CSWitness::fold: out = a + r b over n elements (W1 + r W2, E1 + r T); r: 32 B Montgomery, host */
 int lurk_hip_fold_vec_dev(int field_id, const void* d_a, const void* d_b, const void* r32_mont, size_t n,
                           void* d_out, void* stream);

@@ -107,6 +107,9 @@ SIGNATURES = {
     "lurk_hip_slot_witness_dev": (c_int, [c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     "lurk_hip_slot_witness": (c_int, [c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "lurk_hip_frames_witness_dev": (c_int, [c_int, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "lurk_hip_slot_constraints_size": (c_int, [c_int, c_int] + [ctypes.POINTER(c_size_t)] * 4),
+    "lurk_hip_slot_constraints": (c_int, [c_int, c_int] + [c_void_p] * 9),
+    "lurk_hip_frames_r1cs_create": (c_int, [ctypes.POINTER(c_void_p), c_int, c_size_t, ctypes.POINTER(c_size_t), c_size_t, c_size_t, c_size_t, c_size_t, c_size_t] + [c_void_p] * 9),
     "lurk_hip_witness_blocks_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
     "lurk_hip_ntt": (c_int, [c_int, c_void_p, c_uint, c_int]),
     "lurk_hip_ntt_dev": (c_int, [c_int, c_void_p, c_uint, c_int, c_void_p]),
@@ -118,6 +121,7 @@ SIGNATURES = {
     "lurk_hip_r1cs_multiply_vec_dev": (c_int, [c_void_p] * 6),
     "lurk_hip_r1cs_cross_term_dev": (c_int, [c_void_p] * 5),
     "lurk_hip_r1cs_cross_term_cached_dev": (c_int, [c_void_p] * 15),
+    "lurk_hip_r1cs_is_sat_dev": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), c_void_p]),
     "lurk_hip_fold_vecs_dev": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
     "lurk_hip_fold_vec_dev": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "lurk_hip_r1cs_multiply_vec": (c_int, [c_void_p] * 5),

@@ -24,11 +24,10 @@
 #include <unordered_map>
 
 #include "common.hpp"
-#include "poseidon29.cuh"
+#include "r1cs_shape.cuh"
 
 namespace lurk {
 
-constexpr int FOLD_BLOCK = 256;
 
 // The cross term and the two folds are links of the step's serial chain (cross term -> commit(T) -> r -> folds -> next cross term) and
 // are bound by HBM latency, not by issue slots; what shares the device with them is an accumulation of the NEXT step's commit(W2)
@@ -36,57 +35,6 @@ constexpr int FOLD_BLOCK = 256;
 // measured round 6, a 60 us fold took 320 us and the cross term 590 instead of 410.  Raised wave priority lets these waves issue when
 // their loads come back (3: the class of commit(T)'s own short kernels; a followed commitment's tail runs at 2, accumulations at 0-1).
 __device__ __forceinline__ void fold_wave_prio() { __builtin_amdgcn_s_setprio(3); }
-
-struct CsrDev {
-    DevBuf rowptr;  // u32 x (rows + 1)
-    DevBuf ent;     // uint2 {col, coefficient id} x nnz
-    size_t nnz = 0;
-};
-
-struct R1csShape {
-    int field_id = 0;
-    size_t num_cons = 0, num_vars = 0, num_io = 0;
-    CsrDev m[3];
-    DevBuf dict;  // distinct coefficients, P29_STRIDE words each (canonical Montgomery-2^261 limbs)
-    size_t dict_size = 0;
-    DevBuf long_rows;  // u32 row ids with more than FOLD_LONG entries in A, B or C
-    size_t n_long = 0;
-    int device = 0;
-};
-
-// ---- rows --------------------------------------------------------------------------------------------------
-// Lazy accumulator of one row value: terms a*b (both tight) are added as unreduced 17-column products.
-// 45 products per column fit 64 bits: the columns are normalised every fourth term.  Every term adds < 2^253
-// to the value: every 64 terms the reduced partial sum re-enters as one term (times the Montgomery one) so that
-// rows of any length stay below 2^261.
-template <class P>
-struct RowAcc {
-    Dot29<P> acc;
-    uint32_t since, terms;
-};
-template <class P>
-__device__ __forceinline__ void row_init(RowAcc<P>& r) {
-    dot29_init<P>(r.acc);
-    r.since = 0;
-    r.terms = 0;
-}
-template <class P>
-__device__ __forceinline__ void row_mac(RowAcc<P>& r, const F29<P>& a, const F29<P>& b, const uint32_t* one29) {
-    if (r.terms == 64) {
-        F29<P> part = dot29_finish<P>(r.acc);
-        dot29_init<P>(r.acc);
-        dot29_mac<P>(r.acc, part, ld_const29<P>(one29));
-        r.terms = 1;
-        r.since = 1;
-    }
-    if (r.since == 4) {
-        dot29_carry<P>(r.acc);
-        r.since = 0;
-    }
-    dot29_mac<P>(r.acc, a, b);
-    r.since++;
-    r.terms++;
-}
 
 constexpr uint32_t FOLD_LONG = 32;  // rows with more entries (in any of A, B, C) go to the wave-per-row kernel
 // Measured in isolation at rc = 100 (bench_tools/fold_bench.py, round 6): a batch of 4 entries keeps 180-200 registers live (two waves
@@ -99,11 +47,6 @@ constexpr uint32_t FOLD_LONG = 32;  // rows with more entries (in any of A, B, C
 #define LURK_FOLD_MIN_WAVES 1  // (HIP: minimum waves per SIMD the cross-term kernels are compiled for)
 #endif
 constexpr int FOLD_BATCH = LURK_FOLD_BATCH;  // entries whose loads are issued together by one lane
-
-struct CsrView {
-    const uint32_t* rowptr;
-    const uint2* ent;
-};
 
 // one lane, one (short) row of one matrix, NV vectors: entries are fetched FOLD_BATCH at a time so that the
 // dependent loads (record -> coefficient, z values) of a batch are in flight together
@@ -194,31 +137,11 @@ __device__ __forceinline__ void fold_store(Fe<P>* dst, const F29<P>& v) {
     *dst = f29_to_mont256<P>(v);
 }
 
-struct R1csDev {
-    CsrView a, b, c;
-    const uint32_t* dict;
-    size_t dict_size;
-    size_t rows;
-    const uint32_t* long_rows;  // rows with > FOLD_LONG entries in A, B or C
-    uint32_t n_long;
-};
-
 __device__ __forceinline__ bool fold_is_long(const R1csDev& s, size_t row, uint32_t* lo, uint32_t* hi) {
     lo[0] = s.a.rowptr[row]; hi[0] = s.a.rowptr[row + 1];
     lo[1] = s.b.rowptr[row]; hi[1] = s.b.rowptr[row + 1];
     lo[2] = s.c.rowptr[row]; hi[2] = s.c.rowptr[row + 1];
     return hi[0] - lo[0] > FOLD_LONG || hi[1] - lo[1] > FOLD_LONG || hi[2] - lo[2] > FOLD_LONG;
-}
-
-// Workgroup -> row block, XCD-aware.  Consecutive workgroup ids go round the 8 XCDs (each with its own 4 MiB L2), and the rows of the
-// step circuit are frame-structured: a frame's rows gather almost only that frame's ~9 000 columns of z (multiframe.rs:699-702).  With
-// the identity mapping every XCD's L2 sees every frame's columns (each 32-byte element of z is fetched into up to 8 L2s); here XCD x
-// walks ONE contiguous eighth of the rows, so a frame's columns of z1 / z2 are fetched by one L2 and hit there for the rest of the
-// frame's rows.
-constexpr unsigned FOLD_XCDS = 8;
-__device__ __forceinline__ size_t fold_row_block(unsigned b, unsigned nblocks) {
-    const unsigned per = (nblocks + FOLD_XCDS - 1) / FOLD_XCDS;
-    return (size_t)(b % FOLD_XCDS) * per + b / FOLD_XCDS;
 }
 
 // LONG = false: one lane per row, long rows skipped;  LONG = true: FOLD_GROUP lanes per entry of long_rows
@@ -543,19 +466,6 @@ static void upload_matrix(R1csShape& sh, int which, const uint64_t* indptr, cons
     if (nnz) LURK_HIP_CHECK(hipMemcpy(m.ent.p, ent.data(), nnz * 8, hipMemcpyHostToDevice));
 }
 
-static R1csDev dev_view(const R1csShape& sh) {
-    R1csDev d;
-    d.a = CsrView{sh.m[0].rowptr.as<uint32_t>(), sh.m[0].ent.as<uint2>()};
-    d.b = CsrView{sh.m[1].rowptr.as<uint32_t>(), sh.m[1].ent.as<uint2>()};
-    d.c = CsrView{sh.m[2].rowptr.as<uint32_t>(), sh.m[2].ent.as<uint2>()};
-    d.dict = sh.dict.as<uint32_t>();
-    d.dict_size = sh.dict_size;
-    d.rows = sh.num_cons;
-    d.long_rows = sh.long_rows.as<uint32_t>();
-    d.n_long = (uint32_t)sh.n_long;
-    return d;
-}
-
 template <class P>
 static void multiply_vec(const R1csShape& sh, const void* d_z, void* az, void* bz, void* cz, hipStream_t s) {
     if (!sh.num_cons) return;
@@ -636,10 +546,6 @@ static void fold_vec(const void* a, const void* b, const void* r32, size_t n, vo
 }  // namespace lurk
 
 using namespace lurk;
-
-struct lurk_hip_r1cs {
-    R1csShape sh;  // immutable after creation: calls on one shape from any thread / stream are independent
-};
 
 extern "C" {
 

@@ -34,6 +34,51 @@ class R1CSShape:
         _lib.check(lib.lurk_hip_r1cs_create(ctypes.byref(self._h), field_id, num_cons, num_vars, num_io, *args))
         self._keep = None  # the library copied everything
 
+    @classmethod
+    def _wrap(cls, handle) -> "R1CSShape":
+        """An R1CSShape around a handle the library created."""
+        self = cls.__new__(cls)
+        self._h, self._keep = handle, None
+        f, dims = ctypes.c_int(), [ctypes.c_size_t() for _ in range(3)]
+        _lib.check(_lib.load().lurk_hip_r1cs_dims(handle, ctypes.byref(f), *[ctypes.byref(x) for x in dims]))
+        self.field_id, (self.num_cons, self.num_vars, self.num_io) = f.value, [x.value for x in dims]
+        return self
+
+    @classmethod
+    def for_frames(cls, field_id: int, num_frames: int, counts5, first: int, frame_len: int, num_vars: int, num_io: int, extra=None) -> "R1CSShape":
+        """The slot rows of a MultiFrame at the layout ``lurk_hip_frames_witness_dev`` writes (``lurk_hip_frames_r1cs_create``): counts5 per
+        frame in (hash4, hash6, hash8, commitment, bit_decomp) order, ONE at column num_vars.  extra = (A, B, C) CSR triples of the caller's
+        further rows over the same columns, appended after the slot rows.  The slot rows' order relative to the rest of lurk-beta's real
+        circuit is unpinned: for checking, benchmarking and cross-checking a host's own shape."""
+        counts = (ctypes.c_size_t * 5)(*[int(c) for c in counts5])
+        keep, args, extra_cons = [], [None] * 9, 0
+        if extra is not None:
+            extra_cons = len(extra[0][0]) - 1
+            args = []
+            for indptr, indices, data in extra:
+                ip = np.ascontiguousarray(indptr, dtype=np.uint64)
+                ix = np.ascontiguousarray(indices, dtype=np.uint64)
+                dv = np.ascontiguousarray(data, dtype=np.uint64)
+                if ip.size != extra_cons + 1 or ix.size * 4 != dv.size:
+                    raise ValueError("malformed CSR matrix")
+                keep += [ip, ix, dv]
+                args += [_lib.ptr(ip), _lib.ptr(ix), _lib.ptr(dv)]
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().lurk_hip_frames_r1cs_create(ctypes.byref(h), field_id, num_frames, counts, first, frame_len, num_vars, num_io, extra_cons,
+                                                           *[a if a is not None else _lib.ptr(None) for a in args]))
+        return cls._wrap(h)
+
+    def is_sat(self, d_z, d_e=None, stream=None):
+        """(n_unsat, first_unsat) of A z o B z == u C z + E, u = z[num_vars]; d_e None: E = 0 (R1CSShape::is_sat / is_sat_relaxed).
+        first_unsat is num_cons when every row holds.  Synchronises the stream."""
+        import torch
+
+        assert d_z.is_cuda and d_z.shape[0] == self.num_cols and (d_e is None or (d_e.is_cuda and d_e.shape[0] == self.num_cons))
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        n, first = ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(_lib.load().lurk_hip_r1cs_is_sat_dev(self._h, _lib.ptr(d_z), _lib.ptr(d_e), ctypes.byref(n), ctypes.byref(first), _lib.ptr(s)))
+        return n.value, first.value
+
     @property
     def num_cols(self) -> int:
         return self.num_vars + 1 + self.num_io

@@ -5,7 +5,8 @@
 //   lurk::host::PoseidonCache   <- PoseidonCache<F>::hash3/4/6/8, compute_hash  (/root/reference/src/hash.rs:86-204)
 //   lurk::host::Trie            <- coprocessor::trie::Trie<F, 8, HEIGHT>        (/root/reference/src/coprocessor/trie/mod.rs:328-800)
 //   lurk::host::CommitmentKey   <- arecibo CommitmentKey + CE::commit(ck, v)     (callers /root/reference/src/proof/nova.rs:287-293)
-//   lurk::host::R1CSShape       <- arecibo R1CSShape::multiply_vec / commit_T cross term / witness fold (nova.rs:291-293)
+//   lurk::host::R1CSShape       <- arecibo R1CSShape::multiply_vec / commit_T cross term / witness fold (nova.rs:291-293), is_sat / is_sat_relaxed
+//   lurk::host::MultiFrame      <- the slot part of a MultiFrame's W (multiframe.rs:520-592, 699-702): layout, slot_shape (the slot rows)
 //
 // Field elements are 32-byte canonical little-endian values (Fe); points use the repr-c layouts.
 #pragma once
@@ -239,6 +240,13 @@ class R1CSShape {
         check(lurk_hip_r1cs_cross_term(h_, z1.data(), z2.data(), t.data()));
         return t;
     }
+    // R1CSShape::is_sat / is_sat_relaxed on the device: {failing rows, lowest failing row (num_cons when none)} of A z o B z == u C z + E;
+    // d_z / d_e: the current device's memory (d_e == nullptr: E = 0); synchronises `stream`
+    std::pair<uint64_t, uint64_t> is_sat(const void* d_z, const void* d_e = nullptr, void* stream = nullptr) const {
+        uint64_t n = 0, first = 0;
+        check(lurk_hip_r1cs_is_sat_dev(h_, d_z, d_e, &n, &first, stream));
+        return {n, first};
+    }
     // a + r b
     std::vector<Fe> fold(const std::vector<Fe>& a, const std::vector<Fe>& b, const Fe& r) const {
         if (a.size() != b.size()) throw std::invalid_argument("length mismatch");
@@ -247,6 +255,12 @@ class R1CSShape {
         return out;
     }
 
+    // wraps a shape the library created (MultiFrame::slot_shape)
+    explicit R1CSShape(lurk_hip_r1cs* h) : h_(h) {
+        size_t nio = 0;
+        check(lurk_hip_r1cs_dims(h, &field_, &num_cons_, &num_vars_, &nio));
+        num_cols_ = num_vars_ + 1 + nio;
+    }
     lurk_hip_r1cs* handle() const { return h_; }
     size_t num_cons() const { return num_cons_; }
     size_t num_cols() const { return num_cols_; }
@@ -271,6 +285,47 @@ inline std::vector<Fe> slot_witness(int field_id, int slot_type, const std::vect
     check(lurk_hip_slot_witness(field_id, slot_type, preimages.data(), n, preimages_mont ? 1 : 0, out.data()));
     return out;
 }
+// the constraint rows one slot's gadget enforces on its block (lurk_hip_slot_constraints): A, B, C; local column `size` is ONE.  Host-only.
+inline std::array<SparseMatrix, 3> slot_constraints(int field_id, int slot_type) {
+    size_t rows = 0, nnz[3] = {0, 0, 0};
+    check(lurk_hip_slot_constraints_size(field_id, slot_type, &rows, &nnz[0], &nnz[1], &nnz[2]));
+    std::array<SparseMatrix, 3> m;
+    for (int w = 0; w < 3; w++) {
+        m[w].indptr.resize(rows + 1);
+        m[w].indices.resize(nnz[w]);
+        m[w].data.resize(nnz[w]);
+    }
+    check(lurk_hip_slot_constraints(field_id, slot_type, m[0].indptr.data(), m[0].indices.data(), m[0].data.data(), m[1].indptr.data(), m[1].indices.data(),
+                                    m[1].data.data(), m[2].indptr.data(), m[2].indices.data(), m[2].data.data()));
+    return m;
+}
+// The layout of one MultiFrame's W = [globals | frame 0 | ...], frame = [slot blocks | body], as lurk_hip_frames_witness_dev writes it
+// (counts5: hash4, hash6, hash8, commitment, bit_decomp per frame), and the resident shape of its slot rows.
+struct MultiFrame {
+    int field_id;
+    size_t num_frames, globals_len, body_len;
+    std::array<size_t, 5> counts5;
+    size_t slots_len() const {
+        static const int types[5] = {LURK_SLOT_HASH4, LURK_SLOT_HASH6, LURK_SLOT_HASH8, LURK_SLOT_COMMITMENT, LURK_SLOT_BIT_DECOMP};
+        size_t n = 0;
+        for (int k = 0; k < 5; k++) n += counts5[k] ? counts5[k] * slot_witness_size(field_id, types[k]) : 0;
+        return n;
+    }
+    size_t frame_len() const { return slots_len() + body_len; }
+    size_t w_len() const { return globals_len + num_frames * frame_len(); }
+    // lurk_hip_frames_r1cs_create at this layout: ONE at column w_len; extra = further rows (A, B, C), appended after the slot rows.  The
+    // slot rows' order relative to the rest of lurk-beta's circuit is unpinned: for checking, benchmarking, cross-checking a host's shape.
+    std::unique_ptr<R1CSShape> slot_shape(size_t num_io, const std::array<SparseMatrix, 3>* extra = nullptr) const {
+        lurk_hip_r1cs* h = nullptr;
+        const size_t xc = extra ? (*extra)[0].indptr.size() - 1 : 0;
+        auto ip = [&](int w) { return extra ? (*extra)[w].indptr.data() : nullptr; };
+        auto ix = [&](int w) { return extra ? (*extra)[w].indices.data() : nullptr; };
+        auto dv = [&](int w) { return extra ? (const void*)(*extra)[w].data.data() : nullptr; };
+        check(lurk_hip_frames_r1cs_create(&h, field_id, num_frames, counts5.data(), globals_len, frame_len(), w_len(), num_io, xc, ip(0), ix(0), dv(0), ip(1), ix(1),
+                                          dv(1), ip(2), ix(2), dv(2)));
+        return std::unique_ptr<R1CSShape>(new R1CSShape(h));
+    }
+};
 // StoreCore::hydrate_z_cache (/root/reference/src/lem/store_core.rs:256-269) over a topologically ordered node array
 inline std::vector<Fe> store_hydrate(int field_id, const std::vector<lurk_hip_store_node>& nodes, const std::vector<Fe>& values, size_t* levels = nullptr) {
     std::vector<Fe> digests(nodes.size());

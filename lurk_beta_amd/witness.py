@@ -43,6 +43,18 @@ def slot_witness(field_id: int, slot_type: int, preimages: np.ndarray, mont: boo
     return out
 
 
+def slot_constraints(field_id: int, slot_type: int):
+    """The R1CS rows one slot's gadget enforces on its block (``lurk_hip_slot_constraints``): three CSR triples (indptr, indices, data) for
+    A, B, C; local column k < size is element k of the block, column ``size`` the constant ONE; data (nnz, 4) u64 Montgomery.  Host
+    computation: needs no GPU."""
+    lib = _lib.load()
+    v = [ctypes.c_size_t() for _ in range(4)]
+    _lib.check(lib.lurk_hip_slot_constraints_size(field_id, slot_type, *[ctypes.byref(x) for x in v]))
+    out = [(np.zeros(v[0].value + 1, dtype=np.uint64), np.zeros(v[1 + k].value, dtype=np.uint64), np.zeros((v[1 + k].value, 4), dtype=np.uint64)) for k in range(3)]
+    _lib.check(lib.lurk_hip_slot_constraints(field_id, slot_type, *[_lib.ptr(a) for m in out for a in m]))
+    return tuple(out)
+
+
 class MultiFrameWitness:
     """Layout of one MultiFrame's aux vector W = [globals | frame 0 | ... | frame rc-1], frame = [slot blocks | body], and
     its assembly on the device.  The layout is fixed for a proof (same step circuit every step), so the per-slot offsets
@@ -104,3 +116,11 @@ class MultiFrameWitness:
                                                        self.body_len, _lib.ptr(s)))
             self._keep_b = b
         return d_w
+
+    def r1cs(self, num_io: int, extra=None):
+        """The resident shape of this MultiFrame's slot rows at its own layout (``R1CSShape.for_frames``): num_vars = w_len, ONE at column
+        w_len; extra = (A, B, C) CSR triples of further rows (the non-slot body), appended after the slot rows."""
+        from .fold import R1CSShape
+
+        return R1CSShape.for_frames(self.field_id, self.num_frames, [self.counts.get(name, 0) for name, _ in SLOT_ORDER], self.globals_len, self.frame_len,
+                                    self.w_len, num_io, extra)

@@ -148,9 +148,57 @@ impl R1csShape {
         })?;
         Ok(Self(p))
     }
+    /// The slot rows of a MultiFrame at the layout `lurk_hip_frames_witness_dev` writes (`lurk_hip_frames_r1cs_create`): `counts5` per frame
+    /// in (hash4, hash6, hash8, commitment, bit_decomp) order, ONE at column `num_vars`; `extra` = the caller's further rows (A, B, C over the
+    /// same columns), appended after the slot rows.  The slot rows' order relative to the rest of lurk-beta's real circuit is unpinned: for
+    /// checking, benchmarking and cross-checking a host's own shape.
+    #[allow(clippy::too_many_arguments)]
+    pub fn for_frames(field_id: c_int, num_frames: usize, counts5: &[usize; 5], first: usize, frame_len: usize, num_vars: usize, num_io: usize,
+                      extra: Option<(Csr, Csr, Csr)>) -> Result<Self, Error> {
+        let mut p = core::ptr::null_mut();
+        let null = core::ptr::null::<u64>();
+        check(unsafe {
+            match extra {
+                Some((a, b, c)) => lurk_hip_frames_r1cs_create(&mut p, field_id, num_frames, counts5.as_ptr(), first, frame_len, num_vars, num_io, a.indptr.len().saturating_sub(1),
+                                                               a.indptr.as_ptr(), a.indices.as_ptr(), a.data.as_ptr().cast(), b.indptr.as_ptr(), b.indices.as_ptr(),
+                                                               b.data.as_ptr().cast(), c.indptr.as_ptr(), c.indices.as_ptr(), c.data.as_ptr().cast()),
+                None => lurk_hip_frames_r1cs_create(&mut p, field_id, num_frames, counts5.as_ptr(), first, frame_len, num_vars, num_io, 0, null, null, null.cast(), null, null,
+                                                    null.cast(), null, null, null.cast()),
+            }
+        })?;
+        Ok(Self(p))
+    }
+    /// `R1CSShape::is_sat` / `is_sat_relaxed` on the device: (failing rows, lowest failing row - `num_cons` when none) of
+    /// A z o B z == u C z + E; `d_e` null: E = 0.  Synchronises `stream`.
+    /// # Safety
+    /// `d_z`: `num_vars + 1 + num_io` Montgomery scalars in the current device's memory, `d_e`: `num_cons` of them or null.
+    pub unsafe fn is_sat(&self, d_z: *const c_void, d_e: *const c_void, stream: *mut c_void) -> Result<(u64, u64), Error> {
+        let (mut n, mut first) = (0u64, 0u64);
+        check(lurk_hip_r1cs_is_sat_dev(self.0, d_z, d_e, &mut n, &mut first, stream))?;
+        Ok((n, first))
+    }
     pub fn as_ptr(&self) -> *mut lurk_hip_r1cs {
         self.0
     }
+}
+/// One sparse matrix of a slot's rows, owned (`lurk_hip_slot_constraints`).
+pub struct SlotMatrix {
+    pub indptr: Vec<u64>,
+    pub indices: Vec<u64>,
+    pub data: Vec<u8>,
+}
+/// The constraint rows one slot's gadget enforces on its block: A, B, C; local column `size` is the constant ONE.  Host-only.
+pub fn slot_constraints(field_id: c_int, slot_type: c_int) -> Result<[SlotMatrix; 3], Error> {
+    let (mut rows, mut na, mut nb, mut nc) = (0usize, 0usize, 0usize, 0usize);
+    check(unsafe { lurk_hip_slot_constraints_size(field_id, slot_type, &mut rows, &mut na, &mut nb, &mut nc) })?;
+    let mk = |nnz: usize| SlotMatrix { indptr: vec![0; rows + 1], indices: vec![0; nnz], data: vec![0; nnz * 32] };
+    let mut m = [mk(na), mk(nb), mk(nc)];
+    let [a, b, c] = &mut m;
+    check(unsafe {
+        lurk_hip_slot_constraints(field_id, slot_type, a.indptr.as_mut_ptr(), a.indices.as_mut_ptr(), a.data.as_mut_ptr().cast(), b.indptr.as_mut_ptr(),
+                                  b.indices.as_mut_ptr(), b.data.as_mut_ptr().cast(), c.indptr.as_mut_ptr(), c.indices.as_mut_ptr(), c.data.as_mut_ptr().cast())
+    })?;
+    Ok(m)
 }
 impl Drop for R1csShape {
     fn drop(&mut self) {
