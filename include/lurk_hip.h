@@ -54,11 +54,13 @@ const char* lurk_hip_last_error(void);
 const char* lurk_hip_version(void);
 /* The ABI revision this header describes; lurk_hip_abi_version() is what the loaded library was built from (a binding compares the
  * two at start-up).  A revision that only adds entry points raises the number too: a binding built against revision n runs on any library
- * that reports >= n until a revision says otherwise.  3: lurk_hip_slot_constraints_size / lurk_hip_slot_constraints,
+ * that reports >= n until a revision says otherwise.  4: the verifiers - lurk_hip_r1cs_sparse_mle_dev, lurk_hip_ipa_s_vector_dev,
+ * lurk_hip_sumcheck_verify, lurk_hip_ipa_verify_dev, lurk_hip_spartan_verify_dev, lurk_hip_spartan_verify_batch_dev (additions only).
+ * 3: lurk_hip_slot_constraints_size / lurk_hip_slot_constraints,
  * lurk_hip_frames_r1cs_create, lurk_hip_r1cs_is_sat_dev (additions only).  2 (round 6): lurk_hip_msm_ctx_info's *precomputed is a boolean (the key's form comes from lurk_hip_msm_ctx_form),
  * LURK_MSM_SLOTS is 6, LURK_MSM_SUBMIT_FOLLOW, the parameter blocks lurk_hip_ro_params / lurk_hip_ck_params, lurk_hip_scratch_trim.
  * 1: rounds 1-4 (*precomputed returned the form 0 / 1 / 2, four slots). */
-#define LURK_HIP_ABI_VERSION 3
+#define LURK_HIP_ABI_VERSION 4
 int lurk_hip_abi_version(void);
 /* Prover scratch (the compressing SNARK's sum-check tables, eq tables, opening-argument halves) comes from one stack arena per
  * (device, stream) that grows by blocks of >= 256 MiB and is KEPT between proofs: about 2 GB per stream that has run a 2^20-row proof,
@@ -731,7 +733,7 @@ int lurk_hip_ipa_prove_dev(lurk_hip_msm_ctx* key, void* d_a32, void* d_b32, size
  * -> arecibo RelaxedR1CSSNARK::prove): outer cubic sum-check, inner quadratic sum-check over the transposed shape, the two evaluation claims
  * batched to one point, one inner-product argument under the resident key - a sequence of the entry points above with the vectors resident
  * and the Keccak transcript inside.  The protocol is this repository's own (oracle/spartan_ref.py, oracle/spartan_fast.py: the oracle's
- * prover gives the same proof element for element, its verifier accepts it), not arecibo's byte for byte.
+ * prover gives the same proof element for element, its verifier and lurk_hip_spartan_verify_dev below accept it), not arecibo's byte for byte.
  *   shape: num_cons x (num_vars + 1 + num_io) columns of z = [W | u | X]; shape_t: its transpose over 2 num_vars rows and num_cons columns
  *   (created with num_vars' = num_cons - 1, num_io' = 0); num_cons, num_vars: powers of two.  key: >= max(num_cons, num_vars) points, the
  *   key that committed W and E; ck_c: the inner-product base (a 96-byte Jacobian).  x, u: canonical; d_w (num_vars), d_e (num_cons):
@@ -790,6 +792,63 @@ typedef struct lurk_hip_spartan_batch_proof {
 int lurk_hip_spartan_prove_batch_dev(const lurk_hip_spartan_instance* instances, size_t n_instances, lurk_hip_msm_ctx* key,
                                      const void* ck_c_jacobian96, const void* label, size_t label_len, lurk_hip_spartan_batch_proof* out,
                                      void* stream);
+
+/* ---- the verifiers (the other half of the CompressedSNARK trait: /root/reference/src/proof/nova.rs:358-373, supernova.rs:304-316) ------
+ * A verification is a SUCCESSFUL call whatever its answer: the return value says whether the call worked (bad arguments, no device,
+ * out of memory -> non-zero with lurk_hip_last_error), *accepted = 1 / 0 is the answer and *failed_check (may be NULL) names the first
+ * check that failed.  Malformed input is rejected before any arithmetic: a scalar of the proof or the statement that is not below the
+ * field order, a point of the proof or a commitment that is neither the identity nor on the curve (or whose coordinates are not
+ * reduced), an opening challenge that is zero. */
+#define LURK_VERIFY_ACCEPTED 0
+#define LURK_VERIFY_MALFORMED 1 /* input rejected before any arithmetic */
+#define LURK_VERIFY_OUTER 2     /* outer sum-check: a round, or its final claim against claims_outer / eval_e */
+#define LURK_VERIFY_INNER 3     /* inner sum-check: a round, or its final claim against the matrices at (r_x, r_y) and eval_w */
+#define LURK_VERIFY_BATCH 4     /* the sum-check that batches the evaluation claims to one point */
+#define LURK_VERIFY_OPENING 5   /* the inner-product argument's final point equation */
+/* Building block: the sparse multilinear evaluation of a resident shape, M~ = sum_i eq_x[i] sum_{k in row i} val[k] eq_y[col[k]] for
+ * M = A, B, C in ONE launch over the shape's non-empty rows (SparsePolynomial::evaluate of arecibo's Spartan verifier).  d_eq_x (n_x
+ * elements), d_eq_y (n_y): Montgomery, device memory - whole eq tables or their leading parts (the batched verifier passes truncated
+ * tables); n_x >= the shape's rows and n_y > its largest column, otherwise the call is refused.  out: three Montgomery elements
+ * (A~, B~, C~) in HOST memory; the call synchronises the stream for them. */
+int lurk_hip_r1cs_sparse_mle_dev(const lurk_hip_r1cs* shape, const void* d_eq_x, size_t n_x, const void* d_eq_y, size_t n_y,
+                                 void* out_abc96_mont, void* stream);
+/* Building block: the s vector of the inner-product argument's verifier, d_out[i] = prod_j (bit_{ell-1-j}(i) ? r_j : r_j^-1), 2^ell
+ * Montgomery elements on the device (challenge 0 decides the highest index bit) - what ell rounds of lurk_hip_ipa_coef_fold_dev leave,
+ * in one launch: one batched inversion on the host, two tables of 2^(ell/2) products, one product per element.  challenges: ell
+ * canonical values of `field_id` in host memory, each non-zero and below the field order (refused otherwise); 0 <= ell <= 30. */
+int lurk_hip_ipa_s_vector_dev(int field_id, const void* challenges32_canonical, int ell, void* d_out32_mont, void* stream);
+/* SumcheckProof::verify (host only, no device needed): `rounds` round polynomials of degree + 1 canonical coefficients each (low to
+ * high, as lurk_hip_sumcheck_prove_dev writes them), the challenge of every round (the caller replays its transcript).  Per round
+ * p(0) + p(1) must equal the running claim, which becomes p(r).  *ok = 1 and the final claim in out_final32_canonical, or *ok = 0 (a
+ * round failed, or a value was not reduced).  degree: 2 or 3. */
+int lurk_hip_sumcheck_verify(int field_id, int degree, size_t rounds, const void* claim32_canonical, const void* polys,
+                             const void* challenges32_canonical, void* out_final32_canonical, int* ok);
+/* InnerProductArgument::verify under a resident key: with r_j = challenge(j, L_j, R_j) (the caller's transcript, as in
+ * lurk_hip_ipa_prove_dev), s the vector above and b_hat = <s, b>, accepts iff
+ *     P + sum_j (r_j^2 L_j + r_j^-2 R_j) == [a_hat] <s, key> + [a_hat b_hat] ck_c
+ * P: the commitment to a plus [<a, b>] ck_c; ck_c: the extra base as the prover was given it (already scaled).  b: d_b32_mont (n
+ * Montgomery scalars on the device, not modified) or, when that is NULL, eq(eq_point) for log2(n) canonical values on the host - b_hat
+ * then has the closed form prod_j (r_j^-1 (1 - z_j) + r_j z_j) and no vector is read.  l, r: log2(n) x 96-byte Jacobians; a_hat
+ * canonical.  n: a power of two, at most the key's points (a call error otherwise, not a rejection).  Device work: the s vector and ONE
+ * commitment under the key; the 2 log2(n) + 2 scalar multiples of the equation run on the host. */
+int lurk_hip_ipa_verify_dev(lurk_hip_msm_ctx* key, size_t n, const void* p_jacobian96, const void* ck_c_jacobian96, const void* d_b32_mont,
+                            const void* eq_point32_canonical, const void* l_jacobian96, const void* r_jacobian96, const void* a_hat32,
+                            lurk_hip_ipa_challenge_fn challenge, void* user, int* accepted, int* failed_check, void* stream);
+/* CompressedSNARK::verify for one curve: the verifier of lurk_hip_spartan_prove_dev's proof (oracle/spartan_fast.py: verify, check for
+ * check, over the same transcript).  The statement is (shape, X, u, comm_W, comm_E) under (key, ck_c, label); `proof` holds the prover's
+ * outputs in the prover's layout (read only).  Device work: two eq tables, one sparse evaluation of the shape, the s vector, one
+ * commitment under the key; everything else is a few hundred field operations and 2 log2(N) + 5 scalar multiples on the host.  Scratch
+ * comes from the stream's arena; verifications on different streams are independent. */
+int lurk_hip_spartan_verify_dev(const lurk_hip_r1cs* shape, size_t num_cons, size_t num_vars, size_t num_io, lurk_hip_msm_ctx* key,
+                                const void* ck_c_jacobian96, const void* x32_canonical, const void* u32_canonical,
+                                const void* comm_w_jacobian96, const void* comm_e_jacobian96, const void* label, size_t label_len,
+                                const lurk_hip_spartan_proof* proof, int* accepted, int* failed_check, void* stream);
+/* The verifier of lurk_hip_spartan_prove_batch_dev's proof (oracle/spartan_fast.py: verify_batched).  Of an instance it reads shape,
+ * num_cons, num_vars, num_io, x, u and the two commitments; shape_t, d_w32_mont and d_e32_mont are ignored (a verifier has no witness
+ * and needs no transpose). */
+int lurk_hip_spartan_verify_batch_dev(const lurk_hip_spartan_instance* instances, size_t n_instances, lurk_hip_msm_ctx* key,
+                                      const void* ck_c_jacobian96, const void* label, size_t label_len,
+                                      const lurk_hip_spartan_batch_proof* proof, int* accepted, int* failed_check, void* stream);
 
 /* ---- synthetic inputs (bench / tests) -------------------------------------
  * SplitMix64 counter mode, seed 0x4C55524B.  dist 0 = uniform, 1 = witness-like. */

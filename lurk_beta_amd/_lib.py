@@ -175,6 +175,15 @@ SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "lurk_hip_ipa_prove_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lurk_hip_spartan_prove_batch_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lurk_hip_r1cs_sparse_mle_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lurk_hip_ipa_s_vector_dev": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "lurk_hip_sumcheck_verify": (c_int, [c_int, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
+    "lurk_hip_ipa_verify_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]),
+    "lurk_hip_spartan_verify_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                            c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]),
+    "lurk_hip_spartan_verify_batch_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                                  c_void_p]),
     "lurk_hip_synth_scalars_dev": (c_int, [c_int, c_u64, c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p]),
     "lurk_hip_synth_bases_dev": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p]),
 }

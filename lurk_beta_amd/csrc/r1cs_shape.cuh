@@ -25,6 +25,14 @@ struct SatPlan {
     }
 };
 
+// Row classes of the sparse multilinear evaluation (verify.hip), as above but over the rows that have an entry at all: a row
+// without one contributes nothing and is not visited.  Built on the first call, immutable afterwards.
+struct MlePlan {
+    DevBuf rows;  // [wide | mid | lane] row ids
+    size_t n_wide = 0, n_mid = 0, n_lane = 0;
+    uint64_t max_col = 0;  // the largest column index of the three matrices (0 for an empty shape)
+};
+
 struct CsrDev {
     DevBuf rowptr;  // u32 x (rows + 1)
     DevBuf ent;     // uint2 {col, coefficient id} x nnz
@@ -43,6 +51,9 @@ struct R1csShape {
     // lurk_hip_r1cs_is_sat_dev's row classes (r1cs_sat.hip): built on the first call, so that a shape that is never checked pays nothing
     mutable std::mutex sat_mu;
     mutable std::unique_ptr<SatPlan> sat;
+    // lurk_hip_r1cs_sparse_mle_dev's row classes (verify.hip): built on the first call under mle_mu, read-only afterwards
+    mutable std::mutex mle_mu;
+    mutable std::unique_ptr<MlePlan> mle;
 };
 
 // ---- rows --------------------------------------------------------------------------------------------------

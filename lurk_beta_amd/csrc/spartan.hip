@@ -11,73 +11,9 @@
 // inner products, the sum-check and inner-product round loops with the Keccak round bindings - with the vectors resident and the
 // field arithmetic of the claims on the host: lurk_beta_amd/spartan.py: SpartanProver.prove did the same from Python (0.4 ms of
 // interpreter between the sum-checks, 0.8 ms between proofs).
-#include <memory>
-#include <vector>
-
-#include "common.hpp"
-#include "field.cuh"
+#include "spartan_transcript.hpp"
 
 namespace lurk {
-
-static void sp_ok(int rc) {
-    if (rc != 0) throw HipFailure{rc, lurk_hip_last_error()};
-}
-
-using SpScratch = ArenaBuf;  // scratch vectors come off the stream's arena (common.hpp): a push, not a hipMallocAsync
-
-struct SpTranscript {
-    lurk_hip_keccak_transcript* t = nullptr;
-    ~SpTranscript() {
-        if (t) (void)lurk_hip_keccak_transcript_destroy(t);
-    }
-};
-
-template <class F>
-struct SpField {
-    static Fe<F> from_canonical(const void* p) {
-        Fe<F> x;
-        memcpy(x.l, p, 32);
-        LURK_REQUIRE(!fe_canonical_ge_mod<F>(x.l), "a field element is not reduced modulo the field order");
-        return fe_to_mont<F>(x);
-    }
-    static void to_canonical(const Fe<F>& m, void* out) {
-        const Fe<F> c = fe_from_mont<F>(m);
-        memcpy(out, c.l, 32);
-    }
-};
-
-template <class F>
-static Fe<F> sp_squeeze(lurk_hip_keccak_transcript* t, const char* label, int field_id) {
-    uint64_t r[4];
-    sp_ok(lurk_hip_keccak_transcript_squeeze(t, label, strlen(label), field_id, r));
-    return SpField<F>::from_canonical(r);
-}
-template <class F>
-static void sp_absorb(lurk_hip_keccak_transcript* t, const char* label, const std::vector<Fe<F>>& mont_vals) {
-    std::vector<uint64_t> can(4 * mont_vals.size());
-    for (size_t i = 0; i < mont_vals.size(); i++) SpField<F>::to_canonical(mont_vals[i], can.data() + 4 * i);
-    sp_ok(lurk_hip_keccak_transcript_absorb_scalars(t, label, strlen(label), can.data(), mont_vals.size()));
-}
-// eq(point) as 2^|point| Montgomery elements on the device
-template <class F>
-static void sp_eq(int field_id, const std::vector<Fe<F>>& point, void* d_out, hipStream_t s) {
-    // (the point is copied out of pageable memory before the call returns; every caller's vector outlives the proof anyway)
-    sp_ok(lurk_hip_eq_evals_dev(field_id, point.empty() ? nullptr : (const void*)point.data(), (int)point.size(), d_out, (void*)s));
-}
-// the multilinear extension of a device table at `point` (Montgomery): <table, eq(point)>
-template <class F>
-static Fe<F> sp_mle(int field_id, const void* d_table, const std::vector<Fe<F>>& point, hipStream_t s) {
-    SpScratch eq(((size_t)32) << point.size(), s);
-    sp_eq<F>(field_id, point, eq.p, s);
-    Fe<F> out;
-    sp_ok(lurk_hip_inner_product_dev(field_id, d_table, eq.p, (size_t)1 << point.size(), out.l, (void*)s));
-    return out;
-}
-static int sp_log2(size_t n) {
-    int k = 0;
-    while (((size_t)1 << k) < n) k++;
-    return k;
-}
 
 template <class F>
 static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, const lurk_hip_r1cs* shape_t, size_t nc, size_t nv, size_t nio,
@@ -90,13 +26,8 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
     void* vs = (void*)s;
     stream_pool_retain();
     SpTranscript tr;
-    sp_ok(lurk_hip_keccak_transcript_new(&tr.t, label, label_len));
-    sp_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, "comm_W", 6, curve, comm_w_jac96));
-    sp_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, "comm_E", 6, curve, comm_e_jac96));
-    std::vector<Fe<F>> ux(1 + nio);
-    ux[0] = SpField<F>::from_canonical(u_canonical);
-    for (size_t i = 0; i < nio; i++) ux[1 + i] = SpField<F>::from_canonical((const char*)x_canonical + 32 * i);
-    sp_absorb<F>(tr.t, "uX", ux);
+    std::vector<Fe<F>> ux;
+    sp_prologue<F>(tr, curve, label, label_len, comm_w_jac96, comm_e_jac96, u_canonical, x_canonical, nio, ux);
     // z = [W | u | X | 0 ...] of length 2 num_vars
     SpScratch z(2 * nv * 32, s), az(nc * 32, s), bz(nc * 32, s), cz(nc * 32, s);
     LURK_HIP_CHECK(hipMemsetAsync(z.p, 0, 2 * nv * 32, s));
@@ -104,7 +35,7 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
     LURK_HIP_CHECK(hipMemcpyAsync((char*)z.p + nv * 32, ux.data(), (1 + nio) * 32, hipMemcpyHostToDevice, s));
     sp_ok(lurk_hip_r1cs_multiply_vec_dev(shape, z.p, az.p, bz.p, cz.p, vs));
     std::vector<Fe<F>> tau(ell_x);
-    for (int j = 0; j < ell_x; j++) tau[j] = sp_squeeze<F>(tr.t, "t", field_id);
+    for (int j = 0; j < ell_x; j++) tau[j] = sp_squeeze<F>(tr.t, splabel::TAU, field_id);
     SpScratch d_tau(nc * 32, s), ucze(nc * 32, s);
     sp_eq<F>(field_id, tau, d_tau.p, s);
     sp_ok(lurk_hip_fold_vec_dev(field_id, d_e, cz.p, ux[0].l, nc, ucze.p, vs));  // E + u Cz
@@ -116,27 +47,13 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
         for (int j = 0; j < rounds; j++) into[j] = SpField<F>::from_canonical(buf.data() + 4 * j);
     };
     auto binding = [&](std::vector<uint64_t>& keep, int rounds, const char* absorb, const char* absorb2, const char* squeeze) {
-        keep.assign((size_t)4 * (rounds > 0 ? rounds : 1), 0);
-        lurk_hip_keccak_round_binding b;
-        memset(&b, 0, sizeof(b));
-        b.transcript = tr.t;
-        b.field_id = field_id;
-        b.curve = curve;
-        b.absorb_label = absorb;
-        b.absorb_label_len = strlen(absorb);
-        b.absorb_label2 = absorb2;
-        b.absorb_label2_len = absorb2 ? strlen(absorb2) : 0;
-        b.squeeze_label = squeeze;
-        b.squeeze_label_len = strlen(squeeze);
-        b.challenges_out = keep.data();
-        b.challenges_cap = (size_t)(rounds > 0 ? rounds : 1);
-        return b;
+        return sp_round_binding(tr.t, field_id, curve, keep, rounds, absorb, absorb2, squeeze, 0);
     };
     uint64_t finals4[16], claim_out[4];
     {
         void* tabs[4] = {d_tau.p, az.p, bz.p, ucze.p};  // (consumed: nothing reads Az, Bz or the other two afterwards)
         std::vector<uint64_t> keep;
-        lurk_hip_keccak_round_binding b = binding(keep, ell_x, "p", nullptr, "c");
+        lurk_hip_keccak_round_binding b = binding(keep, ell_x, splabel::POLY, nullptr, splabel::CHALLENGE);
         b.n_scalars = 4;
         sp_ok(lurk_hip_sumcheck_prove_dev(field_id, 3, tabs, nc, zero32, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_outer, finals4, claim_out, vs));
         challenges(keep, ell_x, r_x);
@@ -147,8 +64,8 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
     SpField<F>::to_canonical(claim_bz, (char*)out->claims_outer + 32);
     SpField<F>::to_canonical(claim_cz, (char*)out->claims_outer + 64);
     SpField<F>::to_canonical(eval_e, out->eval_e);
-    sp_absorb<F>(tr.t, "claims_outer", {claim_az, claim_bz, claim_cz, eval_e});
-    const Fe<F> r = sp_squeeze<F>(tr.t, "r", field_id), r2 = fe_mul<F>(r, r);
+    sp_absorb<F>(tr.t, splabel::CLAIMS_OUTER, {claim_az, claim_bz, claim_cz, eval_e});
+    const Fe<F> r = sp_squeeze<F>(tr.t, splabel::R, field_id), r2 = fe_mul<F>(r, r);
     const Fe<F> claim_inner = fe_add<F>(fe_add<F>(claim_az, fe_mul<F>(r, claim_bz)), fe_mul<F>(r2, claim_cz));
     // ---- inner sum-check: (A + r B + r^2 C)(r_x, .) z over the 2 num_vars columns: the transposed shape applied to eq(r_x)
     SpScratch abc(2 * nv * 32, s);
@@ -164,7 +81,7 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
         uint64_t claim_can[4];
         SpField<F>::to_canonical(claim_inner, claim_can);
         std::vector<uint64_t> keep;
-        lurk_hip_keccak_round_binding b = binding(keep, ell_y, "p", nullptr, "c");
+        lurk_hip_keccak_round_binding b = binding(keep, ell_y, splabel::POLY, nullptr, splabel::CHALLENGE);
         b.n_scalars = 3;
         uint64_t fin2[8];
         sp_ok(lurk_hip_sumcheck_prove_dev(field_id, 2, tabs, 2 * nv, claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_inner, fin2, claim_out, vs));
@@ -173,7 +90,7 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
     const std::vector<Fe<F>> r_y_tail(r_y.begin() + 1, r_y.end());
     const Fe<F> eval_w = sp_mle<F>(field_id, d_w, r_y_tail, s);
     SpField<F>::to_canonical(eval_w, out->eval_w);
-    sp_absorb<F>(tr.t, "eval_W", {eval_w});
+    sp_absorb<F>(tr.t, splabel::EVAL_W, {eval_w});
     // ---- the two evaluation claims -> one point: W and E zero-padded to N, their points padded with leading zeros
     SpScratch p1(N * 32, s), p2(N * 32, s);
     LURK_HIP_CHECK(hipMemsetAsync(p1.p, 0, N * 32, s));
@@ -183,7 +100,7 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
     std::vector<Fe<F>> x1((size_t)ell - (ell_y - 1), fe_zero<F>()), x2((size_t)ell - ell_x, fe_zero<F>());
     x1.insert(x1.end(), r_y_tail.begin(), r_y_tail.end());
     x2.insert(x2.end(), r_x.begin(), r_x.end());
-    const Fe<F> rho = sp_squeeze<F>(tr.t, "rho", field_id);
+    const Fe<F> rho = sp_squeeze<F>(tr.t, splabel::RHO, field_id);
     uint64_t fin_batch[16];
     {
         SpScratch e1(N * 32, s), e2(N * 32, s), q1(N * 32, s), q2(N * 32, s);
@@ -198,7 +115,7 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
         SpField<F>::to_canonical(rho, coeffs + 4);
         SpField<F>::to_canonical(fe_add<F>(eval_w, fe_mul<F>(rho, eval_e)), claim_can);
         std::vector<uint64_t> keep;
-        lurk_hip_keccak_round_binding b = binding(keep, ell, "p", nullptr, "c");
+        lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::POLY, nullptr, splabel::CHALLENGE);
         b.n_scalars = 3;
         sp_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 2, 2, tabs, N, coeffs, claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_batch, fin_batch,
                                                 claim_out, vs));
@@ -207,16 +124,16 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
     const Fe<F> ev1 = SpField<F>::from_canonical(fin_batch + 4), ev2 = SpField<F>::from_canonical(fin_batch + 12);  // (A_i(r), B_i(r)) per instance: the B's
     SpField<F>::to_canonical(ev1, (char*)out->evals_batch);
     SpField<F>::to_canonical(ev2, (char*)out->evals_batch + 32);
-    sp_absorb<F>(tr.t, "evals_batch", {ev1, ev2});
-    const Fe<F> gamma = sp_squeeze<F>(tr.t, "gamma", field_id);
+    sp_absorb<F>(tr.t, splabel::EVALS_BATCH, {ev1, ev2});
+    const Fe<F> gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
     SpScratch joint(N * 32, s), eq_rz(N * 32, s);
     sp_ok(lurk_hip_fold_vec_dev(field_id, p1.p, p2.p, gamma.l, N, joint.p, vs));
-    const Fe<F> r0 = sp_squeeze<F>(tr.t, "ipa_r0", field_id);
+    const Fe<F> r0 = sp_squeeze<F>(tr.t, splabel::IPA_R0, field_id);
     uint64_t ck_c_scaled[12], ck_hat[8];
     sp_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
     sp_eq<F>(field_id, r_z, eq_rz.p, s);
     std::vector<uint64_t> keep;
-    lurk_hip_keccak_round_binding b = binding(keep, ell, "L", "R", "r");
+    lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::IPA_L, splabel::IPA_R, splabel::IPA_CHALLENGE);
     sp_ok(lurk_hip_ipa_prove_dev(key, joint.p, eq_rz.p, N, ck_c_scaled, lurk_hip_keccak_ipa_challenge, &b, out->ipa_l, out->ipa_r, out->ipa_a, ck_hat, vs));
     LURK_HIP_CHECK(hipStreamSynchronize(s));
 }
@@ -241,23 +158,11 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
     const int ell = sp_log2(N);
     stream_pool_retain();
     SpTranscript tr;
-    sp_ok(lurk_hip_keccak_transcript_new(&tr.t, label, label_len));
-    {
-        Fe<F> nn = fe_from_u64<F>((uint64_t)n);
-        sp_absorb<F>(tr.t, "n", {nn});
-    }
-    std::vector<std::vector<Fe<F>>> ux(n);
-    for (size_t i = 0; i < n; i++) {
-        sp_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, "comm_W", 6, curve, inst[i].comm_w_jacobian96));
-        sp_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, "comm_E", 6, curve, inst[i].comm_e_jacobian96));
-        ux[i].resize(1 + inst[i].num_io);
-        ux[i][0] = SpField<F>::from_canonical(inst[i].u32_canonical);
-        for (size_t k = 0; k < inst[i].num_io; k++) ux[i][1 + k] = SpField<F>::from_canonical((const char*)inst[i].x32_canonical + 32 * k);
-        sp_absorb<F>(tr.t, "uX", ux[i]);
-    }
+    std::vector<std::vector<Fe<F>>> ux;
+    sp_prologue_batch<F>(tr, curve, label, label_len, inst, n, ux);
     std::vector<Fe<F>> tau(ell_x);
-    for (int j = 0; j < ell_x; j++) tau[j] = sp_squeeze<F>(tr.t, "t", field_id);
-    const Fe<F> rho_o = sp_squeeze<F>(tr.t, "rho_outer", field_id);
+    for (int j = 0; j < ell_x; j++) tau[j] = sp_squeeze<F>(tr.t, splabel::TAU, field_id);
+    const Fe<F> rho_o = sp_squeeze<F>(tr.t, splabel::RHO_OUTER, field_id);
     auto powers = [](const Fe<F>& b, size_t count) {
         std::vector<Fe<F>> v(count);
         Fe<F> acc = fe_one<F>();
@@ -274,22 +179,7 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         for (int j = 0; j < rounds; j++) into[j] = SpField<F>::from_canonical(buf.data() + 4 * j);
     };
     auto binding = [&](std::vector<uint64_t>& keep, int rounds, const char* absorb, const char* absorb2, const char* squeeze, int n_scalars) {
-        keep.assign((size_t)4 * (rounds > 0 ? rounds : 1), 0);
-        lurk_hip_keccak_round_binding b;
-        memset(&b, 0, sizeof(b));
-        b.transcript = tr.t;
-        b.field_id = field_id;
-        b.curve = curve;
-        b.n_scalars = n_scalars;
-        b.absorb_label = absorb;
-        b.absorb_label_len = strlen(absorb);
-        b.absorb_label2 = absorb2;
-        b.absorb_label2_len = absorb2 ? strlen(absorb2) : 0;
-        b.squeeze_label = squeeze;
-        b.squeeze_label_len = strlen(squeeze);
-        b.challenges_out = keep.data();
-        b.challenges_cap = (size_t)(rounds > 0 ? rounds : 1);
-        return b;
+        return sp_round_binding(tr.t, field_id, curve, keep, rounds, absorb, absorb2, squeeze, n_scalars);
     };
     typedef std::unique_ptr<SpScratch> Buf;
     auto mk = [&](size_t elems) { return Buf(new SpScratch(elems * 32, s)); };
@@ -333,7 +223,7 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         }
         const std::vector<uint64_t> coeffs = canon(powers(rho_o, n));
         std::vector<uint64_t> keep;
-        lurk_hip_keccak_round_binding b = binding(keep, ell_x, "p", nullptr, "c", 4);
+        lurk_hip_keccak_round_binding b = binding(keep, ell_x, splabel::POLY, nullptr, splabel::CHALLENGE, 4);
         sp_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 3, n, tabs.data(), LX, coeffs.data(), zero32, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_outer,
                                                 fin_outer.data(), claim_out, vs));
         challenges(keep, ell_x, r_x);
@@ -359,10 +249,10 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
             flat.push_back(cl_c[i]);
         }
         flat.insert(flat.end(), ev_e.begin(), ev_e.end());
-        sp_absorb<F>(tr.t, "claims_outer", flat);
+        sp_absorb<F>(tr.t, splabel::CLAIMS_OUTER, flat);
     }
-    const Fe<F> r = sp_squeeze<F>(tr.t, "r", field_id), r2 = fe_mul<F>(r, r);
-    const Fe<F> rho_i = sp_squeeze<F>(tr.t, "rho_inner", field_id);
+    const Fe<F> r = sp_squeeze<F>(tr.t, splabel::R, field_id), r2 = fe_mul<F>(r, r);
+    const Fe<F> rho_i = sp_squeeze<F>(tr.t, splabel::RHO_INNER, field_id);
     // ---- inner sum-check: sum_i rho_i^i (A_i + r B_i + r^2 C_i)(r_x, .) z_i over 2^ell_y columns
     {
         std::vector<Buf> keepers;
@@ -390,7 +280,7 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         uint64_t claim_can[4];
         SpField<F>::to_canonical(claim, claim_can);
         std::vector<uint64_t> keep, fin(n * 8);
-        lurk_hip_keccak_round_binding b = binding(keep, ell_y, "p", nullptr, "c", 3);
+        lurk_hip_keccak_round_binding b = binding(keep, ell_y, splabel::POLY, nullptr, splabel::CHALLENGE, 3);
         sp_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 2, n, tabs.data(), LY, coeffs.data(), claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_inner,
                                                 fin.data(), claim_out, vs));
         challenges(keep, ell_y, r_y);
@@ -400,7 +290,7 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         ev_w[i] = sp_mle<F>(field_id, inst[i].d_w32_mont, std::vector<Fe<F>>(r_y.begin() + py + 1, r_y.end()), s);
         SpField<F>::to_canonical(ev_w[i], (char*)out->evals_w + 32 * i);
     }
-    sp_absorb<F>(tr.t, "evals_W", ev_w);
+    sp_absorb<F>(tr.t, splabel::EVALS_W, ev_w);
     // ---- all 2 n evaluation claims -> one point
     std::vector<Buf> polys(2 * n);
     std::vector<std::vector<Fe<F>>> points(2 * n);
@@ -417,7 +307,7 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         claims[2 * i] = ev_w[i];
         claims[2 * i + 1] = ev_e[i];
     }
-    const Fe<F> rho = sp_squeeze<F>(tr.t, "rho", field_id);
+    const Fe<F> rho = sp_squeeze<F>(tr.t, splabel::RHO, field_id);
     std::vector<uint64_t> fin_batch(2 * n * 8);
     {
         std::vector<Buf> keepers;
@@ -437,7 +327,7 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         uint64_t claim_can[4];
         SpField<F>::to_canonical(claim, claim_can);
         std::vector<uint64_t> keep;
-        lurk_hip_keccak_round_binding b = binding(keep, ell, "p", nullptr, "c", 3);
+        lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::POLY, nullptr, splabel::CHALLENGE, 3);
         sp_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 2, 2 * n, tabs.data(), N, coeffs.data(), claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_batch,
                                                 fin_batch.data(), claim_out, vs));
         challenges(keep, ell, r_z);
@@ -447,8 +337,8 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         evals_batch[k] = SpField<F>::from_canonical(fin_batch.data() + 8 * k + 4);  // (eq_k(r_z), poly_k(r_z)): the polynomial's
         SpField<F>::to_canonical(evals_batch[k], (char*)out->evals_batch + 32 * k);
     }
-    sp_absorb<F>(tr.t, "evals_batch", evals_batch);
-    const Fe<F> gamma = sp_squeeze<F>(tr.t, "gamma", field_id);
+    sp_absorb<F>(tr.t, splabel::EVALS_BATCH, evals_batch);
+    const Fe<F> gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
     Buf joint = padded_copy(polys[0]->p, N, N), eq_rz = mk(N);
     {
         Fe<F> g = gamma;
@@ -457,12 +347,12 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
             g = fe_mul<F>(g, gamma);
         }
     }
-    const Fe<F> r0 = sp_squeeze<F>(tr.t, "ipa_r0", field_id);
+    const Fe<F> r0 = sp_squeeze<F>(tr.t, splabel::IPA_R0, field_id);
     uint64_t ck_c_scaled[12], ck_hat[8];
     sp_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
     sp_eq<F>(field_id, r_z, eq_rz->p, s);
     std::vector<uint64_t> keep;
-    lurk_hip_keccak_round_binding b = binding(keep, ell, "L", "R", "r", 0);
+    lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::IPA_L, splabel::IPA_R, splabel::IPA_CHALLENGE, 0);
     sp_ok(lurk_hip_ipa_prove_dev(key, joint->p, eq_rz->p, N, ck_c_scaled, lurk_hip_keccak_ipa_challenge, &b, out->ipa_l, out->ipa_r, out->ipa_a, ck_hat, vs));
     LURK_HIP_CHECK(hipStreamSynchronize(s));
 }

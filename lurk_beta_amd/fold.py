@@ -79,6 +79,18 @@ class R1CSShape:
         _lib.check(_lib.load().lurk_hip_r1cs_is_sat_dev(self._h, _lib.ptr(d_z), _lib.ptr(d_e), ctypes.byref(n), ctypes.byref(first), _lib.ptr(s)))
         return n.value, first.value
 
+    def sparse_mle(self, d_eq_x, d_eq_y, stream=None) -> np.ndarray:
+        """(A~, B~, C~) as a (3, 4) Montgomery array: M~ = sum_i eq_x[i] sum_{k in row i} val[k] eq_y[col[k]] in one launch over the shape
+        (lurk_hip_r1cs_sparse_mle_dev: the matrices' multilinear extensions at (r_x, r_y) when the tables are eq(r_x), eq(r_y), or their
+        leading parts).  d_eq_x: >= num_cons elements, d_eq_y: more than the largest column.  Synchronises the stream."""
+        import torch
+
+        assert d_eq_x.is_cuda and d_eq_y.is_cuda and d_eq_x.is_contiguous() and d_eq_y.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        out = np.zeros((3, 4), dtype=np.uint64)
+        _lib.check(_lib.load().lurk_hip_r1cs_sparse_mle_dev(self._h, _lib.ptr(d_eq_x), d_eq_x.shape[0], _lib.ptr(d_eq_y), d_eq_y.shape[0], _lib.ptr(out), _lib.ptr(s)))
+        return out
+
     @property
     def num_cols(self) -> int:
         return self.num_vars + 1 + self.num_io

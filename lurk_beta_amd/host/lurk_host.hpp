@@ -272,6 +272,47 @@ class R1CSShape {
     lurk_hip_r1cs* h_ = nullptr;
 };
 
+// ---- the verifiers (CompressedSNARK::verify, /root/reference/src/proof/nova.rs:358-373; supernova.rs:304-316) ------------------------
+// The answer of a verification: accepted, or the first check that failed (LURK_VERIFY_*); a call that could not run throws.
+struct Verdict {
+    bool accepted = false;
+    int failed_check = LURK_VERIFY_MALFORMED;
+};
+// lurk_hip_spartan_verify_dev: the proof in the prover's layout (lurk_hip_spartan_proof over the caller's buffers); x: num_io canonical
+// elements, u canonical; the shape's own (num_cons, num_vars, num_io) are the statement's
+inline Verdict spartan_verify(const R1CSShape& shape, const CommitmentKey& key, const Jacobian& ck_c, const std::vector<Fe>& x, const Fe& u,
+                              const Jacobian& comm_w, const Jacobian& comm_e, const std::string& label, const lurk_hip_spartan_proof& proof,
+                              void* stream = nullptr) {
+    Verdict v;
+    int acc = 0;
+    check(lurk_hip_spartan_verify_dev(shape.handle(), shape.num_cons(), shape.num_vars(), x.size(), key.handle(), &ck_c, x.data(), &u, &comm_w, &comm_e,
+                                      label.data(), label.size(), &proof, &acc, &v.failed_check, stream));
+    v.accepted = acc != 0;
+    return v;
+}
+// lurk_hip_spartan_verify_batch_dev: of an instance only shape, sizes, x, u and the two commitments are read
+inline Verdict spartan_verify_batch(const std::vector<lurk_hip_spartan_instance>& instances, const CommitmentKey& key, const Jacobian& ck_c,
+                                    const std::string& label, const lurk_hip_spartan_batch_proof& proof, void* stream = nullptr) {
+    Verdict v;
+    int acc = 0;
+    check(lurk_hip_spartan_verify_batch_dev(instances.data(), instances.size(), key.handle(), &ck_c, label.data(), label.size(), &proof, &acc,
+                                            &v.failed_check, stream));
+    v.accepted = acc != 0;
+    return v;
+}
+// SumcheckProof::verify on the host (no device): the final claim, or nothing when a round fails; polys: rounds x (degree + 1) canonical
+inline bool sumcheck_verify(int field_id, int degree, const Fe& claim, const std::vector<Fe>& polys, const std::vector<Fe>& challenges, Fe* final_claim) {
+    int ok = 0;
+    check(lurk_hip_sumcheck_verify(field_id, degree, challenges.size(), &claim, polys.data(), challenges.data(), final_claim, &ok));
+    return ok != 0;
+}
+// the matrices' multilinear extensions at the point whose eq tables are d_eq_x / d_eq_y (device, Montgomery): {A~, B~, C~}, Montgomery
+inline std::array<Fe, 3> sparse_mle(const R1CSShape& shape, const void* d_eq_x, size_t n_x, const void* d_eq_y, size_t n_y, void* stream = nullptr) {
+    std::array<Fe, 3> out;
+    check(lurk_hip_r1cs_sparse_mle_dev(shape.handle(), d_eq_x, n_x, d_eq_y, n_y, out.data(), stream));
+    return out;
+}
+
 // compute_witness_size (/root/reference/src/lem/multiframe.rs:503-516): elements a slot contributes to the witness vector
 inline size_t slot_witness_size(int field_id, int slot_type) {
     size_t n = 0;

@@ -118,3 +118,63 @@ def prove(curve: int, order: int, d_ck, ck_c_jac: np.ndarray, d_a, d_b, r0: int,
         return Ls, Rs, a_hat, ck_cur[:1].cpu().numpy().view(np.uint64).reshape(8)
     finally:
         lib.lurk_hip_msm_ctx_destroy(ctx)
+
+
+def s_vector(field_id: int, challenges, stream=None):
+    """The verifier's s vector, s[i] = prod_j (bit_{ell-1-j}(i) ? r_j : r_j^-1), as a (2^ell, 4) Montgomery device tensor in one launch
+    (lurk_hip_ipa_s_vector_dev).  challenges: canonical integers, non-zero and below the field order."""
+    import torch
+
+    ell = len(challenges)
+    if any(int(c) < 0 or int(c) >> 256 for c in challenges):
+        raise ValueError("a challenge does not fit 32 bytes")
+    ch = np.stack([_limbs(int(c)) for c in challenges]) if ell else np.zeros((1, 4), dtype=np.uint64)
+    out = torch.empty((1 << ell, 4), dtype=torch.int64, device="cuda")
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.load().lurk_hip_ipa_s_vector_dev(field_id, _lib.ptr(ch), ell, _lib.ptr(out), _lib.ptr(s)))
+    return out
+
+
+def verify(key, n: int, P_jac, ck_c_jac, Ls, Rs, a_hat: int, challenge, d_b=None, eq_point=None, stream=None):
+    """InnerProductArgument::verify under the resident ``CommitmentKey`` (lurk_hip_ipa_verify_dev): accepts iff
+    P + sum_j (r_j^2 L_j + r_j^-2 R_j) == [a_hat] <s, key> + [a_hat <s, b>] ck_c with b = d_b (device, Montgomery) or eq(eq_point).
+    P, ck_c (already scaled), L_j, R_j: 96-byte Jacobians; challenge: a ``_lib.KeccakRounds`` or challenge(round, L, R) -> r.
+    Returns (accepted, failed_check); n not a power of two raises (a call error, not a rejection)."""
+    import torch
+
+    rounds = max(len(Ls), 1)
+    l = np.zeros((rounds, 12), dtype=np.uint64)
+    r = np.zeros((rounds, 12), dtype=np.uint64)
+    for j, (a, b) in enumerate(zip(Ls, Rs)):
+        l[j], r[j] = a, b
+    if len(Ls) != len(Rs) or (n >= 1 and n & (n - 1) == 0 and len(Ls) != n.bit_length() - 1) or int(a_hat) < 0 or int(a_hat) >> 256:
+        return False, 1
+    failure = []
+
+    def on_round(_user, j, l_ptr, r_ptr, out_ptr):
+        try:
+            L = np.ctypeslib.as_array(ctypes.cast(l_ptr, ctypes.POINTER(ctypes.c_uint64)), shape=(12,)).copy()
+            Rr = np.ctypeslib.as_array(ctypes.cast(r_ptr, ctypes.POINTER(ctypes.c_uint64)), shape=(12,)).copy()
+            ctypes.memmove(out_ptr, int(challenge(j, L, Rr)).to_bytes(32, "little"), 32)
+            return 0
+        except BaseException as e:  # noqa: BLE001 - an exception must not unwind through the C frames
+            failure.append(e)
+            return 1
+
+    if isinstance(challenge, _lib.KeccakRounds):
+        cb_ptr, user = challenge.callback("ipa")
+    else:
+        cb = _lib.IPA_CHALLENGE_FN(on_round)
+        cb_ptr, user = ctypes.cast(cb, ctypes.c_void_p), None
+    pt = np.stack([_limbs(int(z)) for z in eq_point]) if eq_point is not None and len(eq_point) else None
+    P = np.ascontiguousarray(P_jac, dtype=np.uint64)
+    ck_c = np.ascontiguousarray(ck_c_jac, dtype=np.uint64)
+    ah = _limbs(int(a_hat))
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    acc, failed = ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.load().lurk_hip_ipa_verify_dev(key._ctx, n, _lib.ptr(P), _lib.ptr(ck_c), _lib.ptr(d_b), _lib.ptr(pt), _lib.ptr(l), _lib.ptr(r), _lib.ptr(ah), cb_ptr, user,
+                                             ctypes.byref(acc), ctypes.byref(failed), _lib.ptr(s))
+    if failure:
+        raise failure[0]
+    _lib.check(rc)
+    return bool(acc.value), failed.value

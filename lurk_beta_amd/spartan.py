@@ -383,3 +383,176 @@ class BatchedSpartanProver:
         _lib.check(_lib.load().lurk_hip_inner_product_dev(self.sf, _lib.ptr(d_a), _lib.ptr(d_b), d_a.shape[0], _lib.ptr(out),
                                                           _lib.ptr(torch.cuda.current_stream().cuda_stream)))
         return sumcheck._ints(out)[0] * self.provers[0].Rinv % self.q
+
+
+# ---- the verifiers -----------------------------------------------------------------------------------------------------------------
+# failed-check codes of the library's verifiers (include/lurk_hip.h: LURK_VERIFY_*)
+VERIFY_ACCEPTED, VERIFY_MALFORMED, VERIFY_OUTER, VERIFY_INNER, VERIFY_BATCH, VERIFY_OPENING = 0, 1, 2, 3, 4, 5
+_BASE_P = (0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001, 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001)
+
+
+class _Malformed(Exception):
+    """a value of the proof or the statement that cannot be marshalled (wrong count, not a 256-bit integer, a coordinate not reduced)"""
+
+
+def _scalars(vals, count: int) -> np.ndarray:
+    """`count` canonical integers as limbs, NOT reduced: the library rejects what is not below the field order."""
+    vals = list(vals)
+    if len(vals) != count:
+        raise _Malformed
+    if any(not isinstance(v, (int, np.integer)) or int(v) < 0 or int(v) >> 256 for v in vals):
+        raise _Malformed
+    return sumcheck._limbs([int(v) for v in vals]) if count else np.zeros((1, 4), dtype=np.uint64)
+
+
+def _jacobian(curve: int, pt) -> np.ndarray:
+    """A point as the proof dictionaries carry it (affine canonical integers, None = the identity) or as a 96-byte Jacobian -> Jacobian."""
+    if pt is None:
+        return np.zeros(12, dtype=np.uint64)
+    if isinstance(pt, np.ndarray):
+        if pt.size != 12:
+            raise _Malformed
+        return np.ascontiguousarray(pt, dtype=np.uint64).reshape(12)
+    p = _BASE_P[0 if curve == 0 else 1]
+    if len(pt) != 2 or any(int(c) < 0 or int(c) >= p for c in pt):
+        raise _Malformed
+    R = (1 << 256) % p
+    return np.concatenate([sumcheck._limbs([int(pt[0]) * R % p, int(pt[1]) * R % p]).reshape(8), sumcheck._limbs([R])[0]])
+
+
+def _ck_c_jacobian(curve: int, N: int, d_ck, ck_c) -> np.ndarray:
+    if ck_c is None:
+        if d_ck is None:
+            raise ValueError("the inner-product base is needed: d_ck (N + 1 points, the last one the base) or ck_c")
+        row = d_ck[N]
+        ck_c = (row.cpu().numpy() if hasattr(row, "cpu") else np.asarray(row)).view(np.uint64).reshape(8)
+    ck_c = np.ascontiguousarray(ck_c, dtype=np.uint64).reshape(-1)
+    return ck_c if ck_c.size == 12 else np.concatenate([ck_c, _mont_one(0 if curve == 0 else 1)])
+
+
+def _points(curve: int, pts, count: int) -> np.ndarray:
+    pts = list(pts)
+    if len(pts) != count:
+        raise _Malformed
+    out = np.zeros((max(count, 1), 12), dtype=np.uint64)
+    for j, pt in enumerate(pts):
+        out[j] = _jacobian(curve, pt)
+    return out
+
+
+class SpartanVerifier:
+    """The verifier of ``SpartanProver``'s proofs (CompressedSNARK::verify per curve, /root/reference/src/proof/nova.rs:358-373) as ONE
+    library call, lurk_hip_spartan_verify_dev: the shape stays resident, a verification runs two eq tables, one sparse evaluation of the
+    shape, the s vector and one commitment under the resident key on the device, the rest on the host.  mats as for the prover."""
+
+    def __init__(self, curve: int, order: int, mats, num_cons: int, num_vars: int, num_io: int):
+        self.curve, self.q, self.num_cons, self.num_vars, self.num_io = curve, order, num_cons, num_vars, num_io
+        self.sf = 1 if curve == 0 else 0
+        assert num_cons & (num_cons - 1) == 0 and num_vars & (num_vars - 1) == 0 and 1 + num_io <= num_vars
+        self.shape = R1CSShape(self.sf, num_cons, num_vars, num_io, *mats)
+        self._owns_shape = True
+        self.last_failed_check = None
+
+    @classmethod
+    def from_shape(cls, shape: R1CSShape, curve: int, order: int) -> "SpartanVerifier":
+        """Shares a resident shape (``prover.shape``): nothing is uploaded again."""
+        self = cls.__new__(cls)
+        self.curve, self.q, self.sf = curve, order, 1 if curve == 0 else 0
+        self.num_cons, self.num_vars, self.num_io = shape.num_cons, shape.num_vars, shape.num_io
+        self.shape, self._owns_shape, self.last_failed_check = shape, False, None
+        return self
+
+    def verify(self, X, u, comm_W_jac, comm_E_jac, proof: dict, key, d_ck=None, ck_c=None, label: bytes = None, stream=None) -> bool:
+        """proof: the dictionary the provers return.  key: the resident ``CommitmentKey`` that committed W and E; the inner-product base is
+        d_ck[N] (N = max(num_cons, num_vars)) or ck_c (an affine Montgomery point or a Jacobian).  Returns the verdict; the first failed
+        check (VERIFY_*) is left in ``last_failed_check`` (0 when accepted)."""
+        import ctypes
+
+        import torch
+
+        nc, nv = self.num_cons, self.num_vars
+        ell_x, ell_y = nc.bit_length() - 1, nv.bit_length()
+        N = max(nc, nv)
+        ell = N.bit_length() - 1
+        ck_c_jac = _ck_c_jacobian(self.curve, N, d_ck, ck_c)
+        if label is None:
+            label = b"lurk-hip spartan v2" + (b"pallas" if self.curve == 0 else b"vesta")
+        self.last_failed_check = VERIFY_MALFORMED
+        try:
+            if any(len(p) != 4 for p in proof["polys_outer"]) or any(len(p) != 3 for p in proof["polys_inner"]) or any(len(p) != 3 for p in proof["polys_batch"]):
+                raise _Malformed
+            bufs = dict(polys_outer=_scalars([c for p in proof["polys_outer"] for c in p], 4 * ell_x), claims_outer=_scalars(proof["claims_outer"], 3),
+                        eval_e=_scalars([proof["eval_E"]], 1), polys_inner=_scalars([c for p in proof["polys_inner"] for c in p], 3 * ell_y),
+                        eval_w=_scalars([proof["eval_W"]], 1), polys_batch=_scalars([c for p in proof["polys_batch"] for c in p], 3 * ell),
+                        evals_batch=_scalars(proof["evals_batch"], 2), ipa_l=_points(self.curve, proof["ipa_L"], ell), ipa_r=_points(self.curve, proof["ipa_R"], ell),
+                        ipa_a=_scalars([proof["ipa_a"]], 1))
+            x, uu = _scalars(X, self.num_io), _scalars([u], 1)
+            cw, ce = _jacobian(self.curve, comm_W_jac), _jacobian(self.curve, comm_E_jac)
+        except (_Malformed, KeyError, TypeError):
+            return False
+        pf = _lib.SpartanProofStruct(*[bufs[k].ctypes.data for k, _ in _lib.SpartanProofStruct._fields_])
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        acc, failed = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().lurk_hip_spartan_verify_dev(self.shape._h, nc, nv, self.num_io, key._ctx, _lib.ptr(ck_c_jac), _lib.ptr(x), _lib.ptr(uu), _lib.ptr(cw),
+                                                           _lib.ptr(ce), label, len(label), ctypes.byref(pf), ctypes.byref(acc), ctypes.byref(failed), _lib.ptr(s)))
+        self.last_failed_check = failed.value
+        return bool(acc.value)
+
+    def close(self):
+        if self._owns_shape:
+            self.shape.close()
+
+
+class BatchedSpartanVerifier:
+    """The verifier of ``BatchedSpartanProver``'s proofs (lurk_hip_spartan_verify_batch_dev).  ``verifiers``: one ``SpartanVerifier`` per
+    circuit, in the order the batch was proved in."""
+
+    def __init__(self, verifiers):
+        assert verifiers and all(v.curve == verifiers[0].curve for v in verifiers)
+        self.verifiers = list(verifiers)
+        self.curve, self.q = verifiers[0].curve, verifiers[0].q
+        self.last_failed_check = None
+
+    def verify(self, instances, proof: dict, key, d_ck=None, ck_c=None, label: bytes = None, stream=None) -> bool:
+        """instances[i] = dict(X, u, comm_W, comm_E) for verifiers[i] (further keys - the prover's d_W, d_E - are ignored)."""
+        import ctypes
+
+        import torch
+
+        n = len(self.verifiers)
+        ell_x = max(v.num_cons for v in self.verifiers).bit_length() - 1
+        ell_y = max(v.num_vars for v in self.verifiers).bit_length()
+        N = max(max(v.num_cons, v.num_vars) for v in self.verifiers)
+        ell = N.bit_length() - 1
+        ck_c_jac = _ck_c_jacobian(self.curve, N, d_ck, ck_c)
+        if label is None:
+            label = b"lurk-hip spartan v2" + (b"pallas" if self.curve == 0 else b"vesta") + b"/batched"
+        self.last_failed_check = VERIFY_MALFORMED
+        keep, arr = [], (_lib.SpartanInstanceStruct * n)()
+        try:
+            if len(instances) != n:
+                raise _Malformed
+            if any(len(p) != 4 for p in proof["polys_outer"]) or any(len(p) != 3 for p in proof["polys_inner"]) or any(len(p) != 3 for p in proof["polys_batch"]):
+                raise _Malformed
+            if len(proof["claims_outer"]) != n or any(len(c) != 3 for c in proof["claims_outer"]):
+                raise _Malformed
+            bufs = dict(polys_outer=_scalars([c for p in proof["polys_outer"] for c in p], 4 * ell_x),
+                        claims_outer=_scalars([c for cl in proof["claims_outer"] for c in cl], 3 * n), evals_e=_scalars(proof["evals_E"], n),
+                        polys_inner=_scalars([c for p in proof["polys_inner"] for c in p], 3 * ell_y), evals_w=_scalars(proof["evals_W"], n),
+                        polys_batch=_scalars([c for p in proof["polys_batch"] for c in p], 3 * ell), evals_batch=_scalars(proof["evals_batch"], 2 * n),
+                        ipa_l=_points(self.curve, proof["ipa_L"], ell), ipa_r=_points(self.curve, proof["ipa_R"], ell), ipa_a=_scalars([proof["ipa_a"]], 1))
+            for i, (v, it) in enumerate(zip(self.verifiers, instances)):
+                x, uu = _scalars(it["X"], v.num_io), _scalars([it["u"]], 1)
+                cw, ce = _jacobian(self.curve, it["comm_W"]), _jacobian(self.curve, it["comm_E"])
+                keep += [x, uu, cw, ce]
+                arr[i] = _lib.SpartanInstanceStruct(v.shape._h.value, None, v.num_cons, v.num_vars, v.num_io, x.ctypes.data, uu.ctypes.data, None, None, cw.ctypes.data,
+                                                    ce.ctypes.data)
+        except (_Malformed, KeyError, TypeError):
+            return False
+        pf = _lib.SpartanBatchProofStruct(*[bufs[k].ctypes.data for k, _ in _lib.SpartanBatchProofStruct._fields_])
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        acc, failed = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().lurk_hip_spartan_verify_batch_dev(ctypes.cast(arr, ctypes.c_void_p), n, key._ctx, _lib.ptr(ck_c_jac), label, len(label), ctypes.byref(pf),
+                                                                 ctypes.byref(acc), ctypes.byref(failed), _lib.ptr(s)))
+        self.last_failed_check = failed.value
+        return bool(acc.value)

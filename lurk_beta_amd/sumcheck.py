@@ -142,3 +142,22 @@ def prove_cubic_batch(field_id: int, modulus: int, quads, coeffs, challenge, str
     tensors of one common length (consumed; a table may be shared by several instances only if it is passed as separate copies).  The
     claim starts at 0 (every instance satisfied).  Returns (round polynomials, challenges, [final (A, B, C, D)(r) per instance], claim)."""
     return _prove_batch(field_id, modulus, 3, [tuple(q) for q in quads], coeffs, 0, challenge, stream)
+
+
+def verify(field_id: int, degree: int, claim: int, polys, challenges):
+    """SumcheckProof::verify on the host (lurk_hip_sumcheck_verify; no device needed): polys[j] = the round polynomial's degree + 1
+    canonical coefficients, challenges[j] = the round's challenge.  Returns the final claim, or None when a round's p(0) + p(1) misses
+    the running claim or a value is not reduced."""
+    import ctypes
+
+    rounds = len(polys)
+    if len(challenges) != rounds or any(len(p) != degree + 1 for p in polys):
+        return None
+    vals = [int(claim)] + [int(c) for p in polys for c in p] + [int(c) for c in challenges]
+    if any(v < 0 or v >> 256 for v in vals):
+        return None
+    pl = _limbs([c for p in polys for c in p]) if rounds else np.zeros((1, 4), dtype=np.uint64)
+    ch = _limbs(list(challenges)) if rounds else np.zeros((1, 4), dtype=np.uint64)
+    out, ok = np.zeros(4, dtype=np.uint64), ctypes.c_int(0)
+    _lib.check(_lib.load().lurk_hip_sumcheck_verify(field_id, degree, rounds, _lib.ptr(_limbs([claim])), _lib.ptr(pl), _lib.ptr(ch), _lib.ptr(out), ctypes.byref(ok)))
+    return _ints(out)[0] if ok.value else None

@@ -279,6 +279,73 @@ pub unsafe fn spartan_prove_batch(instances: &[lurk_hip_spartan_instance], key: 
     Ok(p)
 }
 
+/// The answer of a verification (`lurk_hip_spartan_verify_dev` / `_verify_batch_dev`): a proof that does not verify is a successful call.
+/// `failed_check` is one of `LURK_VERIFY_*` (0 = accepted, 1 malformed input, 2 outer / 3 inner / 4 batching sum-check, 5 the opening).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct Verdict {
+    pub accepted: bool,
+    pub failed_check: c_int,
+}
+/// The verifier of [`spartan_prove`]'s proof: the same statement without the witness and without the transposed shape.
+/// # Safety
+/// `key` holds at least max(`num_cons`, `num_vars`) points and is the key that committed W and E.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn spartan_verify(shape: &R1csShape, num_cons: usize, num_vars: usize, key: *mut lurk_hip_msm_ctx, ck_c: &[u8; 96], x: &[u8], u: &[u8; 32], comm_w: &[u8; 96],
+                             comm_e: &[u8; 96], label: &[u8], proof: &SpartanProof, stream: *mut c_void) -> Result<Verdict, Error> {
+    let log2 = |n: usize| n.trailing_zeros() as usize;
+    let (ell_x, ell_y, ell) = (log2(num_cons), log2(num_vars) + 1, log2(num_cons.max(num_vars)));
+    if proof.polys_outer.len() != ell_x * 128 || proof.polys_inner.len() != ell_y * 96 || proof.polys_batch.len() < ell * 96 || proof.ipa_l.len() < ell * 96
+        || proof.ipa_r.len() < ell * 96 || x.len() % 32 != 0 {
+        return Ok(Verdict { accepted: false, failed_check: LURK_VERIFY_MALFORMED });
+    }
+    // (the library only reads through these pointers)
+    let pf = lurk_hip_spartan_proof {
+        polys_outer: proof.polys_outer.as_ptr() as *mut c_void, claims_outer: proof.claims_outer.as_ptr() as *mut c_void, eval_e: proof.eval_e.as_ptr() as *mut c_void,
+        polys_inner: proof.polys_inner.as_ptr() as *mut c_void, eval_w: proof.eval_w.as_ptr() as *mut c_void, polys_batch: proof.polys_batch.as_ptr() as *mut c_void,
+        evals_batch: proof.evals_batch.as_ptr() as *mut c_void, ipa_l: proof.ipa_l.as_ptr() as *mut c_void, ipa_r: proof.ipa_r.as_ptr() as *mut c_void,
+        ipa_a: proof.ipa_a.as_ptr() as *mut c_void,
+    };
+    let (mut accepted, mut failed): (c_int, c_int) = (0, 0);
+    check(lurk_hip_spartan_verify_dev(shape.as_ptr(), num_cons, num_vars, x.len() / 32, key, ck_c.as_ptr().cast(), x.as_ptr().cast(), u.as_ptr().cast(),
+                                      comm_w.as_ptr().cast(), comm_e.as_ptr().cast(), label.as_ptr().cast(), label.len(), &pf, &mut accepted, &mut failed, stream))?;
+    Ok(Verdict { accepted: accepted != 0, failed_check: failed })
+}
+/// The verifier of [`spartan_prove_batch`]'s proof; of an instance `shape_t`, `d_w32_mont` and `d_e32_mont` are ignored (may be null).
+/// # Safety
+/// Every instance's shape, x, u and commitment pointers are valid; `key` as for [`spartan_verify`].
+pub unsafe fn spartan_verify_batch(instances: &[lurk_hip_spartan_instance], key: *mut lurk_hip_msm_ctx, ck_c: &[u8; 96], label: &[u8], proof: &SpartanBatchProof,
+                                   stream: *mut c_void) -> Result<Verdict, Error> {
+    let log2 = |n: usize| n.trailing_zeros() as usize;
+    let n = instances.len();
+    let max_nc = instances.iter().map(|i| i.num_cons).max().unwrap_or(2);
+    let max_nv = instances.iter().map(|i| i.num_vars).max().unwrap_or(2);
+    let (ell_x, ell_y, ell) = (log2(max_nc), log2(max_nv) + 1, log2(max_nc.max(max_nv)));
+    if proof.polys_outer.len() != ell_x * 128 || proof.claims_outer.len() != n * 96 || proof.evals_e.len() != n * 32 || proof.polys_inner.len() != ell_y * 96
+        || proof.evals_w.len() != n * 32 || proof.polys_batch.len() < ell * 96 || proof.evals_batch.len() != 2 * n * 32 || proof.ipa_l.len() < ell * 96
+        || proof.ipa_r.len() < ell * 96 {
+        return Ok(Verdict { accepted: false, failed_check: LURK_VERIFY_MALFORMED });
+    }
+    let pf = lurk_hip_spartan_batch_proof {
+        polys_outer: proof.polys_outer.as_ptr() as *mut c_void, claims_outer: proof.claims_outer.as_ptr() as *mut c_void, evals_e: proof.evals_e.as_ptr() as *mut c_void,
+        polys_inner: proof.polys_inner.as_ptr() as *mut c_void, evals_w: proof.evals_w.as_ptr() as *mut c_void, polys_batch: proof.polys_batch.as_ptr() as *mut c_void,
+        evals_batch: proof.evals_batch.as_ptr() as *mut c_void, ipa_l: proof.ipa_l.as_ptr() as *mut c_void, ipa_r: proof.ipa_r.as_ptr() as *mut c_void,
+        ipa_a: proof.ipa_a.as_ptr() as *mut c_void,
+    };
+    let (mut accepted, mut failed): (c_int, c_int) = (0, 0);
+    check(lurk_hip_spartan_verify_batch_dev(instances.as_ptr(), n, key, ck_c.as_ptr().cast(), label.as_ptr().cast(), label.len(), &pf, &mut accepted, &mut failed, stream))?;
+    Ok(Verdict { accepted: accepted != 0, failed_check: failed })
+}
+/// `SumcheckProof::verify` on the host (`lurk_hip_sumcheck_verify`, no device needed): the final claim, or `None` when a round fails.
+pub fn sumcheck_verify(field_id: c_int, degree: c_int, claim: &[u8; 32], polys: &[u8], challenges: &[u8]) -> Result<Option<[u8; 32]>, Error> {
+    let rounds = challenges.len() / 32;
+    if challenges.len() % 32 != 0 || degree < 2 || polys.len() != rounds * (degree as usize + 1) * 32 {
+        return Ok(None);
+    }
+    let (mut out, mut ok): ([u8; 32], c_int) = ([0; 32], 0);
+    check(unsafe { lurk_hip_sumcheck_verify(field_id, degree, rounds, claim.as_ptr().cast(), polys.as_ptr().cast(), challenges.as_ptr().cast(), out.as_mut_ptr().cast(), &mut ok) })?;
+    Ok(if ok != 0 { Some(out) } else { None })
+}
+
 /// One curve's half of `RecursiveSNARK::prove_step`: the running relaxed pair (z1 = [W | u | X], E) and the running instance stay in
 /// the context; `step` is `NIFS::prove` (commit W2, cross term, commit T, r from the transcript, fold).
 /// Borrowing the shape and the key ties their lifetimes to the context's, as the C ABI requires.
