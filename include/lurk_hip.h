@@ -37,10 +37,23 @@ extern "C" {
 #define LURK_FIELD_PALLAS_FP 0 /* pasta_curves::Fp  = pallas::Base  = vesta::Scalar */
 #define LURK_FIELD_PALLAS_FQ 1 /* pasta_curves::Fq  = pallas::Scalar = vesta::Base  */
 #define LURK_FIELD_BN254_FR 2  /* halo2curves::bn256::Fr (the field of every KAT in the reference) */
+#define LURK_FIELD_BN254_FQ 3  /* halo2curves::bn256::Fq = grumpkin::Fr: the BN254 base field.  Offered where a commitment needs it
+                                * (the MSM contexts, the point helpers, lurk_hip_synth_scalars_dev); every other entry point that
+                                * takes a field id refuses it */
 
 /* curve ids (CurveCycleEquipped engines, /root/reference/src/proof/nova.rs:40-71) */
 #define LURK_CURVE_PALLAS 0
 #define LURK_CURVE_VESTA 1
+/* the BN254 / Grumpkin cycle (lurk-beta's default: Bn256EngineKZG + GrumpkinEngine).  Both have a = 0: BN254 G1 is y^2 = x^3 + 3 over
+ * Fq with scalars in Fr, Grumpkin is y^2 = x^3 - 17 over Fr with scalars in Fq.  Layouts as halo2curves `repr-c` has them, recalled
+ * [MEM] and unpinned like the Pasta ones: affine {x, y} 64 B Montgomery with (0, 0) for the identity, Jacobian {x, y, z} 96 B.
+ * Offered: every lurk_hip_msm_* / lurk_hip_msm_ctx_* / lurk_hip_msm_multi_* commitment path, the point helpers,
+ * lurk_hip_synth_bases_dev (generators (1, 2) and (1, sqrt(-16))) and lurk_hip_fold_ctx_* on BN254 with a caller-supplied challenge.
+ * Refused by name (non-zero, the curve named in lurk_hip_last_error()): lurk_hip_msm_ctx_from_label and the other hash-to-curve calls,
+ * lurk_hip_msm_ctx_fold_key_dev, the IPA / Spartan / verify calls, lurk_hip_fold_step, _set_pp_digest, _challenge and
+ * lurk_hip_nifs_* (no Poseidon constants over Fq yet), and a folding context on Grumpkin. */
+#define LURK_CURVE_BN254 2
+#define LURK_CURVE_GRUMPKIN 3
 
 #define LURK_HIP_OK 0
 #define LURK_HIP_ERR_NO_DEVICE 1
@@ -91,6 +104,10 @@ int lurk_hip_msm_pallas(void* out_jacobian96, const void* bases_affine64, size_t
                         const void* scalars32, int is_mont);
 int lurk_hip_msm_vesta(void* out_jacobian96, const void* bases_affine64, size_t npoints,
                        const void* scalars32, int is_mont);
+int lurk_hip_msm_bn254(void* out_jacobian96, const void* bases_affine64, size_t npoints,
+                       const void* scalars32, int is_mont);
+int lurk_hip_msm_grumpkin(void* out_jacobian96, const void* bases_affine64, size_t npoints,
+                          const void* scalars32, int is_mont);
 /* The two symbols above under the names and the signature pasta-msm's src/lib.rs binds (pasta-msm 0.1.x, arecibo's
  * dependency; un-vendored: /root/reference/Cargo.toml:128 pulls it in through nova): a pasta-msm whose build script links
  * liblurk_hip.so instead of compiling its own C objects needs no source change.  They return nothing, as the originals; a
@@ -115,6 +132,13 @@ typedef struct lurk_hip_rust_error {
 } lurk_hip_rust_error;
 lurk_hip_rust_error cuda_pippenger_pallas(void* out_jacobian96, const void* points_affine64, size_t npoints, const void* scalars32, bool is_mont);
 lurk_hip_rust_error cuda_pippenger_vesta(void* out_jacobian96, const void* points_affine64, size_t npoints, const void* scalars32, bool is_mont);
+/* grumpkin-msm's symbols (arecibo's MSM crate for the BN254 / Grumpkin cycle; names and signatures recalled [MEM], unpinned): the same
+ * behaviour as the four pasta-msm names above - mult_pippenger_* return nothing and abort with the library's message on failure,
+ * cuda_pippenger_* return the RustError by value. */
+void mult_pippenger_bn254(void* out_jacobian96, const void* points_affine64, size_t npoints, const void* scalars32, bool is_mont);
+void mult_pippenger_grumpkin(void* out_jacobian96, const void* points_affine64, size_t npoints, const void* scalars32, bool is_mont);
+lurk_hip_rust_error cuda_pippenger_bn254(void* out_jacobian96, const void* points_affine64, size_t npoints, const void* scalars32, bool is_mont);
+lurk_hip_rust_error cuda_pippenger_grumpkin(void* out_jacobian96, const void* points_affine64, size_t npoints, const void* scalars32, bool is_mont);
 
 /* Resident-bases context: the commitment key `ck` is constant for the whole proof
  * (/root/reference/src/proof/nova.rs:196-216), so it is uploaded once and kept in HBM.
@@ -243,6 +267,9 @@ int lurk_hip_msm_ctx_from_label(lurk_hip_msm_ctx** ctx, int curve, const void* l
  * reading 13 x the bytes from disk unless the file is hot in the page cache). */
 int lurk_hip_msm_ctx_save(const lurk_hip_msm_ctx* ctx, const char* path, int with_table);
 int lurk_hip_msm_ctx_load(lurk_hip_msm_ctx** ctx, const char* path, int flags);
+/* the same for a caller that knows which curve its key is over: a file that records another curve is refused (both curves named in
+ * lurk_hip_last_error()) before anything is uploaded */
+int lurk_hip_msm_ctx_load_curve(lurk_hip_msm_ctx** ctx, int curve, const char* path, int flags);
 
 /* One process, several GPUs.  arecibo's prover is a single process (/root/reference/src/proof/nova.rs:304-326: one
  * witness-producer thread, rayon inside), so the multi-GPU form of the commitment is a context that owns a list

@@ -6,8 +6,8 @@ in liblurk_hip.so on the GPU - there is no CPU fallback."""
 from . import _lib
 from ._lib import LurkHipError
 
-FIELD_PALLAS_FP, FIELD_PALLAS_FQ, FIELD_BN254_FR = 0, 1, 2
-CURVE_PALLAS, CURVE_VESTA = 0, 1
+FIELD_PALLAS_FP, FIELD_PALLAS_FQ, FIELD_BN254_FR, FIELD_BN254_FQ = 0, 1, 2, 3
+CURVE_PALLAS, CURVE_VESTA, CURVE_BN254, CURVE_GRUMPKIN = 0, 1, 2, 3
 
 from .poseidon import PoseidonCache, HashArity, poseidon_batch, poseidon_tree8, poseidon_constants  # noqa: E402
 
@@ -24,5 +24,5 @@ __all__ = [
     "CommitmentKey", "MultiCommitmentKey", "msm", "point_sum", "point_to_affine", "ntt", "R1CSShape", "fold_vec", "fold_vecs", "FoldingContext", "NivcFoldingContext", "nifs_challenge", "nova_ro_squeeze", "point_mul", "public_io", "MultiFrameWitness", "slot_constraints", "slot_witness", "slot_witness_size",
     "SpartanProver", "BatchedSpartanProver", "SpartanVerifier", "BatchedSpartanVerifier",
     "LurkHipError", "PoseidonCache", "HashArity", "poseidon_batch", "poseidon_tree8", "poseidon_constants",
-    "FIELD_PALLAS_FP", "FIELD_PALLAS_FQ", "FIELD_BN254_FR", "CURVE_PALLAS", "CURVE_VESTA",
+    "FIELD_PALLAS_FP", "FIELD_PALLAS_FQ", "FIELD_BN254_FR", "FIELD_BN254_FQ", "CURVE_PALLAS", "CURVE_VESTA", "CURVE_BN254", "CURVE_GRUMPKIN",
 ]

@@ -60,6 +60,12 @@ SIGNATURES = {
     "mult_pippenger_vesta": (None, [c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_bool]),
     "cuda_pippenger_pallas": (RustError, [c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_bool]),   # pasta-msm's GPU symbol names
     "cuda_pippenger_vesta": (RustError, [c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_bool]),
+    "lurk_hip_msm_bn254": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int]),
+    "lurk_hip_msm_grumpkin": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int]),
+    "mult_pippenger_bn254": (None, [c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_bool]),   # grumpkin-msm's symbol names
+    "mult_pippenger_grumpkin": (None, [c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_bool]),
+    "cuda_pippenger_bn254": (RustError, [c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_bool]),
+    "cuda_pippenger_grumpkin": (RustError, [c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_bool]),
     "lurk_hip_msm_ctx_create": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, c_int]),
     "lurk_hip_msm_ctx_create_dev": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "lurk_hip_msm_ctx_run": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int]),
@@ -84,6 +90,7 @@ SIGNATURES = {
     "lurk_hip_msm_ctx_device": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "lurk_hip_msm_ctx_save": (c_int, [c_void_p, ctypes.c_char_p, c_int]),
     "lurk_hip_msm_ctx_load": (c_int, [ctypes.POINTER(c_void_p), ctypes.c_char_p, c_int]),
+    "lurk_hip_msm_ctx_load_curve": (c_int, [ctypes.POINTER(c_void_p), c_int, ctypes.c_char_p, c_int]),
     "lurk_hip_msm_multi_create": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, ctypes.POINTER(c_int), c_int, c_int]),
     "lurk_hip_msm_multi_num_shards": (c_int, [c_void_p]),
     "lurk_hip_msm_multi_shard": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),

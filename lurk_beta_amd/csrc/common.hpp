@@ -191,6 +191,7 @@ struct MsmTableView {
     int curve = 0, window_bits = 0, windows = 1, form = 0, device = 0;
 };
 MsmTableView msm_ctx_table_view(const lurk_hip_msm_ctx* ctx);
+int msm_multi_curve(const lurk_hip_msm_multi* key);  // the curve id of a multi-device key (msm.hip)
 // lurk_hip_msm_ctx_wait_pair without the normalisation: the two commitments as XYZZ points (4 x 32 B each, Montgomery limbs) - the caller
 // adds to them and normalises both with one field inversion (ipa.hip: ~17 us of host time per inversion, five per round before)
 void msm_ctx_wait_pair_xyzz(lurk_hip_msm_ctx* ctx, int slot, void* out_lo_xyzz128, void* out_hi_xyzz128);
@@ -250,6 +251,23 @@ struct ArenaBuf {
     ArenaBuf(const ArenaBuf&) = delete;
     ArenaBuf& operator=(const ArenaBuf&) = delete;
 };
+
+// curve ids by name, for messages; entry points that exist for the Pasta cycle only refuse the BN254 cycle (and anything else) with it
+inline const char* curve_name(int curve) {
+    switch (curve) {
+        case LURK_CURVE_PALLAS: return "Pallas";
+        case LURK_CURVE_VESTA: return "Vesta";
+        case LURK_CURVE_BN254: return "BN254";
+        case LURK_CURVE_GRUMPKIN: return "Grumpkin";
+    }
+    return "unknown";
+}
+inline void require_pasta_curve(int curve, const char* what) {
+    if (curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA) return;
+    if (curve == LURK_CURVE_BN254 || curve == LURK_CURVE_GRUMPKIN)
+        throw HipFailure{LURK_HIP_ERR_INVALID_ARG, std::string(what) + " is not offered on " + curve_name(curve) + " (Pallas and Vesta only)"};
+    throw HipFailure{LURK_HIP_ERR_INVALID_ARG, "unknown curve id"};
+}
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 

@@ -7,7 +7,7 @@
 // "R-bounded" at every loop boundary: tight limbs (< 2^29, top limb < 2^27) and value < 2^259.
 // Inside a mixed addition values grow through lazy subtractions (each adds the 64p bias, < 2^260); every
 // such value is carried (limbs tight again) before it is multiplied, and the two stored sums X3, Y3 are
-// brought back under 2^259 with f29_reduce (subtract floor(v / 2^254) * p: Pasta primes are 2^254 + eps).
+// brought back under 2^259 with f29_reduce (subtract a multiple of p read off the top limb: to below 2^255.1 for every modulus here).
 #pragma once
 #include "curve.cuh"
 #include "field29.cuh"
@@ -17,6 +17,10 @@
 #endif
 #ifndef LURK_ACC_AFFINE_FIRST
 #define LURK_ACC_AFFINE_FIRST 1
+#endif
+// how the two rare doubling branches are compiled (out of line by default: see xyzz29_double_affine)
+#ifndef LURK_F29_RARE_ATTR
+#define LURK_F29_RARE_ATTR __attribute__((noinline))
 #endif
 
 namespace lurk {
@@ -36,12 +40,18 @@ LURK_HD F29<P> f29_carry_signed(const int32_t* t) {
     return r;
 }
 
+// The Pasta primes are 2^254 + eps with eps < 2^126 and p == 1 mod 2^29; two shortcuts below lean on that shape.  The BN254 primes
+// (0.756 * 2^254, no zero limbs, p != 1 mod 2^29) take the general forms.
+template <class P>
+LURK_HD constexpr bool f29_pasta_shape() {
+    return P::NBITS == 255 && f29_mod<P>(0) == 1u && f29_mod<P>(5) == 0u && f29_mod<P>(6) == 0u && f29_mod<P>(7) == 0u;
+}
+
 // v (tight limbs, top limb any u32 < 2^31) -> equivalent value < 2^255.1 with tight limbs.
 // Pasta: p = 2^254 + eps, eps < 2^126 (limbs 0..4), so  v - k p = (v mod 2^254) - k eps  with k = v >> 254;
 // adding p once keeps it positive:  (v mod 2^254) + 2^254 - (k - 1) eps.
 template <class P>
-LURK_HD F29<P> f29_reduce(const F29<P>& v) {
-    static_assert(P::ID != 2, "f29_reduce is specialised for the Pasta primes");
+LURK_HD F29<P> f29_reduce_pasta(const F29<P>& v) {
     const uint32_t k = v.l[8] >> 22;                    // floor(v / 2^254)  (< 2^9)
     const uint32_t km1 = k ? k - 1 : 0;                 // k = 0: value is already < 2^254, add nothing, subtract nothing
     // e = (k-1) * eps as normalised 29-bit limbs (eps limbs = modulus limbs 0..4)
@@ -58,6 +68,38 @@ LURK_HD F29<P> f29_reduce(const F29<P>& v) {
     t[7] = (int32_t)v.l[7];
     t[8] = (int32_t)(v.l[8] & ((1u << 22) - 1u)) + (k ? (int32_t)(1u << 22) : 0);
     return f29_carry_signed<P>(t);
+}
+// Any modulus of 253 or 254 bits: v - q p with q an under-estimate of floor(v / p) taken from the top limb alone.  With T = v.l[8]
+// (= floor(v / 2^232) < 2^31) and D = (p >> 232) + 1 (so D 2^232 > p), q = floor(T mu / 2^53), mu = floor(2^53 / D):
+//   q <= T / D <= v / p                         the difference is never negative;
+//   q >  T / D - 2  (T mu / 2^53 > T / D - T / 2^53, one more for the floor) and T > v / 2^232 - 1, hence
+//   v - q p < v (1 - p / (D 2^232)) + p / D + 2 p <= v / D + p / D + 2 p < 2^263 / 2^21 + 2^233 + 2 p < 2^255.1   (D > 2^21, 2 p < 2^255).
+// q < 2^10, so q p's running carry stays below 2^39; the limb differences are in (-2^29, 2^29) and the top one in (-2^31, 2^31).
+template <class P>
+LURK_HD F29<P> f29_reduce_general(const F29<P>& v) {
+    constexpr uint32_t D = (P::mod(7) >> 8) + 1u;                       // bits 232.. of p, rounded up
+    static_assert(D > (1u << 21) && D <= (1u << 22), "f29_reduce_general: the modulus must have 253 or 254 bits");
+    constexpr uint64_t mu = ((uint64_t)1 << 53) / D;                    // < 2^32
+    F29_ASSERT(v.l[8] < (1u << 31), "f29_reduce: top limb >= 2^31");
+    const uint32_t q = (uint32_t)(((uint64_t)v.l[8] * mu) >> 53);
+    int32_t t[9];
+    uint64_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        c += (uint64_t)q * f29_mod<P>(i);
+        t[i] = (int32_t)v.l[i] - (int32_t)((uint32_t)c & F29_MASK);
+        c >>= 29;
+    }
+    c += (uint64_t)q * f29_mod<P>(8);
+    t[8] = (int32_t)v.l[8] - (int32_t)(uint32_t)c;                      // >= the borrows of the limbs below: v - q p >= 0
+    const F29<P> r = f29_carry_signed<P>(t);
+    F29_ASSERT(r.l[8] < (1u << 24), "f29_reduce: result not below 2^256");
+    return r;
+}
+template <class P>
+LURK_HD F29<P> f29_reduce(const F29<P>& v) {
+    if constexpr (f29_pasta_shape<P>()) return f29_reduce_pasta<P>(v);
+    else return f29_reduce_general<P>(v);
 }
 
 template <class P>
@@ -84,11 +126,21 @@ LURK_HD void xyzz29_from_xyzz(const Xyzz<P>& a, Xyzz29<P>& r, bool& is_identity)
     r.zzz = f29_from_mont256<P>(a.zzz);
 }
 
-// value == 0 mod p ?  for a carried value v < 2^261 (so v = k p with k < 128): exact, used after the cheap
-// pre-filter v.l[0] < 128 (p == 1 mod 2^29, hence (k p) mod 2^29 == k)
+// value == 0 mod p ?  for a carried value v < 2^261, so v = k p with k < 256 (128 for the Pasta primes).  k is read off the lowest
+// limb: k = v.l[0] * p^-1 mod 2^29 (Pasta: p == 1 mod 2^29, k = v.l[0]).  f29_maybe_multiple_of_p is the cheap pre-filter (almost
+// every value fails it), f29_is_multiple_of_p the exact comparison behind it.
+template <class P>
+LURK_HD uint32_t f29_multiple_candidate(const F29<P>& v) {
+    if constexpr (f29_pasta_shape<P>()) return v.l[0];
+    else return (v.l[0] * ((0u - f29_inv<P>()) & F29_MASK)) & F29_MASK;  // -(-p^-1) = p^-1 mod 2^29
+}
+template <class P>
+LURK_HD bool f29_maybe_multiple_of_p(const F29<P>& v) {
+    return f29_multiple_candidate<P>(v) < (f29_pasta_shape<P>() ? 128u : 256u);
+}
 template <class P>
 LURK_HD bool f29_is_multiple_of_p(const F29<P>& v) {
-    const uint32_t k = v.l[0];
+    const uint32_t k = f29_multiple_candidate<P>(v);
     uint64_t c = 0;
     bool eq = true;
 #pragma unroll
@@ -102,10 +154,10 @@ LURK_HD bool f29_is_multiple_of_p(const F29<P>& v) {
 }
 
 // exceptional case of the mixed addition: acc and (+/-)q share their x and y, the sum is 2(+/-q): affine
-// doubling (a = 0 on both Pasta curves).  Rare, so out of line; arguments and result by value so that the
+// doubling (a = 0 on the Pasta curves, BN254 G1 and Grumpkin).  Rare, so out of line; arguments and result by value so that the
 // caller's accumulator never has its address taken (it must stay in registers).
 template <class P>
-LURK_HD __attribute__((noinline)) Xyzz29<P> xyzz29_double_affine(F29<P> qx, F29<P> qy_signed) {
+LURK_HD LURK_F29_RARE_ATTR Xyzz29<P> xyzz29_double_affine(F29<P> qx, F29<P> qy_signed) {
     const F29<P> u = f29_dbl<P>(qy_signed);                      // limbs < 2^30, value < 2^260
     const F29<P> v = f29_mul<P>(u, u);                           // < 2^259 + p
     const F29<P> w = f29_mul<P>(u, v);
@@ -156,8 +208,8 @@ LURK_HD void xyzz29_madd(Xyzz29<P>& acc, bool& acc_id, const Affine<P>& q, bool 
         r.l[i] = s2.l[i] + (negate ? acc.y.l[i] : f29_bias<P>(i) - acc.y.l[i]);
     }
     r = f29_carry<P>(r);
-    if (p.l[0] < 128u && f29_is_multiple_of_p<P>(p)) {
-        if (r.l[0] < 128u && f29_is_multiple_of_p<P>(r)) {  // r (or r' = -r) == 0: equal points
+    if (f29_maybe_multiple_of_p<P>(p) && f29_is_multiple_of_p<P>(p)) {
+        if (f29_maybe_multiple_of_p<P>(r) && f29_is_multiple_of_p<P>(r)) {  // r (or r' = -r) == 0: equal points
             const F29<P> qys = negate ? f29_reduce<P>(f29_carry<P>(f29_sub<P>(f29_zero<P>(), qy))) : qy;
             acc = xyzz29_double_affine<P>(qx, qys);
         } else {
@@ -231,7 +283,7 @@ LURK_HD Xyzz29<P> xyzz29_dbl(const Xyzz29<P>& a) {
 // Doubling of a general XYZZ29 point: only reached when two equal partial sums meet in a reduction tree - rare, so it goes
 // through the 32-bit-limb group law (out of line; arguments and result by value, see xyzz29_double_affine).
 template <class P>
-LURK_HD __attribute__((noinline)) Xyzz29<P> xyzz29_double_general(Xyzz29<P> a) {
+LURK_HD LURK_F29_RARE_ATTR Xyzz29<P> xyzz29_double_general(Xyzz29<P> a) {
     const Xyzz<P> d = xyzz_dbl<P>(xyzz29_to_xyzz<P>(a, false));
     Xyzz29<P> r;
     bool id;
@@ -264,8 +316,8 @@ LURK_HD void xyzz29_add(Xyzz29<P>& acc, bool& acc_id, const Xyzz29<P>& q, bool q
     const F29<P> s2 = f29_mul<P>(q.y, acc.zzz);
     const F29<P> p = f29_carry<P>(f29_sub<P>(u2, u1));  // U2 - U1 + 64p < 2^260.3
     const F29<P> r = f29_carry<P>(f29_sub<P>(s2, s1));
-    if (p.l[0] < 128u && f29_is_multiple_of_p<P>(p)) {
-        if (r.l[0] < 128u && f29_is_multiple_of_p<P>(r)) acc = xyzz29_double_general<P>(acc);  // equal points
+    if (f29_maybe_multiple_of_p<P>(p) && f29_is_multiple_of_p<P>(p)) {
+        if (f29_maybe_multiple_of_p<P>(r) && f29_is_multiple_of_p<P>(r)) acc = xyzz29_double_general<P>(acc);  // equal points
         else acc_id = true;                                                                     // opposite points
         return;
     }

@@ -87,6 +87,25 @@ struct Bn254Fr {  // BN254 scalar field: the field every golden vector of the re
     LURK_HD static constexpr uint32_t w32(int i) { return 0; }  // NTT is not offered over BN254
 };
 
+struct Bn254Fq {  // BN254 base field = Grumpkin's scalar field (p - 1 has 2-adicity 1: no NTT)
+    static constexpr int ID = 3;
+    static constexpr int NBITS = 254;
+    static constexpr uint32_t INV = 0xe4866389u;
+    LURK_HD static constexpr uint32_t mod(int i) {
+        constexpr uint32_t m[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+        return m[i];
+    }
+    LURK_HD static constexpr uint32_t r(int i) {
+        constexpr uint32_t m[8] = {0xc58f0d9du, 0xd35d438du, 0xf5c70b3du, 0x0a78eb28u, 0x7879462cu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u};
+        return m[i];
+    }
+    LURK_HD static constexpr uint32_t r2(int i) {
+        constexpr uint32_t m[8] = {0x538afa89u, 0xf32cfc5bu, 0xd44501fbu, 0xb5e71911u, 0x0a417ff6u, 0x47ab1effu, 0xcab8351fu, 0x06d89f71u};
+        return m[i];
+    }
+    LURK_HD static constexpr uint32_t w32(int i) { return 0; }
+};
+
 // ------------------------------------------------------------------------------------------
 template <class P>
 struct alignas(16) Fe {
@@ -408,6 +427,7 @@ inline Fe<P> fe_mul_host64(const Fe<P>& a, const Fe<P>& b) {
 #endif
 }  // namespace lurk
 #include "field_mul_asm.cuh"
+#include "field_mul_asm_bn254fq.cuh"
 namespace lurk {
 template <class P>
 LURK_HD Fe<P> fe_mul_inline(const Fe<P>& a, const Fe<P>& b) {

@@ -101,7 +101,7 @@ LURK_HD F29<P> f29_add(const F29<P>& a, const F29<P>& b) {
 // BIAS = 64p with its limbs re-balanced so that limbs 0..7 lie in [2^30, 2^30 + 2^29) and the top limb is
 // ~2^28: limb_i += 2^30 and limb_{i+1} -= 2 (2^30 * 2^(29 i) = 2 * 2^(29 (i+1))).  Subtracting limb-wise any
 // b whose limbs are at most the bias's never underflows: limbs 0..7 <= 2^30 - 2, and the top limb at most 2^28 - 2 (Pasta) or
-// 0xc19139a (BN254), e.g. b tight with value < 2^259.5.
+// 0xc19139a (both BN254 fields), e.g. b tight with value < 2^259.5.
 template <class P>
 LURK_HD constexpr uint32_t f29_bias(int i) {
     uint64_t carry = 0;
@@ -171,6 +171,7 @@ LURK_HD F29<P> f29_mul_portable(const F29<P>& a, const F29<P>& b) {
 
 }  // namespace lurk
 #include "field29_mul_asm.cuh"
+#include "field29_mul_asm_bn254fq.cuh"
 namespace lurk {
 
 template <class P>

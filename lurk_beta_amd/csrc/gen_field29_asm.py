@@ -19,6 +19,10 @@ FIELDS = {
     "PallasFq": 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001,
     "Bn254Fr": 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001,
 }
+# --bn254fq: the blocks of the fourth pack go into field29_mul_asm_bn254fq.cuh (field29_mul_asm.cuh stays what it was)
+BN254FQ_FIELDS = {
+    "Bn254Fq": 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47,
+}
 W = 29
 MASK = (1 << W) - 1
 ACC_LO, ACC_HI = 16, 17
@@ -140,16 +144,21 @@ __device__ __forceinline__ F29<{name}> f29_mul_asm<{name}>(const F29<{name}>& a,
 
 
 def main():
+    bn254fq = sys.argv[1:] == ["--bn254fq"]
     out = [
+        "// field29_mul_asm_bn254fq.cuh - GENERATED by gen_field29_asm.py --bn254fq; do not edit." if bn254fq else
         "// field29_mul_asm.cuh - GENERATED by gen_field29_asm.py; do not edit.",
         "#pragma once",
         "#if defined(__HIP_DEVICE_COMPILE__)",
         "namespace lurk {",
-        "template <class P> __device__ __forceinline__ F29<P> f29_mul_asm(const F29<P>& a, const F29<P>& b);",
-        "template <class P> __device__ __forceinline__ F29<P> f29_sqr_asm(const F29<P>& a);",
-        "",
     ]
-    for name, mod in FIELDS.items():
+    if not bn254fq:  # (the --bn254fq header holds specialisations only: it is included right after this one)
+        out += [
+            "template <class P> __device__ __forceinline__ F29<P> f29_mul_asm(const F29<P>& a, const F29<P>& b);",
+            "template <class P> __device__ __forceinline__ F29<P> f29_sqr_asm(const F29<P>& a);",
+        ]
+    out.append("")
+    for name, mod in (BN254FQ_FIELDS if bn254fq else FIELDS).items():
         out.append(cxx(name, mod))
         out.append(cxx_sqr(name, mod))
     out += ["}  // namespace lurk", "#endif"]

@@ -19,6 +19,8 @@ asm statements carries ~190 `s_nop`s and ~60 moves per product.  Here the whole 
     limb value 1 is the inline constant.
 
 Run:  python gen_field_asm.py > field_mul_asm.cuh
+      python gen_field_asm.py --bn254fq > field_mul_asm_bn254fq.cuh   (the BN254 base field: specialisations only, included
+                                                                       by field.cuh right after field_mul_asm.cuh)
 """
 import sys
 
@@ -26,6 +28,10 @@ FIELDS = {
     "PallasFp": 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001,
     "PallasFq": 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001,
     "Bn254Fr": 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001,
+}
+# --bn254fq: the blocks of the fourth pack go into a header of their own (field_mul_asm.cuh stays what it was)
+BN254FQ_FIELDS = {
+    "Bn254Fq": 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47,
 }
 
 ACC_LO, ACC_HI, H = 16, 17, 18
@@ -229,7 +235,25 @@ __device__ __forceinline__ Fe<{name}> fe_mul_asm<{name}>(const Fe<{name}>& a, co
 """
 
 
+def main_bn254fq():
+    out = [
+        "// field_mul_asm_bn254fq.cuh - GENERATED by gen_field_asm.py --bn254fq; do not edit.",
+        "// The BN254 base field's blocks: specialisations of the templates field_mul_asm.cuh declares (included right after it).",
+        "#pragma once",
+        "#if defined(__HIP_DEVICE_COMPILE__)",
+        "namespace lurk {",
+        "",
+    ]
+    for name, mod in BN254FQ_FIELDS.items():
+        out.append(cxx(name, mod))
+        out.append(cxx_redc(name, mod))
+    out += ["}  // namespace lurk", "#endif"]
+    sys.stdout.write("\n".join(out) + "\n")
+
+
 def main():
+    if sys.argv[1:] == ["--bn254fq"]:
+        return main_bn254fq()
     out = [
         "// field_mul_asm.cuh - GENERATED by gen_field_asm.py; do not edit.",
         "// One hand-scheduled gfx950 asm block per 255-bit Montgomery product (see the generator's docstring).",

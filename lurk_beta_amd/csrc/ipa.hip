@@ -575,6 +575,7 @@ int lurk_hip_ipa_prove_dev(lurk_hip_msm_ctx* key, void* d_a, void* d_b, size_t n
         size_t points = 0;
         if (lurk_hip_msm_ctx_info(key, &curve, &points, &bits, nullptr) != 0 || lurk_hip_msm_ctx_device(key, &device) != 0)
             throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
+        require_pasta_curve(curve, "lurk_hip_ipa_prove_dev");
         DeviceGuard dg(device);
         if (curve == LURK_CURVE_PALLAS)
             ipa_prove_resident<PallasFp, PallasFq>(key, curve, LURK_FIELD_PALLAS_FQ, d_a, d_b, n, ck_c_jacobian96, challenge, user, (uint64_t*)out_l_jacobian96,
@@ -589,6 +590,7 @@ int lurk_hip_msm_ctx_fold_key_dev(lurk_hip_msm_ctx* key, size_t n, const void* w
     return guarded([&] {
         LURK_REQUIRE(key && weights32_mont && d_out_affine64, "null argument");
         const MsmTableView v = msm_ctx_table_view(key);
+        require_pasta_curve(v.curve, "lurk_hip_msm_ctx_fold_key_dev");
         DeviceGuard dg(v.device);
         if (v.curve == LURK_CURVE_PALLAS) key_fold<PallasFp, PallasFq>(v, n, weights32_mont, n_weights, d_out_affine64, (hipStream_t)stream);
         else key_fold<PallasFq, PallasFp>(v, n, weights32_mont, n_weights, d_out_affine64, (hipStream_t)stream);
@@ -598,7 +600,7 @@ int lurk_hip_msm_ctx_fold_key_dev(lurk_hip_msm_ctx* key, size_t n, const void* w
 int lurk_hip_points_fold_halves_dev(int curve, const void* d_points_affine64, size_t len, const void* s_lo32_mont, const void* s_hi32_mont,
                                     void* d_out_affine64, void* stream) {
     return guarded([&] {
-        LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
+        require_pasta_curve(curve, "lurk_hip_points_fold_halves_dev");
         LURK_REQUIRE(len >= 2 && len % 2 == 0, "length must be even and >= 2");
         LURK_REQUIRE(d_points_affine64 && d_out_affine64 && s_lo32_mont && s_hi32_mont, "null argument");
         if (curve == LURK_CURVE_PALLAS) points_fold_halves<PallasFp, PallasFq>(d_points_affine64, len, s_lo32_mont, s_hi32_mont, d_out_affine64, (hipStream_t)stream);

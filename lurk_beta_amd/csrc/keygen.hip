@@ -463,7 +463,7 @@ int lurk_hip_ck_params_set(const lurk_hip_ck_params* params) {
 int lurk_hip_ck_from_label_host(int curve, const void* label, size_t label_len, size_t npoints, void* out_affine64) {
     // pure host computation: no device is needed
     try {
-        LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
+        require_pasta_curve(curve, "lurk_hip_ck_from_label_host (hash-to-curve)");
         LURK_REQUIRE((label || label_len == 0) && (npoints == 0 || out_affine64), "null argument");
         LURK_REQUIRE(npoints <= ((size_t)1 << 16), "the host form maps at most 2^16 points: build keys with lurk_hip_ck_from_label_dev / lurk_hip_msm_ctx_from_label");
         if (curve == LURK_CURVE_PALLAS) keygen_from_label_host<PallasFp>(curve, label, label_len, npoints, out_affine64);
@@ -478,7 +478,7 @@ int lurk_hip_ck_from_label_host(int curve, const void* label, size_t label_len, 
 
 int lurk_hip_ck_hash_to_curve_dev(int curve, const char* domain_prefix, const void* d_uniform32, size_t n, void* d_out_affine64, void* stream) {
     return guarded([&] {
-        LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
+        require_pasta_curve(curve, "lurk_hip_ck_hash_to_curve_dev");
         LURK_REQUIRE(domain_prefix && (n == 0 || (d_uniform32 && d_out_affine64)), "null argument");
         if (curve == LURK_CURVE_PALLAS) keygen_device<PallasFp>(curve, domain_prefix, d_uniform32, n, d_out_affine64, (hipStream_t)stream);
         else keygen_device<PallasFq>(curve, domain_prefix, d_uniform32, n, d_out_affine64, (hipStream_t)stream);
@@ -487,7 +487,7 @@ int lurk_hip_ck_hash_to_curve_dev(int curve, const char* domain_prefix, const vo
 
 int lurk_hip_ck_from_label_dev(int curve, const void* label, size_t label_len, size_t npoints, void* d_out_affine64, void* stream) {
     return guarded([&] {
-        LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
+        require_pasta_curve(curve, "lurk_hip_ck_from_label_dev (hash-to-curve)");
         LURK_REQUIRE((label || label_len == 0) && (npoints == 0 || d_out_affine64), "null argument");
         keygen_from_label_device(curve, label, label_len, npoints, d_out_affine64, (hipStream_t)stream);
     });

@@ -1,4 +1,4 @@
-// msm.hip - Pedersen multi-scalar multiplication over the Pasta curves for gfx950.
+// msm.hip - Pedersen multi-scalar multiplication over the Pasta curves and the BN254 / Grumpkin cycle for gfx950.
 //
 // Replaces pasta-msm's mult_pippenger_{pallas,vesta} as reached from arecibo's
 // CommitmentEngine::commit (callers: /root/reference/src/proof/nova.rs:287-293,
@@ -979,9 +979,21 @@ struct MsmCtx : MsmCtxBase {
     }
 };
 
+// curve id -> f(base field pack, scalar field pack).  Every entry point that takes a curve id goes through this (or refuses the
+// id by name): nothing falls through to a default curve.  The kernels of the BN254 cycle are instantiated in msm_*_bn254.hip.
+template <class F>
+static void with_curve(int curve, F&& f) {
+    switch (curve) {
+        case LURK_CURVE_PALLAS: f(PallasFp{}, PallasFq{}); return;
+        case LURK_CURVE_VESTA: f(PallasFq{}, PallasFp{}); return;
+        case LURK_CURVE_BN254: f(Bn254Fq{}, Bn254Fr{}); return;
+        case LURK_CURVE_GRUMPKIN: f(Bn254Fr{}, Bn254Fq{}); return;
+    }
+    LURK_REQUIRE(false, "unknown curve id");
+}
 static MsmCtxBase* new_ctx(int curve) {
-    LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
-    MsmCtxBase* c = curve == LURK_CURVE_PALLAS ? (MsmCtxBase*)new MsmCtx<PallasFp, PallasFq>() : (MsmCtxBase*)new MsmCtx<PallasFq, PallasFp>();
+    MsmCtxBase* c = nullptr;
+    with_curve(curve, [&](auto P, auto SF) { c = new MsmCtx<decltype(P), decltype(SF)>(); });
     c->curve = curve;
     c->device = current_device();
     return c;
@@ -991,8 +1003,9 @@ static void ctx_set_bases(MsmCtxBase* c, const void* d_bases, size_t n, bool cop
     int c_override = (flags >> 8) & 0xff;
     LURK_REQUIRE(!((flags & LURK_MSM_FLAG_SMALL_FORM) && (flags & LURK_MSM_FLAG_NO_SMALL_FORM)), "LURK_MSM_FLAG_SMALL_FORM and LURK_MSM_FLAG_NO_SMALL_FORM exclude each other");
     const int small_pref = (flags & LURK_MSM_FLAG_SMALL_FORM) ? 1 : (flags & LURK_MSM_FLAG_NO_SMALL_FORM) ? -1 : 0;
-    if (c->curve == LURK_CURVE_PALLAS) static_cast<MsmCtx<PallasFp, PallasFq>*>(c)->set_bases_device(d_bases, n, copy, pre, c_override, s, small_pref);
-    else static_cast<MsmCtx<PallasFq, PallasFp>*>(c)->set_bases_device(d_bases, n, copy, pre, c_override, s, small_pref);
+    with_curve(c->curve, [&](auto P, auto SF) {
+        static_cast<MsmCtx<decltype(P), decltype(SF)>*>(c)->set_bases_device(d_bases, n, copy, pre, c_override, s, small_pref);
+    });
 }
 
 template <class P>
@@ -1080,7 +1093,7 @@ struct lurk_hip_msm_multi {
         std::unique_ptr<DeviceWorker> worker;
         std::unique_ptr<MsmCtxBase> ctx;  // created, used and destroyed on the worker thread
         DevBuf staged;                    // device copy of this shard's scalars (host-pointer commits)
-        Jacobian<PallasFp> partial;       // both curves share the 96-byte layout
+        Jacobian<PallasFp> partial;       // every curve shares the 96-byte layout
     };
     int curve = 0;
     size_t npoints = 0;
@@ -1115,8 +1128,7 @@ struct lurk_hip_msm_multi {
         std::vector<Jacobian<PallasFp>> parts;
         for (auto& sp : shards)
             if (sp->lo < n && sp->lo != sp->hi) parts.push_back(sp->partial);
-        if (curve == LURK_CURVE_PALLAS) point_sum_host<PallasFp>(parts.data(), parts.size(), out);
-        else point_sum_host<PallasFq>(parts.data(), parts.size(), out);
+        with_curve(curve, [&](auto P, auto) { point_sum_host<decltype(P)>(parts.data(), parts.size(), out); });
     }
     ~lurk_hip_msm_multi() {
         for (auto& sp : shards) {
@@ -1139,12 +1151,19 @@ int lurk_hip_msm_pallas(void* out, const void* bases, size_t n, const void* scal
 int lurk_hip_msm_vesta(void* out, const void* bases, size_t n, const void* scalars, int is_mont) {
     return msm_oneshot(LURK_CURVE_VESTA, out, bases, n, scalars, is_mont);
 }
+int lurk_hip_msm_bn254(void* out, const void* bases, size_t n, const void* scalars, int is_mont) {
+    return msm_oneshot(LURK_CURVE_BN254, out, bases, n, scalars, is_mont);
+}
+int lurk_hip_msm_grumpkin(void* out, const void* bases, size_t n, const void* scalars, int is_mont) {
+    return msm_oneshot(LURK_CURVE_GRUMPKIN, out, bases, n, scalars, is_mont);
+}
 
 // pasta-msm's own C symbols: they return nothing (its CPU Pippenger cannot fail), so a failure here ends the process with the
 // library's message - never a silent wrong commitment, never a CPU fallback
 static void pasta_msm_symbol(int curve, void* out, const void* points, size_t npoints, const void* scalars, bool is_mont) {
     if (msm_oneshot(curve, out, points, npoints, scalars, is_mont ? 1 : 0) != 0) {
-        fprintf(stderr, "liblurk_hip: mult_pippenger_%s failed: %s\n", curve == LURK_CURVE_PALLAS ? "pallas" : "vesta", lurk_hip_last_error());
+        static const char* const names[] = {"pallas", "vesta", "bn254", "grumpkin"};
+        fprintf(stderr, "liblurk_hip: mult_pippenger_%s failed: %s\n", names[curve], lurk_hip_last_error());
         abort();
     }
 }
@@ -1169,6 +1188,19 @@ lurk_hip_rust_error cuda_pippenger_pallas(void* out, const void* points, size_t 
 }
 lurk_hip_rust_error cuda_pippenger_vesta(void* out, const void* points, size_t npoints, const void* scalars, bool is_mont) {
     return rust_error_from(msm_oneshot(LURK_CURVE_VESTA, out, points, npoints, scalars, is_mont ? 1 : 0));
+}
+// grumpkin-msm's names (the BN254 / Grumpkin cycle), the same behaviour
+void mult_pippenger_bn254(void* out, const void* points, size_t npoints, const void* scalars, bool is_mont) {
+    pasta_msm_symbol(LURK_CURVE_BN254, out, points, npoints, scalars, is_mont);
+}
+void mult_pippenger_grumpkin(void* out, const void* points, size_t npoints, const void* scalars, bool is_mont) {
+    pasta_msm_symbol(LURK_CURVE_GRUMPKIN, out, points, npoints, scalars, is_mont);
+}
+lurk_hip_rust_error cuda_pippenger_bn254(void* out, const void* points, size_t npoints, const void* scalars, bool is_mont) {
+    return rust_error_from(msm_oneshot(LURK_CURVE_BN254, out, points, npoints, scalars, is_mont ? 1 : 0));
+}
+lurk_hip_rust_error cuda_pippenger_grumpkin(void* out, const void* points, size_t npoints, const void* scalars, bool is_mont) {
+    return rust_error_from(msm_oneshot(LURK_CURVE_GRUMPKIN, out, points, npoints, scalars, is_mont ? 1 : 0));
 }
 
 int lurk_hip_msm_oneshot_key_cache(int enable) {
@@ -1299,8 +1331,19 @@ int lurk_hip_msm_ctx_save(const lurk_hip_msm_ctx* ctx, const char* path, int wit
     });
 }
 
+// expect_curve >= 0: the file must hold a key of that curve (checked on the header, before anything is mapped or uploaded)
+static void msm_ctx_load_impl(lurk_hip_msm_ctx** ctx, const char* path, int flags, int expect_curve);
 int lurk_hip_msm_ctx_load(lurk_hip_msm_ctx** ctx, const char* path, int flags) {
+    return guarded([&] { msm_ctx_load_impl(ctx, path, flags, -1); });
+}
+int lurk_hip_msm_ctx_load_curve(lurk_hip_msm_ctx** ctx, int curve, const char* path, int flags) {
     return guarded([&] {
+        LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
+        msm_ctx_load_impl(ctx, path, flags, curve);
+    });
+}
+static void msm_ctx_load_impl(lurk_hip_msm_ctx** ctx, const char* path, int flags, int expect_curve) {
+    {
         LURK_REQUIRE(ctx && path, "null argument");
         *ctx = nullptr;
         const int fd = open(path, O_RDONLY);
@@ -1308,12 +1351,16 @@ int lurk_hip_msm_ctx_load(lurk_hip_msm_ctx** ctx, const char* path, int flags) {
         struct stat st;
         KeyFileHeader h{};
         bool good = fstat(fd, &st) == 0 && (size_t)st.st_size >= sizeof(h) && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
-        good = good && memcmp(h.magic, "LURKHIPK", 8) == 0 && h.version == 1 && h.curve <= 1 && h.windows >= 1 && h.windows <= MSM_MAX_W &&
+        good = good && memcmp(h.magic, "LURKHIPK", 8) == 0 && h.version == 1 && h.curve <= (uint32_t)LURK_CURVE_GRUMPKIN && h.windows >= 1 && h.windows <= MSM_MAX_W &&
                (h.windows == 1 || (h.window_bits >= 16 && h.window_bits <= 20 && h.windows == (uint32_t)msm_num_windows((int)h.window_bits))) &&
                h.npoints < ((uint64_t)1 << 31) && (uint64_t)st.st_size == sizeof(h) + (uint64_t)h.windows * h.npoints * 64;
         if (!good) {
             close(fd);
             LURK_REQUIRE(false, std::string("not a lurk-hip key file (or truncated): ") + path);
+        }
+        if (expect_curve >= 0 && (int)h.curve != expect_curve) {
+            close(fd);
+            LURK_REQUIRE(false, std::string("key file ") + path + " holds a " + curve_name((int)h.curve) + " key, not a " + curve_name(expect_curve) + " one");
         }
         const size_t n = h.npoints, total = (size_t)h.windows * n * 64;
         void* map = total ? mmap(nullptr, sizeof(h) + total, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
@@ -1339,7 +1386,7 @@ int lurk_hip_msm_ctx_load(lurk_hip_msm_ctx** ctx, const char* path, int flags) {
         }
         if (map) munmap(map, sizeof(h) + total);
         *ctx = new lurk_hip_msm_ctx{std::move(c)};
-    });
+    }
 }
 int lurk_hip_msm_ctx_rebind_dev(lurk_hip_msm_ctx* ctx, const void* d_bases, size_t npoints) {
     return guarded([&] {
@@ -1359,6 +1406,7 @@ int lurk_hip_msm_ctx_from_label(lurk_hip_msm_ctx** ctx, int curve, const void* l
     return guarded([&] {
         LURK_REQUIRE(ctx && (label || label_len == 0), "null argument");
         *ctx = nullptr;
+        require_pasta_curve(curve, "lurk_hip_msm_ctx_from_label (hash-to-curve)");
         std::unique_ptr<MsmCtxBase> c(new_ctx(curve));
         DevBuf bases(npoints * 64);
         keygen_from_label_device(curve, label, label_len, npoints, bases.p, nullptr);
@@ -1411,6 +1459,7 @@ FoldedKeyLease::~FoldedKeyLease() {
 FoldedKeyLease msm_ctx_folded_child(lurk_hip_msm_ctx* parent, const void* d_points, size_t m, hipStream_t s) {
     LURK_REQUIRE(parent && d_points && m, "null argument");
     const int curve = parent->impl->curve;
+    require_pasta_curve(curve, "the inner-product argument's folded key");
     const int flags = LURK_MSM_FLAG_PRECOMPUTE | LURK_MSM_FLAG_WINDOW_BITS(16);
     FoldedChild* fc = nullptr;
     {
@@ -1456,6 +1505,10 @@ void msm_ctx_wait_pair_xyzz(lurk_hip_msm_ctx* ctx, int slot, void* out_lo_xyzz12
     DeviceGuard dg(ctx->impl->device);
     ctx->impl->wait_pair_xyzz(slot, out_lo_xyzz128, out_hi_xyzz128);
 }
+int msm_multi_curve(const lurk_hip_msm_multi* key) {
+    LURK_REQUIRE(key, "null key");
+    return key->curve;
+}
 MsmTableView msm_ctx_table_view(const lurk_hip_msm_ctx* ctx) {
     LURK_REQUIRE(ctx, "null ctx");
     const MsmCtxBase& c = *ctx->impl;
@@ -1478,7 +1531,7 @@ int lurk_hip_msm_multi_create(lurk_hip_msm_multi** out, int curve, const void* b
     return guarded([&] {
         LURK_REQUIRE(out, "null ctx pointer");
         *out = nullptr;
-        LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
+        LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
         LURK_REQUIRE(n == 0 || bases, "null bases");
         LURK_REQUIRE(devices && n_dev >= 1 && n_dev <= 64, "device list must hold 1..64 entries");
         const int have = lurk_hip_device_count();
@@ -1626,8 +1679,7 @@ int lurk_hip_msm_multi_wait(lurk_hip_msm_multi* m, int slot, void* out) {
             }
         }
         if (first) throw *first;
-        if (m->curve == LURK_CURVE_PALLAS) point_sum_host<PallasFp>(parts.data(), parts.size(), out);
-        else point_sum_host<PallasFq>(parts.data(), parts.size(), out);
+        with_curve(m->curve, [&](auto P, auto) { point_sum_host<decltype(P)>(parts.data(), parts.size(), out); });
     });
 }
 int lurk_hip_msm_multi_destroy(lurk_hip_msm_multi* m) {
@@ -1646,10 +1698,9 @@ int lurk_hip_point_sum_gathered(int curve, void* out, const void* gathered, size
 
 int lurk_hip_point_sum(int curve, void* out, const void* points, size_t count) {
     try {
-        LURK_REQUIRE(curve == 0 || curve == 1, "unknown curve id");
+        LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
         LURK_REQUIRE(out && (count == 0 || points), "null argument");
-        if (curve == 0) point_sum_host<PallasFp>(points, count, out);
-        else point_sum_host<PallasFq>(points, count, out);
+        with_curve(curve, [&](auto P, auto) { point_sum_host<decltype(P)>(points, count, out); });
         set_error(0, "");
         return 0;
     } catch (const HipFailure& e) {
@@ -1659,10 +1710,9 @@ int lurk_hip_point_sum(int curve, void* out, const void* points, size_t count) {
 }
 int lurk_hip_point_mul(int curve, void* out, const void* point, const void* scalar32, int is_mont) {
     try {
-        LURK_REQUIRE(curve == 0 || curve == 1, "unknown curve id");
+        LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
         LURK_REQUIRE(out && point && scalar32, "null argument");
-        if (curve == 0) point_mul_host<PallasFp, PallasFq>(point, scalar32, is_mont, out);
-        else point_mul_host<PallasFq, PallasFp>(point, scalar32, is_mont, out);
+        with_curve(curve, [&](auto P, auto SF) { point_mul_host<decltype(P), decltype(SF)>(point, scalar32, is_mont, out); });
         set_error(0, "");
         return 0;
     } catch (const HipFailure& e) {
@@ -1672,10 +1722,9 @@ int lurk_hip_point_mul(int curve, void* out, const void* point, const void* scal
 }
 int lurk_hip_point_to_affine_canonical(int curve, void* out_xy64, const void* point) {
     try {
-        LURK_REQUIRE(curve == 0 || curve == 1, "unknown curve id");
+        LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
         LURK_REQUIRE(out_xy64 && point, "null argument");
-        if (curve == 0) point_affine_canonical_host<PallasFp>(point, out_xy64);
-        else point_affine_canonical_host<PallasFq>(point, out_xy64);
+        with_curve(curve, [&](auto P, auto) { point_affine_canonical_host<decltype(P)>(point, out_xy64); });
         set_error(0, "");
         return 0;
     } catch (const HipFailure& e) {

@@ -36,7 +36,12 @@ void msm_launch_accumulate(const uint32_t* sorted, const Affine<P>* table, const
 #define LURK_ACC_INSTANTIATE(P)                                                                                                             \
     template void msm_launch_accumulate<P>(const uint32_t*, const Affine<P>*, const uint2*, const uint32_t*, const uint32_t*, int, Xyzz<P>*, \
                                            size_t, hipStream_t);
+#ifdef LURK_MSM_BN254_TU  // msm_acc_bn254.hip: the BN254 / Grumpkin base fields, a code object of their own
+LURK_ACC_INSTANTIATE(Bn254Fq)
+LURK_ACC_INSTANTIATE(Bn254Fr)
+#else
 LURK_ACC_INSTANTIATE(PallasFp)
 LURK_ACC_INSTANTIATE(PallasFq)
+#endif
 
 }  // namespace lurk

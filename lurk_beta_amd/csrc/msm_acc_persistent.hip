@@ -62,7 +62,12 @@ void msm_launch_accumulate_persistent(const uint32_t* sorted, const Affine<P>* t
 #define LURK_ACC_PERSISTENT_INSTANTIATE(P)                                                                                                    \
     template void msm_launch_accumulate_persistent<P>(const uint32_t*, const Affine<P>*, const uint2*, const uint32_t*, const uint32_t*, int, \
                                                       Xyzz<P>*, uint32_t*, hipStream_t, unsigned);
+#ifdef LURK_MSM_BN254_TU  // msm_acc_persistent_bn254.hip
+LURK_ACC_PERSISTENT_INSTANTIATE(Bn254Fq)
+LURK_ACC_PERSISTENT_INSTANTIATE(Bn254Fr)
+#else
 LURK_ACC_PERSISTENT_INSTANTIATE(PallasFp)
 LURK_ACC_PERSISTENT_INSTANTIATE(PallasFq)
+#endif
 
 }  // namespace lurk

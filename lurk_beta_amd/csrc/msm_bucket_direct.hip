@@ -102,11 +102,15 @@ __global__ __launch_bounds__(DIRECT_BLOCK) void msm_bucket_direct_big_kernel(con
 
 // lanes per bucket: the most (<= 4) that keeps NB x L within the 131 072 lanes two waves per SIMD hold and leaves a lane >= 4 entries
 // (one key space of 16-bit windows is 32 768 buckets: 4 lanes; a pair's two key spaces: 2)
+#ifdef LURK_MSM_BN254_TU
+int msm_bucket_direct_lanes(size_t NB, size_t entries);  // (defined once, in the Pasta translation unit)
+#else
 int msm_bucket_direct_lanes(size_t NB, size_t entries) {
     int L = 1;
     while (L < 4 && NB * (size_t)(2 * L) <= 131072 && entries / (NB * (size_t)(2 * L)) >= 4) L *= 2;
     return L;
 }
+#endif
 
 template <class P>
 void msm_launch_bucket_direct(const uint32_t* sorted, const Affine<P>* table, const uint32_t* bucket_start, const uint32_t* cnt, uint32_t NB, size_t entries,
@@ -122,7 +126,12 @@ void msm_launch_bucket_direct(const uint32_t* sorted, const Affine<P>* table, co
 #define LURK_DIRECT_INSTANTIATE(P)                                                                                                                      \
     template void msm_launch_bucket_direct<P>(const uint32_t*, const Affine<P>*, const uint32_t*, const uint32_t*, uint32_t, size_t, Xyzz<P>*, uint32_t*, \
                                               uint32_t*, hipStream_t);
+#ifdef LURK_MSM_BN254_TU  // msm_bucket_direct_bn254.hip
+LURK_DIRECT_INSTANTIATE(Bn254Fq)
+LURK_DIRECT_INSTANTIATE(Bn254Fr)
+#else
 LURK_DIRECT_INSTANTIATE(PallasFp)
 LURK_DIRECT_INSTANTIATE(PallasFq)
+#endif
 
 }  // namespace lurk

@@ -36,7 +36,9 @@ LURK_HD int msm_num_windows(int c) { return (256 + c - 1) / c; }
 
 // Signed-digit recoding of a canonical 255-bit scalar (8 x u32 LE) with c-bit windows, one window
 // per call (w ascending, carry threaded through): returns |d_w| | sign<<31 with |d_w| <= 2^(c-1).
-// Scalars are < 2^255 and W*c >= 256, so the top window never carries out.
+// Scalars are < 2^255 and W*c >= 256, so the top window never carries out: its raw digit is below 2^(c-1) (Pasta, 255 bits: the top
+// window of every width 16..20 holds at most c - 1 scalar bits; the BN254-cycle fields have 254 bits, one bit more to spare - e.g.
+// c = 20: 13 x 20 = 260 >= 254, the top window holds 14 bits) and a carry-in of 1 cannot lift it above 2^(c-1).
 LURK_HD uint32_t msm_digit_step(const uint32_t* s, int w, int c, uint32_t& carry) {
     const uint32_t half = 1u << (c - 1), mask = (1u << c) - 1u;
     const int bit = w * c, limb = bit >> 5, sh = bit & 31;

@@ -13,8 +13,12 @@ namespace lurk {
 
 constexpr int MSM_FIN_SMALL = 16;  // = MSM_SMALL of msm.hip (buckets with more partials are summed by a workgroup)
 
+#ifndef LURK_FINALIZE_WAVES  // waves per SIMD the compiler is to leave room for (4 -> 128 VGPRs, 2 -> 256): msm_finalize_bn254.hip sets 2
+#define LURK_FINALIZE_WAVES 4
+#endif
+#define LURK_FINALIZE_BOUNDS __launch_bounds__(256, LURK_FINALIZE_WAVES)
 template <class P>
-__global__ __launch_bounds__(256, 4) void msm_finalize_kernel(const Xyzz<P>* __restrict__ partials, const uint32_t* __restrict__ cnt,
+__global__ LURK_FINALIZE_BOUNDS void msm_finalize_kernel(const Xyzz<P>* __restrict__ partials, const uint32_t* __restrict__ cnt,
                                                              const uint32_t* __restrict__ task_start,
                                                              const uint32_t* __restrict__ group_task_base, uint32_t NB,
                                                              Xyzz<P>* __restrict__ buckets, uint32_t* __restrict__ big_list,
@@ -38,9 +42,15 @@ void msm_launch_finalize(const Xyzz<P>* partials, const uint32_t* cnt, const uin
     hipLaunchKernelGGL((msm_finalize_kernel<P>), dim3(div_up((size_t)NB, 256)), dim3(256), 0, s, partials, cnt, task_start, group_task_base, NB, buckets,
                        big_list, big_count, S);
 }
-template void msm_launch_finalize<PallasFp>(const Xyzz<PallasFp>*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, Xyzz<PallasFp>*, uint32_t*,
-                                            uint32_t*, uint32_t, hipStream_t);
-template void msm_launch_finalize<PallasFq>(const Xyzz<PallasFq>*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, Xyzz<PallasFq>*, uint32_t*,
-                                            uint32_t*, uint32_t, hipStream_t);
+#define LURK_FINALIZE_INSTANTIATE(P)                                                                                                          \
+    template void msm_launch_finalize<P>(const Xyzz<P>*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, Xyzz<P>*, uint32_t*, uint32_t*, \
+                                         uint32_t, hipStream_t);
+#ifdef LURK_MSM_BN254_TU  // msm_finalize_bn254.hip
+LURK_FINALIZE_INSTANTIATE(Bn254Fq)
+LURK_FINALIZE_INSTANTIATE(Bn254Fr)
+#else
+LURK_FINALIZE_INSTANTIATE(PallasFp)
+LURK_FINALIZE_INSTANTIATE(PallasFq)
+#endif
 
 }  // namespace lurk

@@ -5,7 +5,9 @@
 
 namespace lurk {
 
+#ifndef LURK_MSM_BN254_TU  // (defined once)
 size_t msm_precompute_scratch_bytes(size_t n, int W) { return W > 1 ? (size_t)(W - 1) * MSM_PRE_SLOTS * n * sizeof(F29<PallasFp>) : 0; }
+#endif
 
 template <class P>
 __global__ __launch_bounds__(256) void msm_precompute_kernel(const Affine<P>* __restrict__ bases, size_t n, Affine<P>* __restrict__ table, int c,
@@ -22,7 +24,12 @@ void msm_launch_precompute(const Affine<P>* bases, size_t n, Affine<P>* table, i
     hipLaunchKernelGGL((msm_precompute_kernel<P>), dim3(div_up(n, 256)), dim3(256), 0, s, bases, n, table, c, W, (F29<P>*)scratch);
     LURK_HIP_CHECK(hipGetLastError());
 }
+#ifdef LURK_MSM_BN254_TU  // msm_precompute_bn254.hip
+template void msm_launch_precompute<Bn254Fq>(const Affine<Bn254Fq>*, size_t, Affine<Bn254Fq>*, int, int, void*, hipStream_t);
+template void msm_launch_precompute<Bn254Fr>(const Affine<Bn254Fr>*, size_t, Affine<Bn254Fr>*, int, int, void*, hipStream_t);
+#else
 template void msm_launch_precompute<PallasFp>(const Affine<PallasFp>*, size_t, Affine<PallasFp>*, int, int, void*, hipStream_t);
 template void msm_launch_precompute<PallasFq>(const Affine<PallasFq>*, size_t, Affine<PallasFq>*, int, int, void*, hipStream_t);
+#endif
 
 }  // namespace lurk

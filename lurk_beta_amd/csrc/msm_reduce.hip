@@ -258,7 +258,11 @@ __global__ LURK_REDUCE_BOUNDS void msm_planes29_wave_kernel(const Plane29<P>* __
     }
 }
 
+#ifdef LURK_MSM_BN254_TU
+size_t msm_reduce_plane_bytes(size_t nb);  // (defined once, in the Pasta translation unit)
+#else
 size_t msm_reduce_plane_bytes(size_t nb) { return nb * 160; }
+#endif
 
 // LURK_MSM_REDUCE_WAVE=0: every level as its own launch (the round-3 form)
 static bool reduce_wave_levels() {
@@ -329,7 +333,12 @@ void msm_launch_reduce(const Xyzz<P>* buckets, void* planes_a, void* planes_b, i
     }
     LURK_HIP_CHECK(hipGetLastError());
 }
+#ifdef LURK_MSM_BN254_TU  // msm_reduce_bn254.hip
+template void msm_launch_reduce<Bn254Fq>(const Xyzz<Bn254Fq>*, void*, void*, int, int, uint32_t, Xyzz<Bn254Fq>*, hipStream_t);
+template void msm_launch_reduce<Bn254Fr>(const Xyzz<Bn254Fr>*, void*, void*, int, int, uint32_t, Xyzz<Bn254Fr>*, hipStream_t);
+#else
 template void msm_launch_reduce<PallasFp>(const Xyzz<PallasFp>*, void*, void*, int, int, uint32_t, Xyzz<PallasFp>*, hipStream_t);
 template void msm_launch_reduce<PallasFq>(const Xyzz<PallasFq>*, void*, void*, int, int, uint32_t, Xyzz<PallasFq>*, hipStream_t);
+#endif
 
 }  // namespace lurk

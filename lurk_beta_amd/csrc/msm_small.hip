@@ -192,6 +192,10 @@ __global__ __launch_bounds__(SMALL_BLOCK) void msm_small_kernel(const uint4* __r
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
+#ifdef LURK_MSM_BN254_TU  // (the sizing functions are defined once, in the Pasta translation unit)
+unsigned msm_small_groups(size_t n, int c);
+size_t msm_small_scratch_bytes();
+#else
 int msm_small_window_bits(size_t n) { return n <= ((size_t)1 << 14) ? 8 : 6; }
 size_t msm_small_table_entries(size_t n, int c) { return (n * (size_t)msm_num_windows(c)) << (c - 1); }
 unsigned msm_small_groups(size_t n, int c) {
@@ -203,6 +207,7 @@ unsigned msm_small_groups(size_t n, int c) {
 }
 size_t msm_small_scratch_bytes() { return (size_t)1 << 30; }
 unsigned msm_small_out_points(unsigned groups) { return (groups + (1u << SMALL_FINAL_LEVELS) - 1) >> SMALL_FINAL_LEVELS; }
+#endif
 
 // wbases: the per-window bases [w * n + i] = 2^(c w) P_i (msm_precompute_kernel's output); table: n * W * 2^(c-1) records
 template <class P>
@@ -227,7 +232,9 @@ void msm_small_build_table(const Affine<P>* wbases, size_t n, int c, Affine<P>* 
 }
 
 // counter must be zero before the first launch (the kernel leaves it zero); out: pinned host memory, msm_small_out_points() records
+#ifndef LURK_MSM_BN254_TU
 size_t msm_small_group_bytes() { return (size_t)SMALL_MAX_GROUPS * 160; }
+#endif
 template <class P, class SF>
 void msm_small_launch(const void* d_scalars, size_t n, int is_mont, const Affine<P>* table, int c, void* group_pts, uint32_t* counter, Xyzz<P>* out,
                       hipStream_t s) {
@@ -246,7 +253,12 @@ void msm_small_launch(const void* d_scalars, size_t n, int is_mont, const Affine
 #define LURK_SMALL_INSTANTIATE(P, SF)                                                                                      \
     template void msm_small_build_table<P>(const Affine<P>*, size_t, int, Affine<P>*, hipStream_t);                         \
     template void msm_small_launch<P, SF>(const void*, size_t, int, const Affine<P>*, int, void*, uint32_t*, Xyzz<P>*, hipStream_t);
+#ifdef LURK_MSM_BN254_TU  // msm_small_bn254.hip
+LURK_SMALL_INSTANTIATE(Bn254Fq, Bn254Fr)
+LURK_SMALL_INSTANTIATE(Bn254Fr, Bn254Fq)
+#else
 LURK_SMALL_INSTANTIATE(PallasFp, PallasFq)
 LURK_SMALL_INSTANTIATE(PallasFq, PallasFp)
+#endif
 
 }  // namespace lurk

@@ -428,4 +428,9 @@ void msm_launch_sort(const MsmShape& sh, const void* d_scalars, int is_mont, con
 template void msm_launch_sort<PallasFp>(const MsmShape&, const void*, int, const MsmSortBufs&, hipStream_t);
 template void msm_launch_sort<PallasFq>(const MsmShape&, const void*, int, const MsmSortBufs&, hipStream_t);
 
+// canonical scalars: the MONT = false kernels never touch the field pack (it only types the register copy of the scalar)
+void msm_launch_sort_canonical(const MsmShape& sh, const void* d_scalars, const MsmSortBufs& b, hipStream_t s) {
+    msm_launch_sort<PallasFp>(sh, d_scalars, 0, b, s);
+}
+
 }  // namespace lurk

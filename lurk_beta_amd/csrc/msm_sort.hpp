@@ -70,5 +70,9 @@ struct MsmSortBufs {
 // enqueues the whole sort on s: sorted (table index | sign, grouped by key), cnt and bucket_start per key
 template <class SF>
 void msm_launch_sort(const MsmShape& sh, const void* d_scalars, int is_mont, const MsmSortBufs& b, hipStream_t s);
+// the same for scalars that are already canonical (8 x u32, < 2^255), whatever their field: nothing after the Montgomery -> canonical
+// step of pass 1a depends on the modulus.  What the BN254 / Grumpkin scalar fields go through (msm_sort_bn254.hip) - no sort kernel
+// is instantiated a second time for them.
+void msm_launch_sort_canonical(const MsmShape& sh, const void* d_scalars, const MsmSortBufs& b, hipStream_t s);
 
 }  // namespace lurk

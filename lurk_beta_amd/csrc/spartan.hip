@@ -380,6 +380,7 @@ int lurk_hip_spartan_prove_dev(const lurk_hip_r1cs* shape, const lurk_hip_r1cs* 
         size_t points = 0;
         if (lurk_hip_msm_ctx_info(key, &curve, &points, &bits, nullptr) != 0 || lurk_hip_msm_ctx_device(key, &device) != 0)
             throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
+        require_pasta_curve(curve, "lurk_hip_spartan_prove_dev");
         LURK_REQUIRE(points >= (num_cons > num_vars ? num_cons : num_vars), "the key has fewer points than the padded polynomials have elements");
         // every scratch vector below is sized from (num_cons, num_vars, num_io) while the mat-vecs write what the shapes say: the two must agree
         // (the transposed shape is 2 num_vars rows over the num_cons columns, stored as num_vars = num_cons - 1, num_io = 0), and the shapes'
@@ -416,6 +417,7 @@ int lurk_hip_spartan_prove_batch_dev(const lurk_hip_spartan_instance* instances,
         size_t points = 0;
         if (lurk_hip_msm_ctx_info(key, &curve, &points, &bits, nullptr) != 0 || lurk_hip_msm_ctx_device(key, &device) != 0)
             throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
+        require_pasta_curve(curve, "lurk_hip_spartan_prove_batch_dev");
         const int want_field = curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : LURK_FIELD_PALLAS_FP;
         for (size_t i = 0; i < n_instances; i++) {
             const lurk_hip_spartan_instance& it = instances[i];

@@ -166,6 +166,21 @@ struct lurk_hip_fold_ctx {
 
 namespace lurk {
 
+// f(pack) for the scalar field of the context's curve (Pallas: Fq, Vesta: Fp, BN254: Fr)
+template <class Fn>
+static void with_scalar_field(int field_id, Fn&& f) {
+    if (field_id == LURK_FIELD_PALLAS_FQ) f(PallasFq{});
+    else if (field_id == LURK_FIELD_PALLAS_FP) f(PallasFp{});
+    else if (field_id == LURK_FIELD_BN254_FR) f(Bn254Fr{});
+    else LURK_REQUIRE(false, "the folding context's field is none of the three scalar fields it is offered over");
+}
+// the calls that need the random oracle over the curve's base field: Poseidon constants over the BN254 base field do not exist yet
+static void require_transcript(const lurk_hip_fold_ctx* c, const char* what) {
+    if (c->curve == LURK_CURVE_BN254)
+        throw HipFailure{LURK_HIP_ERR_INVALID_ARG, std::string(what) + " is not offered on BN254 (no random oracle over its base field yet): derive r on the host and call "
+                                                                       "lurk_hip_fold_step_finish"};
+}
+
 // [u | X] <- [u1 + r | X1 + r X2] on the host (1 + num_io elements; u2 = 1)
 template <class F>
 static void fold_ux_host(std::vector<uint64_t>& ux, const std::vector<uint64_t>& x2, const void* r_mont) {
@@ -195,8 +210,7 @@ static void fold_instance_settle(lurk_hip_fold_ctx* c) {
     ok(lurk_hip_point_mul(c->curve, pair + 12, c->open_ct, c->owed_r, 1));
     ok(lurk_hip_point_sum(c->curve, new_e, pair, 2));
     std::vector<uint64_t> new_ux = c->ux;
-    if (c->field_id == LURK_FIELD_PALLAS_FQ) fold_ux_host<PallasFq>(new_ux, c->open_x2, c->owed_r);
-    else fold_ux_host<PallasFp>(new_ux, c->open_x2, c->owed_r);
+    with_scalar_field(c->field_id, [&](auto F) { fold_ux_host<decltype(F)>(new_ux, c->open_x2, c->owed_r); });
     memcpy(c->comm_w, new_w, 96);
     memcpy(c->comm_e, new_e, 96);
     c->ux.swap(new_ux);
@@ -434,8 +448,7 @@ static void fold_begin(lurk_hip_fold_ctx* c, const lurk_hip_w2_patch* patches, s
         LURK_HIP_CHECK(hipHostMalloc((void**)&c->pin, need + need / 2, hipHostMallocDefault));
         c->pin_cap = need + need / 2;
     }
-    if (c->field_id == LURK_FIELD_PALLAS_FQ) mont_one<PallasFq>(c->pin);
-    else mont_one<PallasFp>(c->pin);
+    with_scalar_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
     if (c->num_io) memcpy(c->pin + 32, x2_mont, c->num_io * 32);
     LURK_HIP_CHECK(hipMemcpyAsync(z2 + c->num_vars * 32, c->pin, (1 + c->num_io) * 32, hipMemcpyHostToDevice, c->stage_stream[b]));
     const bool late_own_key = patched && fold_late_key(c, patches, n_patches, patched, c->stage_stream[b]);
@@ -599,8 +612,7 @@ static void fold_begin_multi(lurk_hip_fold_ctx* c, const void* w2, int on_device
         LURK_HIP_CHECK(hipHostMalloc((void**)&c->pin, need * 2, hipHostMallocDefault));
         c->pin_cap = need * 2;
     }
-    if (c->field_id == LURK_FIELD_PALLAS_FQ) mont_one<PallasFq>(c->pin);
-    else mont_one<PallasFp>(c->pin);
+    with_scalar_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
     if (c->num_io) memcpy(c->pin + 32, x2_mont, c->num_io * 32);
     LURK_HIP_CHECK(hipMemcpyAsync(z2 + c->num_vars * 32, c->pin, need, hipMemcpyHostToDevice, c->stage_stream[0]));
     LURK_HIP_CHECK(hipEventRecord(c->staged_ev[b], c->stage_stream[0]));
@@ -656,8 +668,7 @@ static void fold_finish(lurk_hip_fold_ctx* c, const void* r32_mont) {
         c->abc_buf = c->tcur;
         c->abc_pending = true;
         c->tcur ^= 1;
-        if (c->field_id == LURK_FIELD_PALLAS_FQ) host_add_mont<PallasFq>(c->u_host, r32_mont);  // u <- u + r u2, u2 = 1 (a fresh instance is strict)
-        else host_add_mont<PallasFp>(c->u_host, r32_mont);
+        with_scalar_field(c->field_id, [&](auto F) { host_add_mont<decltype(F)>(c->u_host, r32_mont); });  // u <- u + r u2, u2 = 1 (a fresh instance is strict)
     } else {
         ok(lurk_hip_fold_vecs_dev(c->field_id, 2, a, b, n, o, r32_mont, c->stream));
         LURK_HIP_CHECK(hipEventRecord(c->folded_ev[c->open_buf], c->stream));
@@ -679,12 +690,18 @@ extern "C" {
 static void fold_ctx_create(lurk_hip_fold_ctx** out, int curve, lurk_hip_r1cs* shape, lurk_hip_msm_ctx* key, lurk_hip_msm_multi* mkey) {
     LURK_REQUIRE(out && shape && (key || mkey), "null argument");
     *out = nullptr;
-    LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
+    // Grumpkin's scalar field is the BN254 base field: fold.hip has no kernels over it
+    LURK_REQUIRE(curve != LURK_CURVE_GRUMPKIN, "a folding context is not offered on Grumpkin (the folding kernels do not cover its scalar field, the BN254 base field)");
+    LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA || curve == LURK_CURVE_BN254, "unknown curve id");
     auto c = std::make_unique<lurk_hip_fold_ctx>();
     c->curve = curve;
     int shape_field = 0;
     ok(lurk_hip_r1cs_dims(shape, &shape_field, &c->num_cons, &c->num_vars, &c->num_io));
-    c->field_id = curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : LURK_FIELD_PALLAS_FP;  // the curve's scalar field
+    c->field_id = curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : curve == LURK_CURVE_VESTA ? LURK_FIELD_PALLAS_FP : LURK_FIELD_BN254_FR;  // the curve's scalar field
+    {   // four curves share the 64-byte point layout: a key over another curve would commit to garbage without a word
+        const int key_curve = key ? msm_ctx_table_view(key).curve : msm_multi_curve(mkey);
+        LURK_REQUIRE(key_curve == curve, std::string("the commitment key is over ") + curve_name(key_curve) + ", not " + curve_name(curve));
+    }
     LURK_REQUIRE(shape_field == c->field_id, "the shape is not over this curve's scalar field");
     c->shape = shape;
     c->key = key;
@@ -734,7 +751,7 @@ static void fold_ctx_create(lurk_hip_fold_ctx** out, int curve, lurk_hip_r1cs* s
         }
     }
     c->ux.assign(4 * (1 + c->num_io), 0);
-    {   // the transcript's width-25 Poseidon constants are generated on first use (~0.15 s): now, not inside the first step
+    if (curve != LURK_CURVE_BN254) {  // the transcript's width-25 Poseidon constants are generated on first use (~0.15 s): now, not inside the first step
         uint64_t one[4] = {1, 0, 0, 0}, out[4];
         ok(lurk_hip_nova_ro_squeeze(c->field_id == LURK_FIELD_PALLAS_FQ ? LURK_FIELD_PALLAS_FP : LURK_FIELD_PALLAS_FQ, one, 1, 128, out));
     }
@@ -860,6 +877,7 @@ int lurk_hip_fold_step(lurk_hip_fold_ctx* c, const void* w2, int w2_on_device, v
                        void* comm_w2_jac96, void* comm_t_jac96, void* r32_mont) {
     return guarded([&] {
         LURK_REQUIRE(c && pp_digest32, "null argument");
+        require_transcript(c, "lurk_hip_fold_step");
         LURK_REQUIRE(c->num_vars == 0 || w2, "null witness");
         LURK_REQUIRE(c->num_io == 0 || x2_mont, "null public IO");
         DeviceGuard dg(c->device);
@@ -950,6 +968,7 @@ int lurk_hip_fold_ctx_set_submit_hook(lurk_hip_fold_ctx* c, lurk_hip_fold_submit
 int lurk_hip_fold_ctx_set_pp_digest(lurk_hip_fold_ctx* c, const void* pp_digest32) {
     return guarded([&] {
         LURK_REQUIRE(c && pp_digest32, "null argument");
+        require_transcript(c, "lurk_hip_fold_ctx_set_pp_digest");
         std::lock_guard<std::recursive_mutex> lk(c->mu);
         memcpy(c->pp_digest, pp_digest32, 32);
         c->has_pp = true;
@@ -960,6 +979,7 @@ int lurk_hip_fold_ctx_set_pp_digest(lurk_hip_fold_ctx* c, const void* pp_digest3
 int lurk_hip_fold_step_challenge(lurk_hip_fold_ctx* c, void* r32_mont) {
     return guarded([&] {
         LURK_REQUIRE(c && r32_mont, "null argument");
+        require_transcript(c, "lurk_hip_fold_step_challenge");
         std::lock_guard<std::recursive_mutex> lk(c->mu);
         step_mark("challenge");
         fold_challenge_finish(c, r32_mont);

@@ -55,14 +55,33 @@ __global__ __launch_bounds__(256) void synth_scalars_kernel(uint64_t stream, int
 }
 
 // ---- fixed-base table: tab[j*256 + d] = d * 256^j * G (affine), j < 32, d < 256 ---------------
+// the generator the synthetic bases are multiples of: (-1, 2) on Pallas and Vesta (y^2 = x^3 + 5), (1, 2) on BN254 G1 (y^2 = x^3 + 3),
+// (1, sqrt(-16)) on Grumpkin (y^2 = x^3 - 17, the root halo2curves lists)
+template <class P>
+__device__ Affine<P> synth_generator() {
+    Affine<P> g;
+    if (P::ID == Bn254Fq::ID) {
+        g.x = fe_one<P>();
+        g.y = fe_dbl<P>(fe_one<P>());
+    } else if (P::ID == Bn254Fr::ID) {
+        // 0x0000000000000002cf135e7506a45d632d270d45f1181294833fc48d823f272c, canonical
+        Fe<P> y;
+        const uint32_t w[8] = {0x823f272cu, 0x833fc48du, 0xf1181294u, 0x2d270d45u, 0x06a45d63u, 0xcf135e75u, 0x00000002u, 0x00000000u};
+        for (int i = 0; i < 8; i++) y.l[i] = w[i];
+        g.x = fe_one<P>();
+        g.y = fe_to_mont<P>(y);
+    } else {
+        g.x = fe_neg<P>(fe_one<P>());
+        g.y = fe_dbl<P>(fe_one<P>());
+    }
+    return g;
+}
 template <class P>
 __global__ void synth_table_kernel(Affine<P>* tab) {
     int id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= 32 * 256) return;
     int j = id >> 8, d = id & 255;
-    Affine<P> g;
-    g.x = fe_neg<P>(fe_one<P>());  // generator (-1, 2)
-    g.y = fe_dbl<P>(fe_one<P>());
+    const Affine<P> g = synth_generator<P>();
     Xyzz<P> b = xyzz_from_affine<P>(g);
     for (int q = 0; q < 8 * j; q++) b = xyzz_dbl<P>(b);
     tab[id] = xyzz_to_affine<P>(xyzz_mul_small<P>(b, (uint32_t)d));
@@ -109,7 +128,7 @@ extern "C" {
 
 int lurk_hip_synth_scalars_dev(int field_id, uint64_t stream_id, int dist, size_t first, size_t n, void* d_out, int out_mont, void* stream) {
     return guarded([&] {
-        LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
+        LURK_REQUIRE(field_id >= 0 && field_id <= LURK_FIELD_BN254_FQ, "unknown field id");
         LURK_REQUIRE(dist == 0 || dist == 1, "dist must be 0 (uniform) or 1 (witness-like)");
         if (n == 0) return;
         LURK_REQUIRE(d_out, "null buffer");
@@ -117,24 +136,31 @@ int lurk_hip_synth_scalars_dev(int field_id, uint64_t stream_id, int dist, size_
         dim3 grid(div_up(n, 256)), block(256);
         if (field_id == 0) hipLaunchKernelGGL((synth_scalars_kernel<PallasFp>), grid, block, 0, s, stream_id, dist, first, n, (Fe<PallasFp>*)d_out, out_mont);
         else if (field_id == 1) hipLaunchKernelGGL((synth_scalars_kernel<PallasFq>), grid, block, 0, s, stream_id, dist, first, n, (Fe<PallasFq>*)d_out, out_mont);
-        else hipLaunchKernelGGL((synth_scalars_kernel<Bn254Fr>), grid, block, 0, s, stream_id, dist, first, n, (Fe<Bn254Fr>*)d_out, out_mont);
+        else if (field_id == 2) hipLaunchKernelGGL((synth_scalars_kernel<Bn254Fr>), grid, block, 0, s, stream_id, dist, first, n, (Fe<Bn254Fr>*)d_out, out_mont);
+        else hipLaunchKernelGGL((synth_scalars_kernel<Bn254Fq>), grid, block, 0, s, stream_id, dist, first, n, (Fe<Bn254Fq>*)d_out, out_mont);
         LURK_HIP_CHECK(hipGetLastError());
     });
 }
 
 int lurk_hip_synth_bases_dev(int curve, size_t first, size_t n, void* d_out, void* stream) {
     return guarded([&] {
-        LURK_REQUIRE(curve == 0 || curve == 1, "unknown curve id");
+        LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
         if (n == 0) return;
         LURK_REQUIRE(d_out, "null buffer");
         hipStream_t s = (hipStream_t)stream;
         dim3 grid(div_up(n, 256)), block(256);
-        if (curve == 0) {
+        if (curve == LURK_CURVE_PALLAS) {
             const Affine<PallasFp>* tab = get_table<PallasFp>(0, s);
             hipLaunchKernelGGL((synth_bases_kernel<PallasFp, PallasFq>), grid, block, 0, s, tab, first, n, (Affine<PallasFp>*)d_out);
-        } else {
+        } else if (curve == LURK_CURVE_VESTA) {
             const Affine<PallasFq>* tab = get_table<PallasFq>(1, s);
             hipLaunchKernelGGL((synth_bases_kernel<PallasFq, PallasFp>), grid, block, 0, s, tab, first, n, (Affine<PallasFq>*)d_out);
+        } else if (curve == LURK_CURVE_BN254) {
+            const Affine<Bn254Fq>* tab = get_table<Bn254Fq>(LURK_CURVE_BN254, s);
+            hipLaunchKernelGGL((synth_bases_kernel<Bn254Fq, Bn254Fr>), grid, block, 0, s, tab, first, n, (Affine<Bn254Fq>*)d_out);
+        } else {
+            const Affine<Bn254Fr>* tab = get_table<Bn254Fr>(LURK_CURVE_GRUMPKIN, s);
+            hipLaunchKernelGGL((synth_bases_kernel<Bn254Fr, Bn254Fq>), grid, block, 0, s, tab, first, n, (Affine<Bn254Fr>*)d_out);
         }
         LURK_HIP_CHECK(hipGetLastError());
     });

@@ -338,7 +338,7 @@ struct NifsPre {
     NifsStages<PallasFp, PallasFq> vesta;
 };
 NifsPre* nifs_pre_begin(int curve, const void* pp_digest32, const void* comm_w1, const void* comm_e1, const void* u1_mont, const void* x1_mont, size_t num_io) {
-    LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
+    require_pasta_curve(curve, "the folding transcript (Nova's random oracle)");
     auto p = std::make_unique<NifsPre>();
     p->curve = curve;
     if (curve == LURK_CURVE_PALLAS) p->pallas.begin(curve, pp_digest32, comm_w1, comm_e1, u1_mont, x1_mont, num_io);
@@ -450,7 +450,7 @@ int lurk_hip_nifs_absorb_list(int curve, const void* pp_digest32, const void* co
                               const void* x1_mont, const void* comm_w2_jac96, const void* x2_mont, size_t num_io, const void* comm_t_jac96,
                               void* out_elems32, size_t cap, size_t* count) {
     return host_guarded([&] {
-        LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
+        require_pasta_curve(curve, "lurk_hip_nifs_absorb_elems (Nova's random oracle)");
         LURK_REQUIRE(pp_digest32 && comm_w1_jac96 && comm_e1_jac96 && u1_mont && comm_w2_jac96 && comm_t_jac96 && count, "null argument");
         LURK_REQUIRE(num_io == 0 || (x1_mont && x2_mont), "null public IO");
         std::vector<uint64_t> el;
@@ -480,7 +480,7 @@ int lurk_hip_nifs_challenge(int curve, const void* pp_digest32, const void* comm
                             const void* x1_mont, const void* comm_w2_jac96, const void* x2_mont, size_t num_io, const void* comm_t_jac96,
                             void* r32_mont) {
     return host_guarded([&] {
-        LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA, "unknown curve id");
+        require_pasta_curve(curve, "lurk_hip_nifs_challenge (Nova's random oracle)");
         LURK_REQUIRE(pp_digest32 && comm_w1_jac96 && comm_e1_jac96 && u1_mont && comm_w2_jac96 && comm_t_jac96 && r32_mont, "null argument");
         LURK_REQUIRE(num_io == 0 || (x1_mont && x2_mont), "null public IO");
         if (curve == LURK_CURVE_PALLAS)

@@ -701,6 +701,7 @@ static KeyInfo key_info(const lurk_hip_msm_ctx* key) {
     int bits = 0;
     if (lurk_hip_msm_ctx_info(key, &k.curve, &k.points, &bits, nullptr) != 0 || lurk_hip_msm_ctx_device(key, &k.device) != 0)
         throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
+    require_pasta_curve(k.curve, "the verifiers of the opening argument and of the compressing SNARK");
     k.field_id = k.curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : LURK_FIELD_PALLAS_FP;
     return k;
 }

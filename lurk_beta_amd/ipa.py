@@ -13,7 +13,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .msm import point_sum
+from .msm import point_sum, require_pasta_curve
 from .step import point_mul
 
 
@@ -70,6 +70,7 @@ def prove(curve: int, order: int, d_ck, ck_c_jac: np.ndarray, d_a, d_b, r0: int,
     a_hat canonical."""
     import torch
 
+    require_pasta_curve(curve, "the inner-product argument")
     lib = _lib.load()
     sf = 1 if curve == 0 else 0  # scalar field id
     q = order
@@ -140,6 +141,7 @@ def verify(key, n: int, P_jac, ck_c_jac, Ls, Rs, a_hat: int, challenge, d_b=None
     P + sum_j (r_j^2 L_j + r_j^-2 R_j) == [a_hat] <s, key> + [a_hat <s, b>] ck_c with b = d_b (device, Montgomery) or eq(eq_point).
     P, ck_c (already scaled), L_j, R_j: 96-byte Jacobians; challenge: a ``_lib.KeccakRounds`` or challenge(round, L, R) -> r.
     Returns (accepted, failed_check); n not a power of two raises (a call error, not a rejection)."""
+    require_pasta_curve(key.curve, "the inner-product argument's verifier")
     import torch
 
     rounds = max(len(Ls), 1)

@@ -13,19 +13,29 @@ import numpy as np
 
 from . import _lib
 
-CURVE_SCALAR_FIELD = {0: 1, 1: 0}  # Pallas scalars live in Fq, Vesta scalars in Fp
-CURVE_BASE_FIELD = {0: 0, 1: 1}
+CURVE_PALLAS, CURVE_VESTA, CURVE_BN254, CURVE_GRUMPKIN = 0, 1, 2, 3
+FIELD_BN254_FQ = 3  # the BN254 base field = Grumpkin's scalar field (commitment paths and point helpers only)
+CURVE_NAMES = {CURVE_PALLAS: "pallas", CURVE_VESTA: "vesta", CURVE_BN254: "bn254", CURVE_GRUMPKIN: "grumpkin"}
+CURVE_SCALAR_FIELD = {0: 1, 1: 0, 2: 2, 3: 3}  # Pallas scalars live in Fq, Vesta scalars in Fp; BN254 scalars in Fr, Grumpkin scalars in Fq
+CURVE_BASE_FIELD = {0: 0, 1: 1, 2: 3, 3: 2}
+
+
+def require_pasta_curve(curve: int, what: str) -> None:
+    """The Python mirrors of the calls the library offers on Pallas and Vesta only refuse the other curves by name, as the C side does."""
+    if curve not in (CURVE_PALLAS, CURVE_VESTA):
+        name = {CURVE_BN254: "BN254", CURVE_GRUMPKIN: "Grumpkin"}.get(curve, f"curve id {curve}")
+        raise _lib.LurkHipError(2, f"{what} is not offered on {name} (Pallas and Vesta only)")
 
 
 def msm(curve: int, bases: np.ndarray, scalars: np.ndarray, is_mont: bool = False) -> np.ndarray:
-    """One-shot ``mult_pippenger_{pallas,vesta}``: host buffers in, 96-byte Jacobian out (12 u64)."""
+    """One-shot ``mult_pippenger_{pallas,vesta,bn254,grumpkin}``: host buffers in, 96-byte Jacobian out (12 u64)."""
     lib = _lib.load()
     bases = np.ascontiguousarray(bases, dtype=np.uint64)
     scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
     n = scalars.size // 4
     assert bases.size // 8 == n, "bases and scalars differ in length"
     out = np.zeros(12, dtype=np.uint64)
-    fn = lib.lurk_hip_msm_pallas if curve == 0 else lib.lurk_hip_msm_vesta
+    fn = getattr(lib, "lurk_hip_msm_" + CURVE_NAMES[curve])
     _lib.check(fn(_lib.ptr(out), _lib.ptr(bases), n, _lib.ptr(scalars), int(is_mont)))
     return out
 
@@ -80,14 +90,18 @@ class CommitmentKey:
             _lib.check(lib.lurk_hip_msm_ctx_create(ctypes.byref(self._ctx), curve, _lib.ptr(bases), self.n, flags))
 
     @classmethod
-    def load(cls, path: str, precompute: bool = False, window_bits: int = 0) -> "CommitmentKey":
+    def load(cls, path: str, precompute: bool = False, window_bits: int = 0, curve: int | None = None) -> "CommitmentKey":
         """Key file -> resident context (``lurk_hip_msm_ctx_load``): the public-parameter cache of the commitment path
-        (/root/reference/src/public_parameters/mod.rs:33-56)."""
+        (/root/reference/src/public_parameters/mod.rs:33-56).  curve: the curve the caller expects; a file of another one is refused
+        (``lurk_hip_msm_ctx_load_curve``)."""
         lib = _lib.load()
         self = cls.__new__(cls)
         self._ctx = ctypes.c_void_p()
         flags = (1 if precompute else 0) | ((window_bits & 0xFF) << 8)
-        _lib.check(lib.lurk_hip_msm_ctx_load(ctypes.byref(self._ctx), path.encode(), flags))
+        if curve is None:
+            _lib.check(lib.lurk_hip_msm_ctx_load(ctypes.byref(self._ctx), path.encode(), flags))
+        else:
+            _lib.check(lib.lurk_hip_msm_ctx_load_curve(ctypes.byref(self._ctx), curve, path.encode(), flags))
         info = self.info()
         self.curve, self.n = info["curve"], info["npoints"]
         return self

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib, ipa, sumcheck
 from .fold import R1CSShape, fold_vec
-from .msm import point_to_affine
+from .msm import point_to_affine, require_pasta_curve
 
 
 class Transcript:
@@ -88,6 +88,7 @@ class SpartanProver:
     z = [W | u | X | 0 ...] of length 2 num_vars; num_cons and num_vars powers of two."""
 
     def __init__(self, curve: int, order: int, mats, num_cons: int, num_vars: int, num_io: int):
+        require_pasta_curve(curve, "the compressing SNARK")
         self.curve, self.q, self.num_cons, self.num_vars, self.num_io = curve, order, num_cons, num_vars, num_io
         self.sf = 1 if curve == 0 else 0
         assert num_cons & (num_cons - 1) == 0 and num_vars & (num_vars - 1) == 0 and 1 + num_io <= num_vars
@@ -446,6 +447,7 @@ class SpartanVerifier:
     shape, the s vector and one commitment under the resident key on the device, the rest on the host.  mats as for the prover."""
 
     def __init__(self, curve: int, order: int, mats, num_cons: int, num_vars: int, num_io: int):
+        require_pasta_curve(curve, "the compressing SNARK")
         self.curve, self.q, self.num_cons, self.num_vars, self.num_io = curve, order, num_cons, num_vars, num_io
         self.sf = 1 if curve == 0 else 0
         assert num_cons & (num_cons - 1) == 0 and num_vars & (num_vars - 1) == 0 and 1 + num_io <= num_vars

@@ -127,6 +127,56 @@ pub mod pasta_msm {
     curve_mod!(vesta, LURK_CURVE_VESTA, mult_pippenger_vesta, MSMContextVesta);
 }
 
+/// The `grumpkin-msm` crate's surface (arecibo's MSM crate for the BN254 / Grumpkin cycle, lurk-beta's default): `bn256(points,
+/// scalars)` and `grumpkin(points, scalars)` over `mult_pippenger_bn254` / `mult_pippenger_grumpkin`, and a resident key per curve.
+/// `halo2curves` with `repr-c` lays `G1Affine` out as 64 bytes and `G1` as 96 bytes of Montgomery limbs (recalled, unpinned - as the
+/// symbol names are); scalars are handed over in Montgomery form.  Behind the cargo feature `grumpkin` (it brings in `halo2curves`).
+#[cfg(feature = "grumpkin")]
+pub mod grumpkin_msm {
+    use super::*;
+    use halo2curves::{bn256, grumpkin};
+
+    macro_rules! curve_fn {
+        ($f:ident, $m:ident, $curve_id:expr, $oneshot:ident, $ctx:ident) => {
+            pub fn $f(points: &[$m::G1Affine], scalars: &[$m::Fr]) -> $m::G1 {
+                let n = points.len().min(scalars.len());
+                let mut out = $m::G1::default();
+                // SAFETY: both slices hold at least n elements of the layouts named above; out is 96 writable bytes
+                unsafe { $oneshot((&mut out as *mut $m::G1).cast(), points.as_ptr().cast(), n, scalars.as_ptr().cast(), true) };
+                out
+            }
+            /// A commitment key resident in HBM: `init(points)` / `with(&ctx, scalars)`.
+            pub struct $ctx(*mut lurk_hip_msm_ctx);
+            // SAFETY: every entry point of the library is thread-safe and a handle records its device
+            unsafe impl Send for $ctx {}
+            unsafe impl Sync for $ctx {}
+            impl $ctx {
+                pub fn init(points: &[$m::G1Affine], precompute: bool) -> Result<Self, Error> {
+                    let mut p = core::ptr::null_mut();
+                    let flags = if precompute { LURK_MSM_FLAG_PRECOMPUTE } else { 0 };
+                    check(unsafe { lurk_hip_msm_ctx_create(&mut p, $curve_id, points.as_ptr().cast(), points.len(), flags) })?;
+                    Ok(Self(p))
+                }
+                pub fn with(&self, scalars: &[$m::Fr]) -> Result<$m::G1, Error> {
+                    let mut out = $m::G1::default();
+                    check(unsafe { lurk_hip_msm_ctx_run(self.0, (&mut out as *mut $m::G1).cast(), scalars.as_ptr().cast(), scalars.len(), 1) })?;
+                    Ok(out)
+                }
+                pub fn as_ptr(&self) -> *mut lurk_hip_msm_ctx {
+                    self.0
+                }
+            }
+            impl Drop for $ctx {
+                fn drop(&mut self) {
+                    unsafe { lurk_hip_msm_ctx_destroy(self.0) };
+                }
+            }
+        };
+    }
+    curve_fn!(bn256, bn256, LURK_CURVE_BN254, mult_pippenger_bn254, MSMContextBn256);
+    curve_fn!(grumpkin, grumpkin, LURK_CURVE_GRUMPKIN, mult_pippenger_grumpkin, MSMContextGrumpkin);
+}
+
 /// An R1CS shape resident in HBM (arecibo `R1CSShape { A, B, C }` in CSR form, coefficients in Montgomery form).
 pub struct R1csShape(*mut lurk_hip_r1cs);
 unsafe impl Send for R1csShape {}
