@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Guard for the generated inline-asm multipliers (field_mul_asm.cuh, field29_mul_asm.cuh): they use FIXED scratch registers
+"""Guard for the generated inline-asm multipliers (field_mul_asm.cuh, field29_mul_asm.cuh, field29_mul_asm_p1.cuh): they use FIXED scratch registers
 declared as clobbers.  In a compiled .s (hipcc -save-temps) every asm block is matched against its template and the registers
 the compiler chose for the operands are extracted; an operand placed in a clobbered scratch register would be overwritten
 mid-block.  Usage: check_asm_operands.py <file.s>; exit status 1 on an overlap."""
@@ -7,7 +7,7 @@ import re
 import sys
 import os
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lurk_beta_amd', 'csrc')
-hdrs = [os.path.join(_CSRC, 'field29_mul_asm.cuh'), os.path.join(_CSRC, 'field_mul_asm.cuh')]
+hdrs = [os.path.join(_CSRC, 'field29_mul_asm.cuh'), os.path.join(_CSRC, 'field29_mul_asm_p1.cuh'), os.path.join(_CSRC, 'field_mul_asm.cuh')]
 templates = []
 for h in hdrs:
     src = open(h).read()

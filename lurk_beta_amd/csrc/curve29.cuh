@@ -8,6 +8,10 @@
 // Inside a mixed addition values grow through lazy subtractions (each adds the 64p bias, < 2^260); every
 // such value is carried (limbs tight again) before it is multiplied, and the two stored sums X3, Y3 are
 // brought back under 2^259 with f29_reduce (subtract a multiple of p read off the top limb: to below 2^255.1 for every modulus here).
+// So every product of the group law has tight operands (or one with limbs < 2^30) and goes through f29_mul30 / f29_sqr30, and the
+// Y3 rows (two tight terms) through dot29_finish2: reduction columns below 2^63, which the Pasta blocks without the mads by
+// modulus limb 0 need (field29.cuh).  The exceptions are in the doublings, u * u (2^30 x 2^30) and m * (s - x) (tight x loose): they
+// call the wide f29_mul.
 #pragma once
 #include "curve.cuh"
 #include "field29.cuh"
@@ -40,12 +44,7 @@ LURK_HD F29<P> f29_carry_signed(const int32_t* t) {
     return r;
 }
 
-// The Pasta primes are 2^254 + eps with eps < 2^126 and p == 1 mod 2^29; two shortcuts below lean on that shape.  The BN254 primes
-// (0.756 * 2^254, no zero limbs, p != 1 mod 2^29) take the general forms.
-template <class P>
-LURK_HD constexpr bool f29_pasta_shape() {
-    return P::NBITS == 255 && f29_mod<P>(0) == 1u && f29_mod<P>(5) == 0u && f29_mod<P>(6) == 0u && f29_mod<P>(7) == 0u;
-}
+// (f29_pasta_shape, which two shortcuts below lean on, is field29.cuh's)
 
 // v (tight limbs, top limb any u32 < 2^31) -> equivalent value < 2^255.1 with tight limbs.
 // Pasta: p = 2^254 + eps, eps < 2^126 (limbs 0..4), so  v - k p = (v mod 2^254) - k eps  with k = v >> 254;
@@ -159,16 +158,16 @@ LURK_HD bool f29_is_multiple_of_p(const F29<P>& v) {
 template <class P>
 LURK_HD LURK_F29_RARE_ATTR Xyzz29<P> xyzz29_double_affine(F29<P> qx, F29<P> qy_signed) {
     const F29<P> u = f29_dbl<P>(qy_signed);                      // limbs < 2^30, value < 2^260
-    const F29<P> v = f29_mul<P>(u, u);                           // < 2^259 + p
-    const F29<P> w = f29_mul<P>(u, v);
-    const F29<P> s = f29_mul<P>(qx, v);
-    const F29<P> xx = f29_sqr<P>(qx);
+    const F29<P> v = f29_mul<P>(u, u);                             // < 2^259 + p  (2^30 x 2^30: the wide product)
+    const F29<P> w = f29_mul30<P>(u, v);
+    const F29<P> s = f29_mul30<P>(qx, v);
+    const F29<P> xx = f29_sqr30<P>(qx);
     const F29<P> m = f29_carry<P>(f29_add<P>(f29_dbl<P>(xx), xx));  // 3 x^2, tight
-    const F29<P> m2 = f29_sqr<P>(m);
+    const F29<P> m2 = f29_sqr30<P>(m);
     Xyzz29<P> r;
     r.x = f29_reduce<P>(f29_carry<P>(f29_sub<P>(m2, f29_dbl<P>(s))));
-    const F29<P> t1 = f29_mul<P>(m, f29_sub<P>(s, r.x));
-    const F29<P> t2 = f29_mul<P>(w, qy_signed);
+    const F29<P> t1 = f29_mul<P>(m, f29_sub<P>(s, r.x));            // tight x loose: the wide product
+    const F29<P> t2 = f29_mul30<P>(w, qy_signed);
     r.y = f29_reduce<P>(f29_carry<P>(f29_sub<P>(t1, t2)));
     r.zz = v;
     r.zzz = w;
@@ -197,8 +196,8 @@ LURK_HD void xyzz29_madd(Xyzz29<P>& acc, bool& acc_id, const Affine<P>& q, bool 
     F29_ASSERT_LIMBS(acc.y, 29, "acc.y"); F29_ASSERT_TOP(acc.y, 27, "acc.y");
     F29_ASSERT_LIMBS(acc.zz, 29, "acc.zz"); F29_ASSERT_TOP(acc.zz, 27, "acc.zz");
     F29_ASSERT_LIMBS(acc.zzz, 29, "acc.zzz"); F29_ASSERT_TOP(acc.zzz, 27, "acc.zzz");
-    const F29<P> u2 = ACC_AFFINE ? qx : f29_mul<P>(qx, acc.zz);    // < 2^257.2  (affine: < 2^259)
-    const F29<P> s2 = ACC_AFFINE ? qy : f29_mul<P>(qy, acc.zzz);
+    const F29<P> u2 = ACC_AFFINE ? qx : f29_mul30<P>(qx, acc.zz);    // < 2^257.2  (affine: < 2^259)
+    const F29<P> s2 = ACC_AFFINE ? qy : f29_mul30<P>(qy, acc.zzz);
     const F29<P> p = f29_carry<P>(f29_sub<P>(u2, acc.x));  // U2 - X1 + 64p  < 2^260.3
     // r = S2 - Y1 for +q; for -q the true r is -(S2 + Y1): keep r' = S2 + Y1 and flip the sign of (Q - X3) below
     F29<P> r;
@@ -217,10 +216,10 @@ LURK_HD void xyzz29_madd(Xyzz29<P>& acc, bool& acc_id, const Affine<P>& q, bool 
         }
         return;
     }
-    const F29<P> pp = f29_sqr<P>(p);          // < 2^259.7
-    const F29<P> ppp = f29_mul<P>(p, pp);        // < 2^259.1
-    const F29<P> qq = f29_mul<P>(acc.x, pp);     // < 2^257.8
-    const F29<P> r2 = f29_sqr<P>(r);          // < 2^259.7
+    const F29<P> pp = f29_sqr30<P>(p);          // < 2^259.7
+    const F29<P> ppp = f29_mul30<P>(p, pp);        // < 2^259.1
+    const F29<P> qq = f29_mul30<P>(acc.x, pp);     // < 2^257.8
+    const F29<P> r2 = f29_sqr30<P>(r);          // < 2^259.7
     // X3 = R^2 - PPP - 2Q   (two lazy subtractions: limbs < 2^32, value < 2^261.5)
     F29<P> x3 = f29_sub<P>(f29_sub<P>(r2, ppp), f29_dbl<P>(qq));
     x3 = f29_reduce<P>(f29_carry<P>(x3));        // < 2^255.1, tight
@@ -241,10 +240,10 @@ LURK_HD void xyzz29_madd(Xyzz29<P>& acc, bool& acc_id, const Affine<P>& q, bool 
     // (the f29_reduce is not optional: in the affine-accumulator form r and p reach 2^260.6, the row 2^521.4, so Y3 can exceed
     // 64p = 2^260 and the next addition's 64p - Y1 would go negative - seen on the GPU and reproduced on the host with points
     // 640..642 of the synthetic key; in the general form Y3 stays below 2^259.96, but dropping the reduce there measured no gain)
-    F29<P> y3 = f29_reduce<P>(dot29_finish<P>(row));
+    F29<P> y3 = f29_reduce<P>(dot29_finish2<P>(row));
 #else
-    const F29<P> t1 = f29_mul<P>(r, d);          // r tight (< 2^260.3), d loose (< 2^260.1): < 2^259.5
-    const F29<P> t2 = f29_mul<P>(acc.y, ppp);    // < 2^257.2
+    const F29<P> t1 = f29_mul<P>(r, d);            // r tight (< 2^260.3), d loose (< 2^260.1): < 2^259.5
+    const F29<P> t2 = f29_mul30<P>(acc.y, ppp);    // < 2^257.2
     F29<P> y3 = f29_reduce<P>(f29_carry<P>(f29_sub<P>(t1, t2)));
 #endif
     acc.x = x3;
@@ -253,8 +252,8 @@ LURK_HD void xyzz29_madd(Xyzz29<P>& acc, bool& acc_id, const Affine<P>& q, bool 
         acc.zz = f29_reduce<P>(pp);              // < 2^255.1 (the loop invariant wants < 2^259)
         acc.zzz = f29_reduce<P>(ppp);
     } else {
-        acc.zz = f29_mul<P>(acc.zz, pp);         // < 2^257.8
-        acc.zzz = f29_mul<P>(acc.zzz, ppp);      // < 2^257.2
+        acc.zz = f29_mul30<P>(acc.zz, pp);         // < 2^257.8
+        acc.zzz = f29_mul30<P>(acc.zzz, ppp);      // < 2^257.2
     }
 }
 
@@ -264,19 +263,19 @@ LURK_HD void xyzz29_madd(Xyzz29<P>& acc, bool& acc_id, const Affine<P>& q, bool 
 template <class P>
 LURK_HD Xyzz29<P> xyzz29_dbl(const Xyzz29<P>& a) {
     const F29<P> u = f29_dbl<P>(a.y);                            // limbs < 2^30, value < 2^260
-    const F29<P> v = f29_mul<P>(u, u);                           // < 2^259 + p
-    const F29<P> w = f29_mul<P>(u, v);
-    const F29<P> s = f29_mul<P>(a.x, v);
-    const F29<P> xx = f29_sqr<P>(a.x);
+    const F29<P> v = f29_mul<P>(u, u);                             // < 2^259 + p  (2^30 x 2^30: the wide product)
+    const F29<P> w = f29_mul30<P>(u, v);
+    const F29<P> s = f29_mul30<P>(a.x, v);
+    const F29<P> xx = f29_sqr30<P>(a.x);
     const F29<P> m = f29_carry<P>(f29_add<P>(f29_dbl<P>(xx), xx));  // 3 x^2, tight
-    const F29<P> m2 = f29_sqr<P>(m);
+    const F29<P> m2 = f29_sqr30<P>(m);
     Xyzz29<P> r;
     r.x = f29_reduce<P>(f29_carry<P>(f29_sub<P>(m2, f29_dbl<P>(s))));
-    const F29<P> t1 = f29_mul<P>(m, f29_sub<P>(s, r.x));
-    const F29<P> t2 = f29_mul<P>(w, a.y);
+    const F29<P> t1 = f29_mul<P>(m, f29_sub<P>(s, r.x));            // tight x loose: the wide product
+    const F29<P> t2 = f29_mul30<P>(w, a.y);
     r.y = f29_reduce<P>(f29_carry<P>(f29_sub<P>(t1, t2)));
-    r.zz = f29_mul<P>(v, a.zz);
-    r.zzz = f29_mul<P>(w, a.zzz);
+    r.zz = f29_mul30<P>(v, a.zz);
+    r.zzz = f29_mul30<P>(w, a.zzz);
     return r;
 }
 
@@ -310,10 +309,10 @@ LURK_HD void xyzz29_add(Xyzz29<P>& acc, bool& acc_id, const Xyzz29<P>& q, bool q
     F29_ASSERT_LIMBS(q.y, 29, "add q.y"); F29_ASSERT_TOP(q.y, 27, "add q.y");
     F29_ASSERT_LIMBS(q.zz, 29, "add q.zz"); F29_ASSERT_TOP(q.zz, 27, "add q.zz");
     F29_ASSERT_LIMBS(q.zzz, 29, "add q.zzz"); F29_ASSERT_TOP(q.zzz, 27, "add q.zzz");
-    const F29<P> u1 = f29_mul<P>(acc.x, q.zz);     // < 2^257.2, tight
-    const F29<P> u2 = f29_mul<P>(q.x, acc.zz);
-    const F29<P> s1 = f29_mul<P>(acc.y, q.zzz);
-    const F29<P> s2 = f29_mul<P>(q.y, acc.zzz);
+    const F29<P> u1 = f29_mul30<P>(acc.x, q.zz);     // < 2^257.2, tight
+    const F29<P> u2 = f29_mul30<P>(q.x, acc.zz);
+    const F29<P> s1 = f29_mul30<P>(acc.y, q.zzz);
+    const F29<P> s2 = f29_mul30<P>(q.y, acc.zzz);
     const F29<P> p = f29_carry<P>(f29_sub<P>(u2, u1));  // U2 - U1 + 64p < 2^260.3
     const F29<P> r = f29_carry<P>(f29_sub<P>(s2, s1));
     if (f29_maybe_multiple_of_p<P>(p) && f29_is_multiple_of_p<P>(p)) {
@@ -321,10 +320,10 @@ LURK_HD void xyzz29_add(Xyzz29<P>& acc, bool& acc_id, const Xyzz29<P>& q, bool q
         else acc_id = true;                                                                     // opposite points
         return;
     }
-    const F29<P> pp = f29_sqr<P>(p);               // < 2^259.7
-    const F29<P> ppp = f29_mul<P>(p, pp);          // < 2^259.1
-    const F29<P> qq = f29_mul<P>(u1, pp);          // < 2^256
-    const F29<P> r2 = f29_sqr<P>(r);               // < 2^259.7
+    const F29<P> pp = f29_sqr30<P>(p);               // < 2^259.7
+    const F29<P> ppp = f29_mul30<P>(p, pp);          // < 2^259.1
+    const F29<P> qq = f29_mul30<P>(u1, pp);          // < 2^256
+    const F29<P> r2 = f29_sqr30<P>(r);               // < 2^259.7
     F29<P> x3 = f29_sub<P>(f29_sub<P>(r2, ppp), f29_dbl<P>(qq));
     x3 = f29_reduce<P>(f29_carry<P>(x3));          // < 2^255.1, tight
     F29<P> d;
@@ -338,13 +337,13 @@ LURK_HD void xyzz29_add(Xyzz29<P>& acc, bool& acc_id, const Xyzz29<P>& q, bool q
     dot29_init<P>(row);
     dot29_mac<P>(row, r, f29_carry<P>(d));
     dot29_mac<P>(row, f29_carry<P>(f29_sub<P>(f29_zero<P>(), s1)), ppp);
-    const F29<P> y3 = f29_reduce<P>(dot29_finish<P>(row));
-    const F29<P> zz12 = f29_mul<P>(acc.zz, q.zz);  // < 2^257.2
-    const F29<P> zzz12 = f29_mul<P>(acc.zzz, q.zzz);
+    const F29<P> y3 = f29_reduce<P>(dot29_finish2<P>(row));
+    const F29<P> zz12 = f29_mul30<P>(acc.zz, q.zz);  // < 2^257.2
+    const F29<P> zzz12 = f29_mul30<P>(acc.zzz, q.zzz);
     acc.x = x3;
     acc.y = y3;
-    acc.zz = f29_mul<P>(zz12, pp);                 // < 2^256
-    acc.zzz = f29_mul<P>(zzz12, ppp);
+    acc.zz = f29_mul30<P>(zz12, pp);                 // < 2^256
+    acc.zzz = f29_mul30<P>(zzz12, ppp);
 }
 
 // Sum of nt XYZZ points held in the 8 x 32 form (a bucket's task partials: msm_finalize.hip).  One point is copied, more go through

@@ -14,8 +14,20 @@
 // a*b < 2^261 (2^261 - p), e.g. both operands < 2^261 and one < 2^260 (two all-ones tight operands give a top limb >= 2^29).  Nothing at the C ABI changes: values cross into this layer with f29_from_mont256
 // (x * 2^256 -> x * 2^261 is a 5-bit shift, folded into the limb repacking) and leave it with
 // f29_to_mont256 (one product with 2^256, then a canonical reduction).
+//
+// Two entry points to the product.  f29_mul keeps the contract above.  f29_mul30 is the product of the hot loops, whose operands
+// are always carried first: it needs 9 * la * lb + 5 * 2^58 + carry < 2^63 for la, lb the largest limbs of a and b - tight x
+// (limbs < 2^30) fits, tight x loose and 2^30 x 2^30 do NOT.  On the moduli that are 1 mod 2^29 (both Pasta fields) it runs
+// the blocks of field29_mul_asm_p1.cuh, which carry the accumulator one below its true value through the reduction columns and so
+// drop the nine mads by modulus limb 0: 126 mads per product, 90 per squaring, the same limbs out (gen_field29_asm.py, gen_mul).
+// f29_sqr30 (operand tight) and dot29_finish2 (rows of at most two tight terms) take the same form.  On every other modulus the
+// three are the plain functions.  -DLURK_F29_P1=0 compiles the plain form everywhere (A/B runs).
 #pragma once
 #include "field.cuh"
+
+#ifndef LURK_F29_P1
+#define LURK_F29_P1 1
+#endif
 
 // LURK_F29_CHECK (host builds of the test harness only): every limb / accumulator bound the radix-2^29
 // code relies on is asserted at run time.
@@ -65,6 +77,18 @@ LURK_HD constexpr uint32_t f29_mod(int i) {
 template <class P>
 LURK_HD constexpr uint32_t f29_inv() {  // -p^-1 mod 2^29 (from the 32-bit constant)
     return P::INV & F29_MASK;
+}
+
+// The Pasta primes are 2^254 + eps with eps < 2^126 and p == 1 mod 2^29; shortcuts here and in curve29.cuh lean on that shape.  The
+// BN254 primes (0.756 * 2^254, no zero limbs, p != 1 mod 2^29) take the general forms.
+template <class P>
+LURK_HD constexpr bool f29_pasta_shape() {
+    return P::NBITS == 255 && f29_mod<P>(0) == 1u && f29_mod<P>(5) == 0u && f29_mod<P>(6) == 0u && f29_mod<P>(7) == 0u;
+}
+// the reduction that carries its accumulator one below the true value (f29_mul30, f29_sqr30, dot29_finish2) applies
+template <class P>
+LURK_HD constexpr bool f29_p1_form() {
+    return LURK_F29_P1 != 0 && f29_pasta_shape<P>() && f29_inv<P>() == F29_MASK;
 }
 
 template <class P>
@@ -169,11 +193,54 @@ LURK_HD F29<P> f29_mul_portable(const F29<P>& a, const F29<P>& b) {
     return t;
 }
 
+// portable f29_mul30 (what the blocks of field29_mul_asm_p1.cuh compute, column for column): acc holds H = A - 1 through the
+// reduction columns.  p_0 = 1 and -p^-1 = 2^29 - 1 give m_k = (-A) mod 2^29 = ~H mod 2^29, and A + m_k * p_0 >> 29 = ceil(A / 2^29)
+// = (H >> 29) + 1 with a signed shift (H = -1 for A = 0): nothing is multiplied by p_0, and the m_k and the output limbs are
+// f29_mul_portable's.  The signed shift wants every reduction column below 2^63.
+template <class P>
+LURK_HD F29<P> f29_mul30_portable(const F29<P>& a, const F29<P>& b) {
+    if constexpr (!f29_p1_form<P>()) {
+        return f29_mul_portable<P>(a, b);
+    } else {
+        uint32_t m[9];
+        F29<P> t;
+        uint64_t acc = ~(uint64_t)0;
+#if defined(LURK_F29_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+        {
+            uint64_t ma = 0, mb = 0;
+            for (int i = 0; i < 9; i++) { ma = a.l[i] > ma ? a.l[i] : ma; mb = b.l[i] > mb ? b.l[i] : mb; }
+            // 9 products + 5 reduction terms (< 2^58 each: modulus limbs 1..4 and 8) + the running carry (< 2^36) below 2^63
+            F29_ASSERT((unsigned __int128)ma * mb * 9 + ((unsigned __int128)5 << 58) + ((unsigned __int128)1 << 36) < ((unsigned __int128)1 << 63), "f29_mul column overflow");
+        }
+#endif
+#pragma unroll
+        for (int k = 0; k < 17; k++) {
+#pragma unroll
+            for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) acc += (uint64_t)a.l[i] * b.l[k - i];
+#pragma unroll
+            for (int i = (k > 8 ? k - 8 : 0); i <= (k - 1 < 8 ? k - 1 : 8); i++) acc += (uint64_t)m[i] * f29_mod<P>(k - i);
+            if (k <= 8) {
+                F29_ASSERT((int64_t)acc >= -1, "f29_mul column overflow");
+                m[k] = ~(uint32_t)acc & F29_MASK;
+                acc = (uint64_t)((int64_t)acc >> 29);
+                if (k == 8) acc += 1;
+            } else {
+                t.l[k - 9] = (uint32_t)acc & F29_MASK;
+                acc >>= 29;
+            }
+        }
+        t.l[8] = (uint32_t)acc;
+        return t;
+    }
+}
+
 }  // namespace lurk
 #include "field29_mul_asm.cuh"
 #include "field29_mul_asm_bn254fq.cuh"
+#include "field29_mul_asm_p1.cuh"
 namespace lurk {
 
+// one operand tight and the other loose, or both with limbs < 2^30
 template <class P>
 LURK_HD F29<P> f29_mul(const F29<P>& a, const F29<P>& b) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -182,13 +249,33 @@ LURK_HD F29<P> f29_mul(const F29<P>& a, const F29<P>& b) {
     return f29_mul_portable<P>(a, b);
 #endif
 }
-// a must be tight (the squaring block multiplies a by its doubled copy)
+// the narrower contract (top of the file): 9 * la * lb + 5 * 2^58 + carry < 2^63, e.g. a tight and every limb of b < 2^30
+template <class P>
+LURK_HD F29<P> f29_mul30(const F29<P>& a, const F29<P>& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (f29_p1_form<P>()) return f29_mul_p1_asm<P>(a, b);
+    else return f29_mul_asm<P>(a, b);
+#else
+    return f29_mul30_portable<P>(a, b);
+#endif
+}
+// a must be tight, or have limbs < 2^30 at most (the squaring block multiplies a by its doubled copy)
 template <class P>
 LURK_HD F29<P> f29_sqr(const F29<P>& a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return f29_sqr_asm<P>(a);
 #else
     return f29_mul_portable<P>(a, a);
+#endif
+}
+// a must be tight: the square under f29_mul30's contract (the doubled copy has limbs < 2^30)
+template <class P>
+LURK_HD F29<P> f29_sqr30(const F29<P>& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (f29_p1_form<P>()) return f29_sqr_p1_asm<P>(a);
+    else return f29_sqr_asm<P>(a);
+#else
+    return f29_mul30_portable<P>(a, a);
 #endif
 }
 
@@ -212,8 +299,8 @@ LURK_HD F29<P> f29_invert(const F29<P>& a) {
 #pragma unroll 1
 #endif
     for (int b = top - 1; b >= 0; b--) {
-        acc = f29_sqr<P>(acc);
-        if ((e[b >> 5] >> (b & 31)) & 1u) acc = f29_mul<P>(acc, a);
+        acc = f29_sqr30<P>(acc);
+        if ((e[b >> 5] >> (b & 31)) & 1u) acc = f29_mul30<P>(acc, a);
     }
     return acc;
 }
@@ -285,6 +372,41 @@ LURK_HD F29<P> dot29_finish(const Dot29<P>& A) {
     return t;
 }
 
+// dot29_finish for a row of at most TWO products of tight operands (18 * 2^58 per column: the Y3 rows of curve29.cuh).  Every
+// column plus the reduction's own terms stays below 2^63, so the moduli that are 1 mod 2^29 take the form of f29_mul30_portable:
+// nothing is multiplied by modulus limb 0.  The same limbs out as dot29_finish.
+template <class P>
+LURK_HD F29<P> dot29_finish2(const Dot29<P>& A) {
+    if constexpr (!f29_p1_form<P>()) {
+        return dot29_finish<P>(A);
+    } else {
+        uint32_t m[9];
+        F29<P> t;
+        uint64_t acc = ~(uint64_t)0;  // H = (true accumulator) - 1
+#if defined(LURK_F29_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+        for (int k = 0; k < 17; k++)
+            F29_ASSERT(A.shadow[k] + ((unsigned __int128)5 << 58) + ((unsigned __int128)1 << 36) < ((unsigned __int128)1 << 63), "dot29 column overflow");
+#endif
+#pragma unroll
+        for (int k = 0; k < 17; k++) {
+            acc += A.c[k];
+#pragma unroll
+            for (int i = (k > 8 ? k - 8 : 0); i <= (k - 1 < 8 ? k - 1 : 8); i++) acc += (uint64_t)m[i] * f29_mod<P>(k - i);
+            if (k <= 8) {
+                F29_ASSERT((int64_t)acc >= -1, "dot29 column overflow");
+                m[k] = ~(uint32_t)acc & F29_MASK;
+                acc = (uint64_t)((int64_t)acc >> 29);
+                if (k == 8) acc += 1;
+            } else {
+                t.l[k - 9] = (uint32_t)acc & F29_MASK;
+                acc >>= 29;
+            }
+        }
+        t.l[8] = (uint32_t)acc;
+        return t;
+    }
+}
+
 // 8 x 32 Montgomery(2^256) -> 9 x 29 Montgomery(2^261): value * 32, i.e. limbs of (x << 5); tight.
 template <class P>
 LURK_HD F29<P> f29_from_mont256(const Fe<P>& x) {
@@ -341,7 +463,7 @@ LURK_HD F29<P> f29_const_r256() {
 // lazy Montgomery(2^261) value -> canonical Montgomery(2^256) 8 x 32 (the layout of the C ABI)
 template <class P>
 LURK_HD Fe<P> f29_to_mont256(const F29<P>& a) {
-    F29<P> u = f29_mul<P>(f29_carry<P>(a), f29_const_r256<P>());  // a / 32: tight limbs, value < 2^255 + p < 4p
+    F29<P> u = f29_mul30<P>(f29_carry<P>(a), f29_const_r256<P>());  // a / 32: tight limbs, value < 2^255 + p < 4p
     uint32_t w[8];
     f29_pack<P>(u, w);
     fe_cond_sub2<P>(w);

@@ -11,6 +11,9 @@ values kept lazily in [0, 2^261)).
 Emitted per field: one asm block  t = a*b / 2^261 mod p, value a*b / 2^261 + (< p): limbs 0..7 < 2^29, the top limb takes the rest
 (< 2^29 when a*b < 2^261 (2^261 - p)).
 Contract: every limb of a and b < 2^30 (so a value may be the limb-wise sum of two normalised ones).
+
+--p1 writes field29_mul_asm_p1.cuh: the blocks of the moduli that are 1 mod 2^29 without the nine mads by modulus limb 0 (126 mads
+per product, 90 per squaring), for operands with 9 la lb + 5 2^58 + carry < 2^63 (see gen_mul).
 """
 import sys
 
@@ -23,6 +26,8 @@ FIELDS = {
 BN254FQ_FIELDS = {
     "Bn254Fq": 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47,
 }
+# --p1: a second family of blocks for the moduli that are 1 mod 2^29, in field29_mul_asm_p1.cuh
+P1_FIELDS = ("PallasFp", "PallasFq")
 W = 29
 MASK = (1 << W) - 1
 ACC_LO, ACC_HI = 16, 17
@@ -40,10 +45,18 @@ def limbs29(x):
     return [(x >> (W * i)) & MASK for i in range(9)]
 
 
-def gen_mul(modulus, square=False):
-    """square=True: b is ignored; operands %18.. hold 2*a (limbs < 2^30) and the 36 cross products are issued once."""
+def gen_mul(modulus, square=False, p1=False):
+    """square=True: b is ignored; operands %18.. hold 2*a (limbs < 2^30) and the 36 cross products are issued once.
+    p1=True (--p1, moduli == 1 mod 2^29 only): the accumulator is carried ONE BELOW its true value through the nine reduction
+    columns.  With p_0 = 1 and -p^-1 = 2^29 - 1, m_k = (-A) mod 2^29 and the step  A += m_k * 1; A >>= 29  is ceil(A / 2^29).  For
+    H = A - 1:  m_k = ~H mod 2^29  and  ceil(A / 2^29) - 1 = H >> 29 (arithmetic: H = -1 when A = 0), so the invariant carries
+    into the next column by itself and the nine mads by p_0 are not issued.  It is entered by the first mad's src2 = -1 and left
+    by one 64-bit increment after column 8.  Every m_k and every output limb is the one the plain block computes; the price is
+    that a reduction column must stay below 2^63 (the shift is signed), not 2^64."""
     p = limbs29(modulus)
     inv = (-pow(modulus, -1, 1 << W)) % (1 << W)
+    if p1 and (p[0] != 1 or inv != MASK):
+        raise SystemExit(f"--p1: modulus 0x{modulus:x} is not 1 mod 2^{W}")
     L = []
     T = lambda i: f"%{i}"
     A = lambda i: f"%{9 + i}"
@@ -75,9 +88,17 @@ def gen_mul(modulus, square=False):
             prods = [(A(i), B(k - i)) for i in range(max(0, k - 8), min(k, 8) + 1)]
         prods += [(M(i), P(k - i)) for i in range(max(0, k - 8), min(k - 1, 8) + 1) if p[k - i] != 0]
         for x, y in prods:
-            src2 = "0" if first else f"v[{ACC_LO}:{ACC_HI}]"
+            src2 = ("-1" if p1 else "0") if first else f"v[{ACC_LO}:{ACC_HI}]"
             L.append(f"v_mad_u64_u32 v[{ACC_LO}:{ACC_HI}], s[{DUMMY}:{DUMMY + 1}], {x}, {y}, {src2}")
             first = False
+        if k <= 8 and p1:
+            # m_k = ~H mod 2^29 ; H >>= 29 (signed) ; true value again after the last reduction column
+            L.append(f"v_not_b32 {M(k)}, v{ACC_LO}")
+            L.append(f"v_and_b32 {M(k)}, v{MASK_VGPR}, {M(k)}")
+            L.append(f"v_ashrrev_i64 v[{ACC_LO}:{ACC_HI}], {W}, v[{ACC_LO}:{ACC_HI}]")
+            if k == 8:
+                L.append(f"v_lshl_add_u64 v[{ACC_LO}:{ACC_HI}], v[{ACC_LO}:{ACC_HI}], 0, 1")
+            continue
         if k <= 8:
             # m_k = (-acc * p^-1) mod 2^29 ; acc += m_k * p_0  (clears the low 29 bits)
             if inv == MASK:
@@ -96,8 +117,9 @@ def gen_mul(modulus, square=False):
     return L, p, inv
 
 
-def cxx_sqr(name, modulus):
-    lines, p, inv = gen_mul(modulus, square=True)
+def cxx_sqr(name, modulus, p1=False):
+    lines, p, inv = gen_mul(modulus, square=True, p1=p1)
+    fn = "f29_sqr_p1_asm" if p1 else "f29_sqr_asm"
     nmad = sum(1 for l in lines if l.startswith("v_mad"))
     body = "\n".join(f'        "{l}\\n\\t"' for l in lines)
     outs = ", ".join(f'"=&v"(t.l[{i}])' for i in range(9))
@@ -106,7 +128,7 @@ def cxx_sqr(name, modulus):
     sclob = ", ".join(f'"s{r}"' for r in range(P_SGPR_BASE, DUMMY + 2))
     return f"""// {name} squaring: {nmad} v_mad_u64_u32 (cross products once, against the doubled operand)
 template <>
-__device__ __forceinline__ F29<{name}> f29_sqr_asm<{name}>(const F29<{name}>& a) {{
+__device__ __forceinline__ F29<{name}> {fn}<{name}>(const F29<{name}>& a) {{
     F29<{name}> t, d;
 #pragma unroll
     for (int i = 0; i < 9; i++) d.l[i] = a.l[i] << 1;
@@ -120,8 +142,9 @@ __device__ __forceinline__ F29<{name}> f29_sqr_asm<{name}>(const F29<{name}>& a)
 """
 
 
-def cxx(name, modulus):
-    lines, p, inv = gen_mul(modulus)
+def cxx(name, modulus, p1=False):
+    lines, p, inv = gen_mul(modulus, p1=p1)
+    fn = "f29_mul_p1_asm" if p1 else "f29_mul_asm"
     nmad = sum(1 for l in lines if l.startswith("v_mad"))
     nvalu = sum(1 for l in lines if l.startswith("v_"))
     body = "\n".join(f'        "{l}\\n\\t"' for l in lines)
@@ -131,7 +154,7 @@ def cxx(name, modulus):
     sclob = ", ".join(f'"s{r}"' for r in range(P_SGPR_BASE, DUMMY + 2))
     return f"""// {name}: {nmad} v_mad_u64_u32, {nvalu} VALU instructions, no carry folds
 template <>
-__device__ __forceinline__ F29<{name}> f29_mul_asm<{name}>(const F29<{name}>& a, const F29<{name}>& b) {{
+__device__ __forceinline__ F29<{name}> {fn}<{name}>(const F29<{name}>& a, const F29<{name}>& b) {{
     F29<{name}> t;
     asm(
 {body}
@@ -145,20 +168,32 @@ __device__ __forceinline__ F29<{name}> f29_mul_asm<{name}>(const F29<{name}>& a,
 
 def main():
     bn254fq = sys.argv[1:] == ["--bn254fq"]
+    p1 = sys.argv[1:] == ["--p1"]
     out = [
         "// field29_mul_asm_bn254fq.cuh - GENERATED by gen_field29_asm.py --bn254fq; do not edit." if bn254fq else
+        "// field29_mul_asm_p1.cuh - GENERATED by gen_field29_asm.py --p1; do not edit." if p1 else
         "// field29_mul_asm.cuh - GENERATED by gen_field29_asm.py; do not edit.",
         "#pragma once",
         "#if defined(__HIP_DEVICE_COMPILE__)",
         "namespace lurk {",
     ]
-    if not bn254fq:  # (the --bn254fq header holds specialisations only: it is included right after this one)
+    if p1:
+        # the blocks of the moduli that are 1 mod 2^29 (both Pasta fields) without the nine mads by p_0: see gen_mul
+        out += [
+            "template <class P> __device__ __forceinline__ F29<P> f29_mul_p1_asm(const F29<P>& a, const F29<P>& b);",
+            "template <class P> __device__ __forceinline__ F29<P> f29_sqr_p1_asm(const F29<P>& a);",
+        ]
+    elif not bn254fq:  # (the --bn254fq header holds specialisations only: it is included right after this one)
         out += [
             "template <class P> __device__ __forceinline__ F29<P> f29_mul_asm(const F29<P>& a, const F29<P>& b);",
             "template <class P> __device__ __forceinline__ F29<P> f29_sqr_asm(const F29<P>& a);",
         ]
     out.append("")
-    for name, mod in (BN254FQ_FIELDS if bn254fq else FIELDS).items():
+    if p1:
+        for name in P1_FIELDS:
+            out.append(cxx(name, FIELDS[name], p1=True))
+            out.append(cxx_sqr(name, FIELDS[name], p1=True))
+    for name, mod in ({} if p1 else BN254FQ_FIELDS if bn254fq else FIELDS).items():
         out.append(cxx(name, mod))
         out.append(cxx_sqr(name, mod))
     out += ["}  // namespace lurk", "#endif"]
