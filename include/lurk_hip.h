@@ -48,7 +48,9 @@ extern "C" {
  * Fq with scalars in Fr, Grumpkin is y^2 = x^3 - 17 over Fr with scalars in Fq.  Layouts as halo2curves `repr-c` has them, recalled
  * [MEM] and unpinned like the Pasta ones: affine {x, y} 64 B Montgomery with (0, 0) for the identity, Jacobian {x, y, z} 96 B.
  * Offered: every lurk_hip_msm_* / lurk_hip_msm_ctx_* / lurk_hip_msm_multi_* commitment path, the point helpers,
- * lurk_hip_synth_bases_dev (generators (1, 2) and (1, sqrt(-16))) and lurk_hip_fold_ctx_* on BN254 with a caller-supplied challenge.
+ * lurk_hip_synth_bases_dev (generators (1, 2) and (1, sqrt(-16))) and lurk_hip_fold_ctx_* on BN254 with a caller-supplied challenge;
+ * on BN254 G1 alone the HyperKZG opening argument (lurk_hip_hyperkzg_prove_dev, lurk_hip_hyperkzg_pairing_inputs) and the powers-of-tau
+ * test key (lurk_hip_synth_kzg_bases_dev), which refuse Grumpkin and the Pasta curves by name.
  * Refused by name (non-zero, the curve named in lurk_hip_last_error()): lurk_hip_msm_ctx_from_label and the other hash-to-curve calls,
  * lurk_hip_msm_ctx_fold_key_dev, the IPA / Spartan / verify calls, lurk_hip_fold_step, _set_pp_digest, _challenge and
  * lurk_hip_nifs_* (no Poseidon constants over Fq yet), and a folding context on Grumpkin. */
@@ -756,6 +758,59 @@ int lurk_hip_ipa_prove_dev(lurk_hip_msm_ctx* key, void* d_a32, void* d_b32, size
                            lurk_hip_ipa_challenge_fn challenge, void* user, void* out_l_jacobian96, void* out_r_jacobian96,
                            void* out_a_hat32, void* out_ck_hat_affine64, void* stream);
 
+/* ---- HyperKZG: the opening argument of the BN254 cycle (EE1 of Bn256EngineKZG, /root/reference/src/proof/nova.rs:65-71) ---------------
+ * The three polynomial primitives the argument is made of, over field ids 0, 1 and 2 (vectors of 32-byte Montgomery elements in device
+ * memory; scalars Montgomery in HOST memory):
+ *   mle_fold_pairs   d_out[j] = d_in[2j] + x (d_in[2j+1] - d_in[2j]) for j < ceil(len / 2): the LOWEST variable of a multilinear
+ *                    polynomial's evaluation table is bound (lurk_hip_fold_halves_dev pairs i with len/2 + i: the highest).  An element
+ *                    past the end reads as zero; d_out may not overlap d_in (refused).  len >= 1.  No synchronisation.
+ *   poly_eval        out[k] = sum_j d_coeffs[j] points[k]^j for k < n_points <= 4, one pass over the coefficients (low to high); len = 0
+ *                    gives zeros.  out32_mont: host memory; the call synchronises the stream for it.
+ *   poly_div_linear  for every root u_k (n_roots <= 3, repeats allowed): d_quotients[k] (len - 1 coefficients on the device, may not
+ *                    overlap d_coeffs) and remainders[k] (host) with  coeffs(X) = quotient_k(X) (X - u_k) + remainder_k,  one read of
+ *                    the coefficients for all roots.  d_quotients: a host array of n_roots device pointers (ignored when len == 1).
+ *                    len >= 1; the call synchronises the stream for the remainders. */
+int lurk_hip_mle_fold_pairs_dev(int field_id, const void* d_in, size_t len, const void* x32_mont, void* d_out, void* stream);
+int lurk_hip_poly_eval_dev(int field_id, const void* d_coeffs, size_t len, const void* points32_mont, int n_points, void* out32_mont, void* stream);
+int lurk_hip_poly_div_linear_dev(int field_id, const void* d_coeffs, size_t len, const void* roots32_mont, int n_roots, void* const* d_quotients,
+                                 void* remainders32_mont, void* stream);
+/* The opening argument itself: this repository's own statement of the published HyperKZG scheme, recalled [MEM], NOT byte-compatible
+ * with arecibo (tests/hyperkzg_ref.py restates it in Python integers).  key: a resident BN254 G1 key ck[0 .. N) - with a KZG SRS
+ * ck[i] = [tau^i]G, so G = ck[0]; any other curve is refused by name.  d_poly: n = 2^ell Montgomery Fr values on the device (ell >= 1,
+ * n <= N; not modified), the evaluations P_0 of a multilinear polynomial; x: ell Montgomery scalars on the host, x_0 <-> the most
+ * significant index bit (the convention of lurk_hip_eq_evals_dev).
+ *   P_{i+1}[j] = P_i[2j] + x_{ell-1-i} (P_i[2j+1] - P_i[2j]), i = 0 .. ell-2;  com_i = commit(P_i) under ck[0 .. len P_i), i = 1 .. ell-1;
+ *   y = the same fold of P_{ell-1} with x_0;  r = challenge(0, com_1 .. com_{ell-1}), r = 0 is refused;  u = (r, -r, r^2);
+ *   v[t][i] = P_i(u_t);  q = challenge(1, v);  B = sum_i q^i P_i (each P_i zero-padded to n);  h_t = (B - B(u_t)) / (X - u_t);
+ *   W_t = commit(h_t).
+ * The transcript is the caller's: `challenge` receives the stage, the stage's data (stage 0: count = ell - 1 Jacobians of 96 bytes;
+ * stage 1: count = 3 ell canonical scalars, t-major) and writes the challenge as a canonical 32-byte value below the group order
+ * (return 0; anything else aborts the call and leaves the key usable).  The verifier's third challenge d = challenge(2, W_0 .. W_2) is
+ * not needed by the prover and is not asked for.  Outputs (host): out_com (ell - 1) x 96 B Jacobians (may be NULL when ell = 1), out_v
+ * 3 ell x 32 B canonical (t-major), out_w 3 x 96 B, out_y 32 B canonical.  The call uses all LURK_MSM_SLOTS async slots of the key
+ * (com_{i+1} accumulates while fold i + 1 runs; the three W_t are in flight together) and about 5 n x 32 B of the stream's scratch arena. */
+typedef int (*lurk_hip_hyperkzg_challenge_fn)(void* user, int stage, const void* data, size_t count, void* out32_canonical);
+int lurk_hip_hyperkzg_prove_dev(lurk_hip_msm_ctx* key, const void* d_poly32_mont, size_t n, const void* x32_mont,
+                                lurk_hip_hyperkzg_challenge_fn challenge, void* user, void* out_com_jacobian96, void* out_v32, void* out_w_jacobian96,
+                                void* out_y32, void* stream);
+/* The verifier UP TO THE PAIRING (host code, no device needed; BN254 G1 only, any other curve is refused by name).  c = commit(P_0);
+ * x (ell), y, v (3 ell, t-major), r, q, d: canonical scalars - r, q, d as the caller's transcript gives them, d = challenge(2, W);
+ * com (ell - 1), w (3): 96-byte Jacobians.  Scalar checks, with Y_i = v[2][i] and Y_ell = y, for i = 0 .. ell-1:
+ *     2 r Y_{i+1} = r (1 - x_{ell-1-i}) (v[0][i] + v[1][i]) + x_{ell-1-i} (v[0][i] - v[1][i])
+ * then Bcom = sum_i q^i com_i (com_0 = c), b_t = sum_i q^i v[t][i], G = (1, 2) (= ck[0] of a powers-of-tau key) and
+ *     L = sum_t d^t (Bcom - [b_t] G + [u_t] W_t),   R = sum_t d^t W_t.
+ * The proof is valid iff e(L, H) = e(R, [tau] H): that pairing is the caller's (halo2curves, on the Rust side).  As with the verifiers
+ * below the call succeeds whatever its answer: *accepted = 1 (accepted SO FAR: L and R are the pairing's inputs) or 0 with
+ * *failed_check (may be NULL) = LURK_HYPERKZG_MALFORMED (a scalar not below the group order, r = 0, a point neither the identity nor
+ * on the curve) or LURK_HYPERKZG_FOLD (one of the scalar checks); L and R are then the identity. */
+#define LURK_HYPERKZG_ACCEPTED 0
+#define LURK_HYPERKZG_MALFORMED 1
+#define LURK_HYPERKZG_FOLD 2
+int lurk_hip_hyperkzg_pairing_inputs(int curve, int ell, const void* c_jacobian96, const void* x32_canonical, const void* y32_canonical,
+                                     const void* com_jacobian96, const void* v32_canonical, const void* w_jacobian96, const void* r32_canonical,
+                                     const void* q32_canonical, const void* d32_canonical, void* out_l_jacobian96, void* out_r_jacobian96,
+                                     int* accepted, int* failed_check);
+
 /* The single-instance compressing prover as ONE call (what CompressedSNARK::prove runs per curve: /root/reference/src/proof/nova.rs:341-356
  * -> arecibo RelaxedR1CSSNARK::prove): outer cubic sum-check, inner quadratic sum-check over the transposed shape, the two evaluation claims
  * batched to one point, one inner-product argument under the resident key - a sequence of the entry points above with the vectors resident
@@ -883,6 +938,11 @@ int lurk_hip_synth_scalars_dev(int field_id, uint64_t stream_id, int dist, size_
                                void* d_out32, int out_mont, void* stream);
 /* bases P_i = [k_i]G, k_i = uniform(stream 0, first+i) (0 -> 1); affine Montgomery, 64 B each */
 int lurk_hip_synth_bases_dev(int curve, size_t first, size_t n, void* d_out_affine64, void* stream);
+/* A powers-of-tau key for tests and benchmarks of the HyperKZG argument: d_out[i] = [tau^(first + i)] G on BN254 G1 (G = (1, 2)),
+ * affine Montgomery, from the same fixed-base tables.  tau: a canonical Fr value in host memory.  INSECURE BY CONSTRUCTION: whoever
+ * knows tau (the caller does) can open any commitment to anything - a trapdoor setup that makes a proof checkable without a pairing
+ * (L == [tau] R in G1), never a key to prove under.  Other curves are refused by name. */
+int lurk_hip_synth_kzg_bases_dev(int curve, const void* tau32_canonical, size_t first, size_t n, void* d_out_affine64, void* stream);
 
 #ifdef __cplusplus
 }

@@ -193,6 +193,12 @@ SIGNATURES = {
                                                   c_void_p]),
     "lurk_hip_synth_scalars_dev": (c_int, [c_int, c_u64, c_int, c_size_t, c_size_t, c_void_p, c_int, c_void_p]),
     "lurk_hip_synth_bases_dev": (c_int, [c_int, c_size_t, c_size_t, c_void_p, c_void_p]),
+    "lurk_hip_synth_kzg_bases_dev": (c_int, [c_int, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]),
+    "lurk_hip_mle_fold_pairs_dev": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "lurk_hip_poly_eval_dev": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p]),
+    "lurk_hip_poly_div_linear_dev": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_int, ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
+    "lurk_hip_hyperkzg_prove_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lurk_hip_hyperkzg_pairing_inputs": (c_int, [c_int, c_int] + [c_void_p] * 11 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
 }
 
 
@@ -302,3 +308,5 @@ IPA_CHALLENGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
 FOLD_SUBMIT_HOOK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)
 # lurk_hip_sumcheck_challenge_fn: int (*)(void* user, int round, const void* coefficients, void* out_r32_canonical)
 SUMCHECK_CHALLENGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
+# lurk_hip_hyperkzg_challenge_fn: int (*)(void* user, int stage, const void* data, size_t count, void* out32_canonical)
+HYPERKZG_CHALLENGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)

@@ -100,6 +100,29 @@ __global__ __launch_bounds__(256) void synth_bases_kernel(const Affine<P>* __res
     out[i] = xyzz_to_affine<P>(acc);
 }
 
+// powers of tau: out[i] = [tau^(first + i)] G - a KZG structured reference string with a KNOWN trapdoor (tests and benchmarks only).
+// A lane raises tau to its own index (<= 2 log2(index) products) and walks the fixed-base table like synth_bases_kernel.
+template <class P, class SF>
+__global__ __launch_bounds__(256) void synth_kzg_bases_kernel(const Affine<P>* __restrict__ tab, Fe<SF> tau_mont, size_t first, size_t n, Affine<P>* out) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t e = first + i;
+    Fe<SF> k = fe_one<SF>();
+    int top = 63;
+    while (top >= 0 && !((e >> top) & 1u)) top--;
+    for (int b = top; b >= 0; b--) {
+        k = fe_mul<SF>(k, k);
+        if ((e >> b) & 1u) k = fe_mul<SF>(k, tau_mont);
+    }
+    k = fe_from_mont<SF>(k);
+    Xyzz<P> acc = xyzz_identity<P>();
+    for (int j = 0; j < 32; j++) {
+        uint32_t d = (k.l[j >> 2] >> ((j & 3) * 8)) & 0xff;
+        if (d) xyzz_madd<P>(acc, tab[j * 256 + d], false);
+    }
+    out[i] = xyzz_to_affine<P>(acc);
+}
+
 static std::mutex g_tab_mu;
 static std::map<std::pair<int, int>, DevBuf> g_tab;  // (device, curve) -> table
 
@@ -162,6 +185,26 @@ int lurk_hip_synth_bases_dev(int curve, size_t first, size_t n, void* d_out, voi
             const Affine<Bn254Fr>* tab = get_table<Bn254Fr>(LURK_CURVE_GRUMPKIN, s);
             hipLaunchKernelGGL((synth_bases_kernel<Bn254Fr, Bn254Fq>), grid, block, 0, s, tab, first, n, (Affine<Bn254Fr>*)d_out);
         }
+        LURK_HIP_CHECK(hipGetLastError());
+    });
+}
+
+int lurk_hip_synth_kzg_bases_dev(int curve, const void* tau32_canonical, size_t first, size_t n, void* d_out, void* stream) {
+    return guarded([&] {
+        LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
+        if (curve != LURK_CURVE_BN254)
+            throw HipFailure{LURK_HIP_ERR_INVALID_ARG, std::string("lurk_hip_synth_kzg_bases_dev is offered on BN254 G1 only, not on ") + curve_name(curve)};
+        LURK_REQUIRE(tau32_canonical, "null argument");
+        Fe<Bn254Fr> tau;
+        memcpy(tau.l, tau32_canonical, 32);
+        LURK_REQUIRE(!fe_canonical_ge_mod<Bn254Fr>(tau.l), "tau is not reduced modulo the group order");
+        LURK_REQUIRE(first + n >= first, "index range overflows");
+        if (n == 0) return;
+        LURK_REQUIRE(d_out, "null buffer");
+        hipStream_t s = (hipStream_t)stream;
+        const Affine<Bn254Fq>* tab = get_table<Bn254Fq>(LURK_CURVE_BN254, s);
+        hipLaunchKernelGGL((synth_kzg_bases_kernel<Bn254Fq, Bn254Fr>), dim3(div_up(n, 256)), dim3(256), 0, s, tab, fe_to_mont<Bn254Fr>(tau), first, n,
+                           (Affine<Bn254Fq>*)d_out);
         LURK_HIP_CHECK(hipGetLastError());
     });
 }

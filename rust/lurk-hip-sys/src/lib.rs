@@ -9,6 +9,8 @@
 //! * [`store`]: `HipPoseidonCache` (the shape of `PoseidonCache<F>`), `HipStoreHasher` (the shape of `StoreHasher`,
 //!   `/root/reference/src/lem/store_core.rs:10-14`, layouts of `/root/reference/src/lem/store.rs:29-78`) and `hydrate`
 //!   (`hydrate_z_cache`, `store_core.rs:256-269`, as one level-batched call);
+//! * [`hyperkzg`]: the opening argument of the BN254 cycle (`EE1` of `Bn256EngineKZG`, `/root/reference/src/proof/nova.rs:65-71`): the prover
+//!   with the polynomial resident, the verifier up to the pairing (the pairing stays with the caller);
 //! * [`params`]: the run-time parameter blocks of the two restatements written from memory - Nova's random oracle
 //!   (`lurk_hip_ro_params`) and `from_label` (`lurk_hip_ck_params`) - so that the first run beside arecibo can move one field at a time
 //!   without rebuilding the library (callers: `/root/reference/src/proof/nova.rs:196-216, 282-295`);
@@ -19,6 +21,7 @@
 //! (see `rust/gen_sys.py`), the wrappers are a reading aid for the maintainer who wires the feature in.
 pub mod dump;
 pub mod ffi;
+pub mod hyperkzg;
 pub mod params;
 pub mod store;
 pub use ffi::*;
