@@ -71,11 +71,10 @@ int current_device();
 // More than 64 KB of dynamic LDS has to be requested per kernel and per device; done once for each pair.
 void allow_dynamic_lds(const void* kernel, int bytes);
 
-// Wraps the body of a C-ABI entry point: converts exceptions to error codes.
+// Wraps the body of a host-only C-ABI entry point: converts exceptions to error codes (nothing may unwind into the caller's frames).
 template <class F>
-int guarded(F&& f) {
+int host_guarded(F&& f) {
     try {
-        require_device();
         f();
         set_error(0, "");
         return 0;
@@ -86,6 +85,18 @@ int guarded(F&& f) {
         set_error(LURK_HIP_ERR_HIP, e.what());
         return LURK_HIP_ERR_HIP;
     }
+}
+// The same for an entry point that uses the device: fails loudly unless one is usable.
+template <class F>
+int guarded(F&& f) {
+    return host_guarded([&] {
+        require_device();
+        f();
+    });
+}
+// A nested C-ABI call failed: rethrow its code and message.
+inline void nested_ok(int rc) {
+    if (rc != 0) throw HipFailure{rc, lurk_hip_last_error()};
 }
 
 struct DevBuf {

@@ -716,7 +716,7 @@ LURK_HD Fe<P> fe_inv_pow(const Fe<P>& a) {
     return fe_pow<P>(a, e);
 }
 
-// canonical integer comparison helper: is the canonical value >= MOD ?
+// canonical integer comparison helper: is the canonical value >= MOD ?  (fe_read_canonical / fe_write_canonical, which throw, are in dispatch.hpp)
 template <class P>
 LURK_HD bool fe_canonical_ge_mod(const uint32_t* v) {
     for (int i = 7; i >= 0; i--) {

@@ -24,6 +24,7 @@
 #include <unordered_map>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "r1cs_shape.cuh"
 
 namespace lurk {
@@ -452,9 +453,7 @@ static void upload_matrix(R1csShape& sh, int which, const uint64_t* indptr, cons
             it = ids.emplace(key, id).first;
             dict_words.resize(dict_words.size() + P29_STRIDE);
             uint32_t* rec = dict_words.data() + (size_t)id * P29_STRIDE;
-            if (sh.field_id == 0) dict_record<PallasFp>(key.w, rec);
-            else if (sh.field_id == 1) dict_record<PallasFq>(key.w, rec);
-            else dict_record<Bn254Fr>(key.w, rec);
+            with_field(sh.field_id, [&](auto F) { dict_record<decltype(F)>(key.w, rec); });
         }
         ent[k] = make_uint2((uint32_t)indices[k], it->second);
     }
@@ -575,9 +574,11 @@ int lurk_hip_r1cs_create(lurk_hip_r1cs** out, int field_id, size_t num_cons, siz
             dict_words.resize(dict_words.size() + P29_STRIDE);
             uint32_t* rec = dict_words.data() + sh.dict_size * P29_STRIDE;
             uint64_t one[4];
-            if (field_id == 0) { Fe<PallasFp> o = fe_one<PallasFp>(); memcpy(one, o.l, 32); dict_record<PallasFp>(one, rec); }
-            else if (field_id == 1) { Fe<PallasFq> o = fe_one<PallasFq>(); memcpy(one, o.l, 32); dict_record<PallasFq>(one, rec); }
-            else { Fe<Bn254Fr> o = fe_one<Bn254Fr>(); memcpy(one, o.l, 32); dict_record<Bn254Fr>(one, rec); }
+            with_field(field_id, [&](auto F) {
+                Fe<decltype(F)> o = fe_one<decltype(F)>();
+                memcpy(one, o.l, 32);
+                dict_record<decltype(F)>(one, rec);
+            });
         }
         {   // rows the lane-per-row kernels leave to the wave-per-row ones
             std::vector<uint32_t> lr;
@@ -634,9 +635,7 @@ int lurk_hip_r1cs_multiply_vec_dev(const lurk_hip_r1cs* shape, const void* d_z, 
         LURK_REQUIRE(shape && d_z && d_az && d_bz && d_cz, "null argument");
         DeviceGuard dg(shape->sh.device);
         const R1csShape& sh = shape->sh;
-        if (sh.field_id == 0) multiply_vec<PallasFp>(sh, d_z, d_az, d_bz, d_cz, (hipStream_t)stream);
-        else if (sh.field_id == 1) multiply_vec<PallasFq>(sh, d_z, d_az, d_bz, d_cz, (hipStream_t)stream);
-        else multiply_vec<Bn254Fr>(sh, d_z, d_az, d_bz, d_cz, (hipStream_t)stream);
+        with_field(sh.field_id, [&](auto F) { multiply_vec<decltype(F)>(sh, d_z, d_az, d_bz, d_cz, (hipStream_t)stream); });
     });
 }
 
@@ -645,9 +644,7 @@ int lurk_hip_r1cs_cross_term_dev(lurk_hip_r1cs* shape, const void* d_z1, const v
         LURK_REQUIRE(shape && d_z1 && d_z2 && d_t, "null argument");
         DeviceGuard dg(shape->sh.device);
         const R1csShape& sh = shape->sh;
-        if (sh.field_id == 0) cross_term<PallasFp>(sh, d_z1, d_z2, d_t, (hipStream_t)stream);
-        else if (sh.field_id == 1) cross_term<PallasFq>(sh, d_z1, d_z2, d_t, (hipStream_t)stream);
-        else cross_term<Bn254Fr>(sh, d_z1, d_z2, d_t, (hipStream_t)stream);
+        with_field(sh.field_id, [&](auto F) { cross_term<decltype(F)>(sh, d_z1, d_z2, d_t, (hipStream_t)stream); });
     });
 }
 
@@ -661,12 +658,10 @@ int lurk_hip_r1cs_cross_term_cached_dev(lurk_hip_r1cs* shape, const void* d_z2, 
         LURK_REQUIRE(!prev || (d_az2_prev != d_az2 && d_bz2_prev != d_bz2 && d_cz2_prev != d_cz2), "the previous products are read while the new ones are written: two buffers");
         DeviceGuard dg(shape->sh.device);
         const R1csShape& sh = shape->sh;
-        if (sh.field_id == 0)
-            cross_term_cached<PallasFp>(sh, d_z2, d_az1, d_bz1, d_cz1, u1_32_mont, d_az2_prev, d_bz2_prev, d_cz2_prev, r_prev32_mont, d_t, d_az2, d_bz2, d_cz2, (hipStream_t)stream);
-        else if (sh.field_id == 1)
-            cross_term_cached<PallasFq>(sh, d_z2, d_az1, d_bz1, d_cz1, u1_32_mont, d_az2_prev, d_bz2_prev, d_cz2_prev, r_prev32_mont, d_t, d_az2, d_bz2, d_cz2, (hipStream_t)stream);
-        else
-            cross_term_cached<Bn254Fr>(sh, d_z2, d_az1, d_bz1, d_cz1, u1_32_mont, d_az2_prev, d_bz2_prev, d_cz2_prev, r_prev32_mont, d_t, d_az2, d_bz2, d_cz2, (hipStream_t)stream);
+        with_field(sh.field_id, [&](auto F) {
+            cross_term_cached<decltype(F)>(sh, d_z2, d_az1, d_bz1, d_cz1, u1_32_mont, d_az2_prev, d_bz2_prev, d_cz2_prev, r_prev32_mont, d_t, d_az2, d_bz2, d_cz2,
+                                           (hipStream_t)stream);
+        });
     });
 }
 
@@ -683,9 +678,7 @@ int lurk_hip_fold_vecs_dev(int field_id, int count, const void* const* d_a, cons
             blocks += div_up(n[k], (size_t)FOLD_BLOCK * FOLD_VEC_E);
         }
         LURK_REQUIRE(blocks < ((size_t)1 << 31), "too many elements for one launch");
-        if (field_id == 0) fold_vecs<PallasFp>(count, d_a, d_b, n, d_out, r32_mont, (hipStream_t)stream);
-        else if (field_id == 1) fold_vecs<PallasFq>(count, d_a, d_b, n, d_out, r32_mont, (hipStream_t)stream);
-        else fold_vecs<Bn254Fr>(count, d_a, d_b, n, d_out, r32_mont, (hipStream_t)stream);
+        with_field(field_id, [&](auto F) { fold_vecs<decltype(F)>(count, d_a, d_b, n, d_out, r32_mont, (hipStream_t)stream); });
     });
 }
 
@@ -740,9 +733,7 @@ int lurk_hip_fold_vec_dev(int field_id, const void* d_a, const void* d_b, const 
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
         LURK_REQUIRE(n == 0 || (d_a && d_b && d_out), "null buffer");
         LURK_REQUIRE(r32_mont, "null challenge");
-        if (field_id == 0) fold_vec<PallasFp>(d_a, d_b, r32_mont, n, d_out, (hipStream_t)stream);
-        else if (field_id == 1) fold_vec<PallasFq>(d_a, d_b, r32_mont, n, d_out, (hipStream_t)stream);
-        else fold_vec<Bn254Fr>(d_a, d_b, r32_mont, n, d_out, (hipStream_t)stream);
+        with_field(field_id, [&](auto F) { fold_vec<decltype(F)>(d_a, d_b, r32_mont, n, d_out, (hipStream_t)stream); });
     });
 }
 

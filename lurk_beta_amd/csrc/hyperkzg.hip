@@ -18,6 +18,7 @@
 
 #include "common.hpp"
 #include "curve.cuh"
+#include "dispatch.hpp"
 
 namespace lurk {
 
@@ -342,19 +343,6 @@ static void hk_div_linear(const void* d_b, size_t len, const Fe<F>* roots, int n
     LURK_HIP_CHECK(hipGetLastError());
 }
 
-template <class F>
-static Fe<F> hk_read_canonical(const void* p32, const char* what) {
-    Fe<F> v;
-    memcpy(v.l, p32, 32);
-    if (fe_canonical_ge_mod<F>(v.l)) throw HipFailure{LURK_HIP_ERR_INVALID_ARG, std::string(what) + " is not reduced modulo the field order"};
-    return fe_to_mont<F>(v);
-}
-template <class F>
-static void hk_write_canonical(void* out32, const Fe<F>& mont) {
-    const Fe<F> c = fe_from_mont<F>(mont);
-    memcpy(out32, c.l, 32);
-}
-
 // ---- the prover ------------------------------------------------------------------------------------------------------------------------
 // Commitments stay in flight through the key's async slots: com_{i+1} is submitted behind fold i and accumulates while fold i + 1 (and
 // the ones after it) run on the caller's stream; a slot is waited for only when the loop comes round to it again.  The three W_t take
@@ -362,7 +350,6 @@ static void hk_write_canonical(void* out32, const Fe<F>& mont) {
 template <class F>
 static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, int ell, const void* x32_mont, lurk_hip_hyperkzg_challenge_fn challenge, void* user,
                            uint64_t* out_com, uint64_t* out_v, uint64_t* out_w, void* out_y, hipStream_t s) {
-    auto ok = [](int rc) { if (rc != 0) throw HipFailure{rc, lurk_hip_last_error()}; };
     std::vector<Fe<F>> x(ell);
     memcpy((void*)x.data(), x32_mont, (size_t)ell * 32);
     stream_pool_retain();
@@ -390,9 +377,9 @@ static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, 
         if (drain.pending[slot] >= 0) {
             const long which = drain.pending[slot];
             drain.pending[slot] = -1;
-            ok(lurk_hip_msm_ctx_wait(key, slot, out_com + 12 * which));
+            nested_ok(lurk_hip_msm_ctx_wait(key, slot, out_com + 12 * which));
         }
-        ok(lurk_hip_msm_ctx_submit_dev(key, slot, nxt, len, 1, (void*)s));
+        nested_ok(lurk_hip_msm_ctx_submit_dev(key, slot, nxt, len, 1, (void*)s));
         drain.pending[slot] = i;
         cur = nxt;
     }
@@ -400,17 +387,17 @@ static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, 
     LURK_HIP_CHECK(hipMemcpyAsync(tail, cur, 64, hipMemcpyDeviceToHost, s));
     LURK_HIP_CHECK(hipStreamSynchronize(s));
     const Fe<F> y = fe_add<F>(tail[0], fe_mul<F>(x[0], fe_sub<F>(tail[1], tail[0])));
-    hk_write_canonical<F>(out_y, y);
+    fe_write_canonical<F>(out_y, y);
     for (int k = 0; k < LURK_MSM_SLOTS; k++) {
         if (drain.pending[k] < 0) continue;
         const long which = drain.pending[k];
         drain.pending[k] = -1;
-        ok(lurk_hip_msm_ctx_wait(key, k, out_com + 12 * which));
+        nested_ok(lurk_hip_msm_ctx_wait(key, k, out_com + 12 * which));
     }
     // stage 0: r from the commitments
     uint64_t ch[4] = {0, 0, 0, 0};
     LURK_REQUIRE(challenge(user, 0, out_com, (size_t)(ell - 1), ch) == 0, "the transcript callback failed");
-    const Fe<F> r = hk_read_canonical<F>(ch, "the challenge");
+    const Fe<F> r = fe_read_canonical<F>(ch, "the challenge");
     LURK_REQUIRE(!fe_is_zero<F>(r), "zero challenge");
     const Fe<F> u[3] = {r, fe_neg<F>(r), fe_mul<F>(r, r)};
     // evaluations: P_0 alone, then P_1 .. P_{ell-1} out of the one buffer
@@ -431,11 +418,11 @@ static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, 
     LURK_HIP_CHECK(hipMemcpyAsync((void*)v.data(), d_v, (size_t)3 * ell * 32, hipMemcpyDeviceToHost, s));
     LURK_HIP_CHECK(hipStreamSynchronize(s));
     for (int t = 0; t < 3; t++)
-        for (int i = 0; i < ell; i++) hk_write_canonical<F>(out_v + 4 * ((size_t)t * ell + i), v[(size_t)i * 3 + t]);
+        for (int i = 0; i < ell; i++) fe_write_canonical<F>(out_v + 4 * ((size_t)t * ell + i), v[(size_t)i * 3 + t]);
     // stage 1: q from the evaluations
     ch[0] = ch[1] = ch[2] = ch[3] = 0;
     LURK_REQUIRE(challenge(user, 1, out_v, (size_t)3 * ell, ch) == 0, "the transcript callback failed");
-    const Fe<F> q = hk_read_canonical<F>(ch, "the challenge");
+    const Fe<F> q = fe_read_canonical<F>(ch, "the challenge");
     {
         ProfScope ps("hkzg_batch", s);
         hipLaunchKernelGGL((hk_batch_kernel<F>), dim3(hk_grid(n)), dim3(HK_BLOCK), 0, s, (const Fe<F>*)d_poly, (const Fe<F>*)d_rest, n, ell, q, (Fe<F>*)bpoly.p);
@@ -445,7 +432,7 @@ static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, 
     Fe<F>* d_rem = d_v + (size_t)3 * HK_MAX_POLYS;
     hk_div_linear<F>(bpoly.p, n, u, 3, d_q, d_rem, s);
     for (int t = 0; t < 3; t++) {
-        ok(lurk_hip_msm_ctx_submit_dev(key, t, d_q[t], n - 1, 1, (void*)s));
+        nested_ok(lurk_hip_msm_ctx_submit_dev(key, t, d_q[t], n - 1, 1, (void*)s));
         drain.pending[t] = t;
     }
     Fe<F> rem[3];
@@ -458,26 +445,11 @@ static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, 
     }
     for (int t = 0; t < 3; t++) {
         drain.pending[t] = -1;
-        ok(lurk_hip_msm_ctx_wait(key, t, out_w + 12 * t));
+        nested_ok(lurk_hip_msm_ctx_wait(key, t, out_w + 12 * t));
     }
 }
 
 // ---- the verifier up to the pairing (host only) ------------------------------------------------------------------------------------------
-template <class Fn>
-static int hk_host_guarded(Fn&& f) {
-    try {
-        f();
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    } catch (const std::exception& e) {
-        set_error(LURK_HIP_ERR_HIP, e.what());
-        return LURK_HIP_ERR_HIP;
-    }
-}
-
 // a 96-byte Jacobian of BN254 G1 (Montgomery): reduced coordinates, and the identity (z = 0) or y^2 = x^3 + 3 z^6
 static bool hk_point_ok(const void* p96) {
     using P = Bn254Fq;
@@ -494,7 +466,6 @@ static void hyperkzg_pairing_inputs(int ell, const void* c96, const void* x32, c
                                     const void* q32, const void* d32, void* out_l, void* out_r, int* accepted, int* failed) {
     using F = Bn254Fr;
     const int curve = LURK_CURVE_BN254;
-    auto ok = [](int rc) { if (rc != 0) throw HipFailure{rc, lurk_hip_last_error()}; };
     auto reject = [&](int code) {
         memset(out_l, 0, 96);
         memset(out_r, 0, 96);
@@ -513,11 +484,11 @@ static void hyperkzg_pairing_inputs(int ell, const void* c96, const void* x32, c
     for (int i = 0; wf && i + 1 < ell; i++) wf = hk_point_ok(com + 12 * i);
     for (int t = 0; wf && t < 3; t++) wf = hk_point_ok(w + 12 * t);
     if (!wf) return reject(LURK_HYPERKZG_MALFORMED);
-    const Fe<F> r = hk_read_canonical<F>(r32, "r"), q = hk_read_canonical<F>(q32, "q"), d = hk_read_canonical<F>(d32, "d"), y = hk_read_canonical<F>(y32, "y");
+    const Fe<F> r = fe_read_canonical<F>(r32, "r"), q = fe_read_canonical<F>(q32, "q"), d = fe_read_canonical<F>(d32, "d"), y = fe_read_canonical<F>(y32, "y");
     if (fe_is_zero<F>(r)) return reject(LURK_HYPERKZG_MALFORMED);
     std::vector<Fe<F>> x(ell), v((size_t)3 * ell);
-    for (int i = 0; i < ell; i++) x[i] = hk_read_canonical<F>((const char*)x32 + 32 * i, "x");
-    for (int i = 0; i < 3 * ell; i++) v[i] = hk_read_canonical<F>(v32 + 4 * i, "v");
+    for (int i = 0; i < ell; i++) x[i] = fe_read_canonical<F>((const char*)x32 + 32 * i, "x");
+    for (int i = 0; i < 3 * ell; i++) v[i] = fe_read_canonical<F>(v32 + 4 * i, "v");
     const Fe<F> one = fe_one<F>(), two_r = fe_dbl<F>(r);
     // 2 r Y_{i+1} = r (1 - x_{ell-1-i}) (v[0][i] + v[1][i]) + x_{ell-1-i} (v[0][i] - v[1][i]),  Y_i = v[2][i], Y_ell = y
     for (int i = 0; i < ell; i++) {
@@ -533,12 +504,12 @@ static void hyperkzg_pairing_inputs(int ell, const void* c96, const void* x32, c
     Fe<F> qp = one;
     for (int i = 0; i < ell; i++) {
         uint64_t sc[4];
-        hk_write_canonical<F>(sc, qp);
-        ok(lurk_hip_point_mul(curve, pts.data() + 12 * i, i == 0 ? c96 : (const void*)(com + 12 * (i - 1)), sc, 0));
+        fe_write_canonical<F>(sc, qp);
+        nested_ok(lurk_hip_point_mul(curve, pts.data() + 12 * i, i == 0 ? c96 : (const void*)(com + 12 * (i - 1)), sc, 0));
         qp = fe_mul<F>(qp, q);
     }
     uint64_t bcom[12];
-    ok(lurk_hip_point_sum(curve, bcom, pts.data(), ell));
+    nested_ok(lurk_hip_point_sum(curve, bcom, pts.data(), ell));
     Fe<F> bsum = fe_zero<F>();
     for (int t = 0; t < 3; t++) {
         Fe<F> bt = fe_zero<F>();
@@ -550,20 +521,20 @@ static void hyperkzg_pairing_inputs(int ell, const void* c96, const void* x32, c
     g.y = fe_dbl<Bn254Fq>(fe_one<Bn254Fq>());
     g.z = fe_one<Bn254Fq>();
     uint64_t sc[4];
-    hk_write_canonical<F>(sc, fe_add<F>(fe_add<F>(dp[0], dp[1]), dp[2]));
-    ok(lurk_hip_point_mul(curve, pts.data(), bcom, sc, 0));
-    hk_write_canonical<F>(sc, fe_neg<F>(bsum));
-    ok(lurk_hip_point_mul(curve, pts.data() + 12, &g, sc, 0));
+    fe_write_canonical<F>(sc, fe_add<F>(fe_add<F>(dp[0], dp[1]), dp[2]));
+    nested_ok(lurk_hip_point_mul(curve, pts.data(), bcom, sc, 0));
+    fe_write_canonical<F>(sc, fe_neg<F>(bsum));
+    nested_ok(lurk_hip_point_mul(curve, pts.data() + 12, &g, sc, 0));
     for (int t = 0; t < 3; t++) {
-        hk_write_canonical<F>(sc, fe_mul<F>(dp[t], u[t]));
-        ok(lurk_hip_point_mul(curve, pts.data() + 12 * (2 + t), w + 12 * t, sc, 0));
+        fe_write_canonical<F>(sc, fe_mul<F>(dp[t], u[t]));
+        nested_ok(lurk_hip_point_mul(curve, pts.data() + 12 * (2 + t), w + 12 * t, sc, 0));
     }
-    ok(lurk_hip_point_sum(curve, out_l, pts.data(), 5));
+    nested_ok(lurk_hip_point_sum(curve, out_l, pts.data(), 5));
     for (int t = 0; t < 3; t++) {
-        hk_write_canonical<F>(sc, dp[t]);
-        ok(lurk_hip_point_mul(curve, pts.data() + 12 * t, w + 12 * t, sc, 0));
+        fe_write_canonical<F>(sc, dp[t]);
+        nested_ok(lurk_hip_point_mul(curve, pts.data() + 12 * t, w + 12 * t, sc, 0));
     }
-    ok(lurk_hip_point_sum(curve, out_r, pts.data(), 3));
+    nested_ok(lurk_hip_point_sum(curve, out_r, pts.data(), 3));
     *accepted = 1;
     if (failed) *failed = LURK_HYPERKZG_ACCEPTED;
 }
@@ -571,13 +542,6 @@ static void hyperkzg_pairing_inputs(int ell, const void* c96, const void* x32, c
 }  // namespace lurk
 
 using namespace lurk;
-
-#define HK_FIELD_DISPATCH(field_id, ...)                             \
-    do {                                                             \
-        if ((field_id) == 0) { using F = PallasFp; __VA_ARGS__; }    \
-        else if ((field_id) == 1) { using F = PallasFq; __VA_ARGS__; } \
-        else { using F = Bn254Fr; __VA_ARGS__; }                     \
-    } while (0)
 
 extern "C" {
 
@@ -588,7 +552,8 @@ int lurk_hip_mle_fold_pairs_dev(int field_id, const void* d_in, size_t len, cons
         LURK_REQUIRE(d_in && d_out && x32_mont, "null argument");
         const size_t half = (len + 1) / 2;
         LURK_REQUIRE((const char*)d_out + half * 32 <= (const char*)d_in || (const char*)d_in + len * 32 <= (const char*)d_out, "the output may not alias the input");
-        HK_FIELD_DISPATCH(field_id, {
+        with_field(field_id, [&](auto tag) {
+            using F = decltype(tag);
             Fe<F> x;
             memcpy(x.l, x32_mont, 32);
             hk_fold_pairs<F>(d_in, len, x, d_out, (hipStream_t)stream);
@@ -602,7 +567,8 @@ int lurk_hip_poly_eval_dev(int field_id, const void* d_coeffs, size_t len, const
         LURK_REQUIRE(n_points >= 1 && n_points <= HK_MAX_POINTS, "1 to 4 evaluation points");
         LURK_REQUIRE(points32_mont && out32_mont && (len == 0 || d_coeffs), "null argument");
         hipStream_t s = (hipStream_t)stream;
-        HK_FIELD_DISPATCH(field_id, {
+        with_field(field_id, [&](auto tag) {
+            using F = decltype(tag);
             Fe<F> pts[HK_MAX_POINTS];
             memcpy((void*)pts, points32_mont, (size_t)n_points * 32);
             ArenaBuf d_out(HK_MAX_POINTS * 32, s);
@@ -628,7 +594,8 @@ int lurk_hip_poly_div_linear_dev(int field_id, const void* d_coeffs, size_t len,
             LURK_REQUIRE(q + (len - 1) * 32 <= b || b + len * 32 <= q, "a quotient may not alias the input");
         }
         hipStream_t s = (hipStream_t)stream;
-        HK_FIELD_DISPATCH(field_id, {
+        with_field(field_id, [&](auto tag) {
+            using F = decltype(tag);
             Fe<F> roots[HK_MAX_ROOTS];
             memcpy((void*)roots, roots32_mont, (size_t)n_roots * 32);
             void* none[HK_MAX_ROOTS] = {nullptr, nullptr, nullptr};
@@ -665,7 +632,7 @@ int lurk_hip_hyperkzg_prove_dev(lurk_hip_msm_ctx* key, const void* d_poly32_mont
 int lurk_hip_hyperkzg_pairing_inputs(int curve, int ell, const void* c_jacobian96, const void* x32_canonical, const void* y32_canonical, const void* com_jacobian96,
                                      const void* v32_canonical, const void* w_jacobian96, const void* r32_canonical, const void* q32_canonical,
                                      const void* d32_canonical, void* out_l_jacobian96, void* out_r_jacobian96, int* accepted, int* failed_check) {
-    return hk_host_guarded([&] {
+    return host_guarded([&] {
         if (curve != LURK_CURVE_BN254) {
             if (curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN)
                 throw HipFailure{LURK_HIP_ERR_INVALID_ARG, std::string("lurk_hip_hyperkzg_pairing_inputs is offered on BN254 G1 only, not on ") + curve_name(curve)};

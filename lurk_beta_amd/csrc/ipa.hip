@@ -19,6 +19,7 @@
 #include "common.hpp"
 #include "curve.cuh"
 #include "curve29.cuh"
+#include "dispatch.hpp"
 #include "msm_core.cuh"
 #include "keyfold_plan.hpp"
 
@@ -149,9 +150,8 @@ template <class F>
 static Scalar256 canonical_scalar(const void* s32_mont) {
     Fe<F> s;
     memcpy(s.l, s32_mont, 32);
-    s = fe_from_mont<F>(s);
     Scalar256 k;
-    for (int i = 0; i < 8; i++) k.w[i] = s.l[i];
+    fe_write_canonical<F>(k.w, s);
     return k;
 }
 static int top_bit_of(const Scalar256& a, const Scalar256& b) {
@@ -375,11 +375,10 @@ template <class P, class F>
 static void ipa_prove_resident(lurk_hip_msm_ctx* key, int curve, int field_id, void* d_a, void* d_b, size_t n0, const void* ck_c_jac96,
                                lurk_hip_ipa_challenge_fn challenge, void* user, uint64_t* out_l, uint64_t* out_r, void* out_a_hat32,
                                void* out_ck_hat64, hipStream_t s, int round0 = 0) {
-    auto ok = [](int rc) { if (rc != 0) throw HipFailure{rc, lurk_hip_last_error()}; };
     int kc = 0, kbits = 0, ktable = 0;
     size_t kn = 0;
-    ok(lurk_hip_msm_ctx_info(key, &kc, &kn, &kbits, nullptr));
-    ok(lurk_hip_msm_ctx_form(key, &ktable));
+    nested_ok(lurk_hip_msm_ctx_info(key, &kc, &kn, &kbits, nullptr));
+    nested_ok(lurk_hip_msm_ctx_form(key, &ktable));
     LURK_REQUIRE(kc == curve, "the key is over another curve");
     LURK_REQUIRE(kn >= n0, "the key has fewer points than the vectors have elements");
     const bool pairs = ktable == LURK_MSM_FORM_TABLE;  // the window-table form commits L and R (disjoint supports) in one pass
@@ -430,12 +429,12 @@ static void ipa_prove_resident(lurk_hip_msm_ctx* key, int curve, int field_id, v
             }
         } drain{key, pairs};
         if (pairs) {
-            ok(lurk_hip_msm_ctx_submit_pair_dev(key, 0, dl.p, n0, 1, (void*)s, log_h));  // bit log2(m / 2) of the index set: L's support
+            nested_ok(lurk_hip_msm_ctx_submit_pair_dev(key, 0, dl.p, n0, 1, (void*)s, log_h));  // bit log2(m / 2) of the index set: L's support
             drain.pending = 1;
         } else {
-            ok(lurk_hip_msm_ctx_submit_dev_mode(key, 0, dl.p, n0, 1, (void*)s, LURK_MSM_SUBMIT_FOREGROUND));
+            nested_ok(lurk_hip_msm_ctx_submit_dev_mode(key, 0, dl.p, n0, 1, (void*)s, LURK_MSM_SUBMIT_FOREGROUND));
             drain.pending = 1;
-            ok(lurk_hip_msm_ctx_submit_dev_mode(key, 1, dr.p, n0, 1, (void*)s, LURK_MSM_SUBMIT_FOREGROUND));
+            nested_ok(lurk_hip_msm_ctx_submit_dev_mode(key, 1, dr.p, n0, 1, (void*)s, LURK_MSM_SUBMIT_FOREGROUND));
             drain.pending = 2;
         }
         unsigned blocks = div_up(h, IPA_BLOCK);
@@ -456,8 +455,8 @@ static void ipa_prove_resident(lurk_hip_msm_ctx* key, int curve, int field_id, v
         uint64_t* L = out_l + (size_t)12 * j;
         uint64_t* R = out_r + (size_t)12 * j;
         uint64_t tl[12], tr[12];
-        ok(lurk_hip_point_mul(curve, tl, ck_c_jac96, cl.l, 1));  // two 255-bit host scalar multiples, under the commitment
-        ok(lurk_hip_point_mul(curve, tr, ck_c_jac96, cr.l, 1));
+        nested_ok(lurk_hip_point_mul(curve, tl, ck_c_jac96, cl.l, 1));  // two 255-bit host scalar multiples, under the commitment
+        nested_ok(lurk_hip_point_mul(curve, tr, ck_c_jac96, cr.l, 1));
         if (pairs) {
             // the commitments arrive as XYZZ points, take the multiples of the extra base and leave normalised through ONE inversion
             drain.pending = 0;
@@ -477,16 +476,16 @@ static void ipa_prove_resident(lurk_hip_msm_ctx* key, int curve, int field_id, v
         } else {
             drain.pending = 0;
             const int rc0 = lurk_hip_msm_ctx_wait(key, 0, c_l), rc1 = lurk_hip_msm_ctx_wait(key, 1, c_r);
-            ok(rc0);
-            ok(rc1);
+            nested_ok(rc0);
+            nested_ok(rc1);
         }
         if (!pairs) {
             memcpy(two, c_l, 96);
             memcpy(two + 12, tl, 96);
-            ok(lurk_hip_point_sum(curve, L, two, 2));
+            nested_ok(lurk_hip_point_sum(curve, L, two, 2));
             memcpy(two, c_r, 96);
             memcpy(two + 12, tr, 96);
-            ok(lurk_hip_point_sum(curve, R, two, 2));
+            nested_ok(lurk_hip_point_sum(curve, R, two, 2));
         }
         uint64_t r_can[4] = {0, 0, 0, 0};
         LURK_REQUIRE(challenge(user, round0 + j, L, R, r_can) == 0, "the transcript callback failed");
@@ -504,7 +503,7 @@ static void ipa_prove_resident(lurk_hip_msm_ctx* key, int curve, int field_id, v
     }
     // the final key element is the commitment of the coefficient vector (the verifier's s vector)
     uint64_t ck_hat[12];
-    ok(lurk_hip_msm_ctx_run_dev(key, ck_hat, coef.p, n0, 1, (void*)s));
+    nested_ok(lurk_hip_msm_ctx_run_dev(key, ck_hat, coef.p, n0, 1, (void*)s));
     Jacobian<P> jp;
     memcpy(&jp, ck_hat, 96);
     const Affine<P> aff = xyzz_to_affine<P>(xyzz_from_jacobian<P>(jp));  // Montgomery coordinates, (0, 0) for the identity
@@ -526,9 +525,7 @@ int lurk_hip_inner_product_dev(int field_id, const void* d_a, const void* d_b, s
     return guarded([&] {
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
         LURK_REQUIRE(out32_mont && (n == 0 || (d_a && d_b)), "null argument");
-        if (field_id == 0) inner_product<PallasFp>(d_a, d_b, n, out32_mont, (hipStream_t)stream);
-        else if (field_id == 1) inner_product<PallasFq>(d_a, d_b, n, out32_mont, (hipStream_t)stream);
-        else inner_product<Bn254Fr>(d_a, d_b, n, out32_mont, (hipStream_t)stream);
+        with_field(field_id, [&](auto F) { inner_product<decltype(F)>(d_a, d_b, n, out32_mont, (hipStream_t)stream); });
     });
 }
 
@@ -537,9 +534,7 @@ int lurk_hip_fold_halves_dev(int field_id, void* d_v, size_t len, const void* s_
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
         LURK_REQUIRE(len >= 2 && len % 2 == 0, "length must be even and >= 2");
         LURK_REQUIRE(d_v && s_lo32_mont && s_hi32_mont, "null argument");
-        if (field_id == 0) fold_halves<PallasFp>(d_v, len, s_lo32_mont, s_hi32_mont, (hipStream_t)stream);
-        else if (field_id == 1) fold_halves<PallasFq>(d_v, len, s_lo32_mont, s_hi32_mont, (hipStream_t)stream);
-        else fold_halves<Bn254Fr>(d_v, len, s_lo32_mont, s_hi32_mont, (hipStream_t)stream);
+        with_field(field_id, [&](auto F) { fold_halves<decltype(F)>(d_v, len, s_lo32_mont, s_hi32_mont, (hipStream_t)stream); });
     });
 }
 
@@ -548,9 +543,7 @@ int lurk_hip_ipa_round_scalars_dev(int field_id, const void* d_a, size_t m, cons
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
         LURK_REQUIRE(m >= 2 && (m & (m - 1)) == 0 && n >= m && n % m == 0, "m must be a power of two >= 2 that divides n");
         LURK_REQUIRE(d_a && d_coef && d_out_l, "null argument");  // d_out_r == NULL: the merged form
-        if (field_id == 0) ipa_round_scalars<PallasFp>(d_a, m, d_coef, n, d_out_l, d_out_r, (hipStream_t)stream);
-        else if (field_id == 1) ipa_round_scalars<PallasFq>(d_a, m, d_coef, n, d_out_l, d_out_r, (hipStream_t)stream);
-        else ipa_round_scalars<Bn254Fr>(d_a, m, d_coef, n, d_out_l, d_out_r, (hipStream_t)stream);
+        with_field(field_id, [&](auto F) { ipa_round_scalars<decltype(F)>(d_a, m, d_coef, n, d_out_l, d_out_r, (hipStream_t)stream); });
     });
 }
 
@@ -559,9 +552,7 @@ int lurk_hip_ipa_coef_fold_dev(int field_id, void* d_coef, size_t n, size_t m, c
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
         LURK_REQUIRE(m >= 2 && (m & (m - 1)) == 0 && n >= m && n % m == 0, "m must be a power of two >= 2 that divides n");
         LURK_REQUIRE(d_coef && s_lo32_mont && s_hi32_mont, "null argument");
-        if (field_id == 0) ipa_coef_fold<PallasFp>(d_coef, n, m, s_lo32_mont, s_hi32_mont, (hipStream_t)stream);
-        else if (field_id == 1) ipa_coef_fold<PallasFq>(d_coef, n, m, s_lo32_mont, s_hi32_mont, (hipStream_t)stream);
-        else ipa_coef_fold<Bn254Fr>(d_coef, n, m, s_lo32_mont, s_hi32_mont, (hipStream_t)stream);
+        with_field(field_id, [&](auto F) { ipa_coef_fold<decltype(F)>(d_coef, n, m, s_lo32_mont, s_hi32_mont, (hipStream_t)stream); });
     });
 }
 
@@ -577,12 +568,12 @@ int lurk_hip_ipa_prove_dev(lurk_hip_msm_ctx* key, void* d_a, void* d_b, size_t n
             throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
         require_pasta_curve(curve, "lurk_hip_ipa_prove_dev");
         DeviceGuard dg(device);
-        if (curve == LURK_CURVE_PALLAS)
-            ipa_prove_resident<PallasFp, PallasFq>(key, curve, LURK_FIELD_PALLAS_FQ, d_a, d_b, n, ck_c_jacobian96, challenge, user, (uint64_t*)out_l_jacobian96,
-                                                   (uint64_t*)out_r_jacobian96, out_a_hat32, out_ck_hat_affine64, (hipStream_t)stream);
-        else
-            ipa_prove_resident<PallasFq, PallasFp>(key, curve, LURK_FIELD_PALLAS_FP, d_a, d_b, n, ck_c_jacobian96, challenge, user, (uint64_t*)out_l_jacobian96,
-                                                   (uint64_t*)out_r_jacobian96, out_a_hat32, out_ck_hat_affine64, (hipStream_t)stream);
+        with_pasta_curve(curve, [&](auto base, auto scalar) {
+            using P = decltype(base);
+            using F = decltype(scalar);
+            ipa_prove_resident<P, F>(key, curve, F::ID, d_a, d_b, n, ck_c_jacobian96, challenge, user, (uint64_t*)out_l_jacobian96, (uint64_t*)out_r_jacobian96, out_a_hat32,
+                                     out_ck_hat_affine64, (hipStream_t)stream);
+        });
     });
 }
 
@@ -592,8 +583,7 @@ int lurk_hip_msm_ctx_fold_key_dev(lurk_hip_msm_ctx* key, size_t n, const void* w
         const MsmTableView v = msm_ctx_table_view(key);
         require_pasta_curve(v.curve, "lurk_hip_msm_ctx_fold_key_dev");
         DeviceGuard dg(v.device);
-        if (v.curve == LURK_CURVE_PALLAS) key_fold<PallasFp, PallasFq>(v, n, weights32_mont, n_weights, d_out_affine64, (hipStream_t)stream);
-        else key_fold<PallasFq, PallasFp>(v, n, weights32_mont, n_weights, d_out_affine64, (hipStream_t)stream);
+        with_pasta_curve(v.curve, [&](auto P, auto F) { key_fold<decltype(P), decltype(F)>(v, n, weights32_mont, n_weights, d_out_affine64, (hipStream_t)stream); });
     });
 }
 
@@ -603,8 +593,9 @@ int lurk_hip_points_fold_halves_dev(int curve, const void* d_points_affine64, si
         require_pasta_curve(curve, "lurk_hip_points_fold_halves_dev");
         LURK_REQUIRE(len >= 2 && len % 2 == 0, "length must be even and >= 2");
         LURK_REQUIRE(d_points_affine64 && d_out_affine64 && s_lo32_mont && s_hi32_mont, "null argument");
-        if (curve == LURK_CURVE_PALLAS) points_fold_halves<PallasFp, PallasFq>(d_points_affine64, len, s_lo32_mont, s_hi32_mont, d_out_affine64, (hipStream_t)stream);
-        else points_fold_halves<PallasFq, PallasFp>(d_points_affine64, len, s_lo32_mont, s_hi32_mont, d_out_affine64, (hipStream_t)stream);
+        with_pasta_curve(curve, [&](auto P, auto F) {
+            points_fold_halves<decltype(P), decltype(F)>(d_points_affine64, len, s_lo32_mont, s_hi32_mont, d_out_affine64, (hipStream_t)stream);
+        });
     });
 }
 }

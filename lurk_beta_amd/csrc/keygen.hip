@@ -15,6 +15,7 @@
 
 #include "common.hpp"
 #include "curve.cuh"
+#include "dispatch.hpp"
 #include "keccak.hpp"
 
 namespace lurk {
@@ -399,8 +400,7 @@ void keygen_from_label_device(int curve, const void* label, size_t label_len, si
     const std::vector<uint8_t> stream = ck_xof_stream(prm, label, label_len, n);
     DevBuf d_u(stream.size());
     if (n) LURK_HIP_CHECK(hipMemcpyAsync(d_u.p, stream.data(), stream.size(), hipMemcpyHostToDevice, s));
-    if (curve == LURK_CURVE_PALLAS) keygen_device<PallasFp>(curve, prm.domain_prefix, d_u.p, n, d_out, s);
-    else keygen_device<PallasFq>(curve, prm.domain_prefix, d_u.p, n, d_out, s);
+    with_pasta_curve(curve, [&](auto P, auto) { keygen_device<decltype(P)>(curve, prm.domain_prefix, d_u.p, n, d_out, s); });
     LURK_HIP_CHECK(hipStreamSynchronize(s));  // the staging buffers go out of scope
 }
 
@@ -424,64 +424,42 @@ extern "C" {
 
 int lurk_hip_shake256(const void* in, size_t in_len, void* out, size_t out_len) {
     // pure host computation (the CPU tests compare it with hashlib)
-    try {
+    return host_guarded([&] {
         LURK_REQUIRE((in || in_len == 0) && (out || out_len == 0), "null buffer");
         shake256((const uint8_t*)in, in_len, (uint8_t*)out, out_len);
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+    });
 }
 
 int lurk_hip_ck_params_get(lurk_hip_ck_params* out) {
-    try {
+    return host_guarded([&] {
         LURK_REQUIRE(out, "null argument");
         *out = ck_params();
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+    });
 }
 int lurk_hip_ck_params_set(const lurk_hip_ck_params* params) {
-    try {
+    return host_guarded([&] {
         const lurk_hip_ck_params p = params ? *params : ck_params_default();  // NULL: back to the defaults
         ck_params_validate(p);
         std::lock_guard<std::mutex> lk(g_ck_mu);
         g_ck = p;
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+    });
 }
 
 int lurk_hip_ck_from_label_host(int curve, const void* label, size_t label_len, size_t npoints, void* out_affine64) {
     // pure host computation: no device is needed
-    try {
+    return host_guarded([&] {
         require_pasta_curve(curve, "lurk_hip_ck_from_label_host (hash-to-curve)");
         LURK_REQUIRE((label || label_len == 0) && (npoints == 0 || out_affine64), "null argument");
         LURK_REQUIRE(npoints <= ((size_t)1 << 16), "the host form maps at most 2^16 points: build keys with lurk_hip_ck_from_label_dev / lurk_hip_msm_ctx_from_label");
-        if (curve == LURK_CURVE_PALLAS) keygen_from_label_host<PallasFp>(curve, label, label_len, npoints, out_affine64);
-        else keygen_from_label_host<PallasFq>(curve, label, label_len, npoints, out_affine64);
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+        with_pasta_curve(curve, [&](auto P, auto) { keygen_from_label_host<decltype(P)>(curve, label, label_len, npoints, out_affine64); });
+    });
 }
 
 int lurk_hip_ck_hash_to_curve_dev(int curve, const char* domain_prefix, const void* d_uniform32, size_t n, void* d_out_affine64, void* stream) {
     return guarded([&] {
         require_pasta_curve(curve, "lurk_hip_ck_hash_to_curve_dev");
         LURK_REQUIRE(domain_prefix && (n == 0 || (d_uniform32 && d_out_affine64)), "null argument");
-        if (curve == LURK_CURVE_PALLAS) keygen_device<PallasFp>(curve, domain_prefix, d_uniform32, n, d_out_affine64, (hipStream_t)stream);
-        else keygen_device<PallasFq>(curve, domain_prefix, d_uniform32, n, d_out_affine64, (hipStream_t)stream);
+        with_pasta_curve(curve, [&](auto P, auto) { keygen_device<decltype(P)>(curve, domain_prefix, d_uniform32, n, d_out_affine64, (hipStream_t)stream); });
     });
 }
 

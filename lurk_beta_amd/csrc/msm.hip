@@ -23,6 +23,7 @@
 #include <memory>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "msm_core.cuh"
 #include "msm_sort.hpp"
 
@@ -979,18 +980,6 @@ struct MsmCtx : MsmCtxBase {
     }
 };
 
-// curve id -> f(base field pack, scalar field pack).  Every entry point that takes a curve id goes through this (or refuses the
-// id by name): nothing falls through to a default curve.  The kernels of the BN254 cycle are instantiated in msm_*_bn254.hip.
-template <class F>
-static void with_curve(int curve, F&& f) {
-    switch (curve) {
-        case LURK_CURVE_PALLAS: f(PallasFp{}, PallasFq{}); return;
-        case LURK_CURVE_VESTA: f(PallasFq{}, PallasFp{}); return;
-        case LURK_CURVE_BN254: f(Bn254Fq{}, Bn254Fr{}); return;
-        case LURK_CURVE_GRUMPKIN: f(Bn254Fr{}, Bn254Fq{}); return;
-    }
-    LURK_REQUIRE(false, "unknown curve id");
-}
 static MsmCtxBase* new_ctx(int curve) {
     MsmCtxBase* c = nullptr;
     with_curve(curve, [&](auto P, auto SF) { c = new MsmCtx<decltype(P), decltype(SF)>(); });
@@ -1697,39 +1686,24 @@ int lurk_hip_point_sum_gathered(int curve, void* out, const void* gathered, size
 }
 
 int lurk_hip_point_sum(int curve, void* out, const void* points, size_t count) {
-    try {
+    return host_guarded([&] {
         LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
         LURK_REQUIRE(out && (count == 0 || points), "null argument");
         with_curve(curve, [&](auto P, auto) { point_sum_host<decltype(P)>(points, count, out); });
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+    });
 }
 int lurk_hip_point_mul(int curve, void* out, const void* point, const void* scalar32, int is_mont) {
-    try {
+    return host_guarded([&] {
         LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
         LURK_REQUIRE(out && point && scalar32, "null argument");
         with_curve(curve, [&](auto P, auto SF) { point_mul_host<decltype(P), decltype(SF)>(point, scalar32, is_mont, out); });
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+    });
 }
 int lurk_hip_point_to_affine_canonical(int curve, void* out_xy64, const void* point) {
-    try {
+    return host_guarded([&] {
         LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
         LURK_REQUIRE(out_xy64 && point, "null argument");
         with_curve(curve, [&](auto P, auto) { point_affine_canonical_host<decltype(P)>(point, out_xy64); });
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+    });
 }
 }

@@ -472,21 +472,21 @@ extern "C" {
 
 int lurk_hip_ntt_dev(int field_id, void* d_inout, unsigned log_n, int inverse, void* stream) {
     return guarded([&] {
-        LURK_REQUIRE(field_id == 0 || field_id == 1, "NTT is offered over the Pasta fields only");
+        LURK_REQUIRE(field_id == LURK_FIELD_PALLAS_FP || field_id == LURK_FIELD_PALLAS_FQ, "NTT is offered over the Pasta fields only");
         LURK_REQUIRE(d_inout, "null buffer");
-        if (field_id == 0) ntt_device<PallasFp>(d_inout, log_n, inverse != 0, (hipStream_t)stream);
+        if (field_id == LURK_FIELD_PALLAS_FP) ntt_device<PallasFp>(d_inout, log_n, inverse != 0, (hipStream_t)stream);
         else ntt_device<PallasFq>(d_inout, log_n, inverse != 0, (hipStream_t)stream);
     });
 }
 int lurk_hip_ntt(int field_id, void* inout, unsigned log_n, int inverse) {
     return guarded([&] {
-        LURK_REQUIRE(field_id == 0 || field_id == 1, "NTT is offered over the Pasta fields only");
+        LURK_REQUIRE(field_id == LURK_FIELD_PALLAS_FP || field_id == LURK_FIELD_PALLAS_FQ, "NTT is offered over the Pasta fields only");
         LURK_REQUIRE(inout, "null buffer");
         LURK_REQUIRE(log_n <= 28, "log_n too large");
         size_t n = (size_t)1 << log_n;
         DevBuf d(n * 32);
         LURK_HIP_CHECK(hipMemcpy(d.p, inout, n * 32, hipMemcpyHostToDevice));
-        if (field_id == 0) ntt_device<PallasFp>(d.p, log_n, inverse != 0, nullptr);
+        if (field_id == LURK_FIELD_PALLAS_FP) ntt_device<PallasFp>(d.p, log_n, inverse != 0, nullptr);
         else ntt_device<PallasFq>(d.p, log_n, inverse != 0, nullptr);
         LURK_HIP_CHECK(hipStreamSynchronize(nullptr));
         LURK_HIP_CHECK(hipMemcpy(inout, d.p, n * 32, hipMemcpyDeviceToHost));

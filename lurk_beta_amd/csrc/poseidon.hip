@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "poseidon.cuh"
 #include "poseidon29.cuh"
 #include "poseidon_params.hpp"
@@ -423,9 +424,7 @@ static PoseidonConsts& get_consts(int field_id, int arity) {
     auto it = g_pc.find(key);
     if (it == g_pc.end()) {
         std::unique_ptr<PoseidonConsts> pc;
-        if (field_id == 0) pc = build_consts<PallasFp>(arity);
-        else if (field_id == 1) pc = build_consts<PallasFq>(arity);
-        else pc = build_consts<Bn254Fr>(arity);
+        with_field(field_id, [&](auto F) { pc = build_consts<decltype(F)>(arity); });
         it = g_pc.emplace(key, std::move(pc)).first;
     }
     return *it->second;
@@ -483,9 +482,7 @@ static void launch_batch_f(int arity, const void* d_pre, void* d_out, size_t n, 
 
 void poseidon_batch_device(int field_id, int arity, const void* d_pre, void* d_out, size_t n, int flags, hipStream_t s) {
     PoseidonConsts& pc = get_consts(field_id, arity);
-    if (field_id == 0) launch_batch_f<PallasFp>(arity, d_pre, d_out, n, pc, flags, s);
-    else if (field_id == 1) launch_batch_f<PallasFq>(arity, d_pre, d_out, n, pc, flags, s);
-    else launch_batch_f<Bn254Fr>(arity, d_pre, d_out, n, pc, flags, s);
+    with_field(field_id, [&](auto F) { launch_batch_f<decltype(F)>(arity, d_pre, d_out, n, pc, flags, s); });
 }
 
 // ---- slot witnesses: launch side -------------------------------------------------------------------------------------
@@ -533,7 +530,7 @@ static BitDecompDev& bit_decomp_program(int field_id) {
     auto it = progs.find(field_id);
     if (it == progs.end()) {
         auto bd = std::make_unique<BitDecompDev>();
-        bd->host = field_id == 0 ? make_bit_decomp_program<PallasFp>() : field_id == 1 ? make_bit_decomp_program<PallasFq>() : make_bit_decomp_program<Bn254Fr>();
+        with_field(field_id, [&](auto F) { bd->host = make_bit_decomp_program<decltype(F)>(); });
         it = progs.emplace(field_id, std::move(bd)).first;
     }
     return *it->second;
@@ -575,16 +572,12 @@ void slot_witness_device(int field_id, int slot_type, const void* d_pre, size_t 
     LURK_REQUIRE(slot_is_hash(slot_type) || slot_type == LURK_SLOT_BIT_DECOMP, "unknown slot type");
     if (slot_type == LURK_SLOT_BIT_DECOMP) {
         BitDecompDev& bd = bit_decomp_program(field_id);
-        if (field_id == 0) launch_bit_decomp<PallasFp>(bd, d_pre, n, pre_mont, dst, s);
-        else if (field_id == 1) launch_bit_decomp<PallasFq>(bd, d_pre, n, pre_mont, dst, s);
-        else launch_bit_decomp<Bn254Fr>(bd, d_pre, n, pre_mont, dst, s);
+        with_field(field_id, [&](auto F) { launch_bit_decomp<decltype(F)>(bd, d_pre, n, pre_mont, dst, s); });
         return;
     }
     PoseidonConsts& pc = get_consts(field_id, slot_type);
     const int flags = pre_mont ? PF_IN_MONT : 0;
-    if (field_id == 0) launch_trace_f<PallasFp>(slot_type, d_pre, n, pc, flags, dst, s);
-    else if (field_id == 1) launch_trace_f<PallasFq>(slot_type, d_pre, n, pc, flags, dst, s);
-    else launch_trace_f<Bn254Fr>(slot_type, d_pre, n, pc, flags, dst, s);
+    with_field(field_id, [&](auto F) { launch_trace_f<decltype(F)>(slot_type, d_pre, n, pc, flags, dst, s); });
 }
 
 // All slot blocks of a MultiFrame in one call: the (up to five) launches are independent and, at a folding step's sizes,
@@ -670,31 +663,21 @@ extern "C" {
 
 int lurk_hip_poseidon_constants(int field_id, int arity, int* rf, int* rp, void* rc, void* mds) {
     // pure host computation: usable without a device (tests compare it with the oracle on CPU)
-    try {
+    return host_guarded([&] {
         PoseidonConsts& pc = get_consts(field_id, arity);
         if (rf) *rf = pc.rf;
         if (rp) *rp = pc.rp;
         if (rc) memcpy(rc, pc.rc_canon.data(), pc.rc_canon.size() * 4);
         if (mds) memcpy(mds, pc.mds_canon.data(), pc.mds_canon.size() * 4);
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+    });
 }
 
 int lurk_hip_slot_witness_size(int field_id, int slot_type, size_t* size) {
     // pure host computation (the CPU tests pin it against the reference's constants)
-    try {
+    return host_guarded([&] {
         LURK_REQUIRE(size, "null output");
         *size = slot_witness_size(field_id, slot_type);
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+    });
 }
 
 int lurk_hip_slot_witness_dev(int field_id, int slot_type, const void* d_preimages, size_t n, int preimages_mont, void* d_w,

@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <memory>
 
+#include "dispatch.hpp"
 #include "r1cs_shape.cuh"
 #include "slot_circuit.hpp"
 
@@ -285,29 +286,11 @@ static const SlotCircuit& slot_circuit(int field_id, int slot_type) {
     std::unique_ptr<SlotCircuit>& c = built[std::make_pair(field_id, slot_type)];
     if (!c) {
         c = std::make_unique<SlotCircuit>();
-        if (slot_type == LURK_SLOT_BIT_DECOMP)
-            *c = field_id == 0 ? bit_decomp_slot_circuit<PallasFp>() : field_id == 1 ? bit_decomp_slot_circuit<PallasFq>() : bit_decomp_slot_circuit<Bn254Fr>();
-        else
-            *c = field_id == 0 ? poseidon_slot_circuit<PallasFp>(slot_type)
-                               : field_id == 1 ? poseidon_slot_circuit<PallasFq>(slot_type) : poseidon_slot_circuit<Bn254Fr>(slot_type);
+        with_field(field_id, [&](auto F) {
+            *c = slot_type == LURK_SLOT_BIT_DECOMP ? bit_decomp_slot_circuit<decltype(F)>() : poseidon_slot_circuit<decltype(F)>(slot_type);
+        });
     }
     return *c;
-}
-
-// host-only entry points report like lurk_hip_slot_witness_size: no device needed
-template <class F>
-static int host_guarded(F&& f) {
-    try {
-        f();
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    } catch (const std::exception& e) {
-        set_error(LURK_HIP_ERR_HIP, e.what());
-        return LURK_HIP_ERR_HIP;
-    }
 }
 
 }  // namespace lurk
@@ -427,9 +410,7 @@ int lurk_hip_r1cs_is_sat_dev(const lurk_hip_r1cs* shape, const void* d_z, const 
         LURK_REQUIRE(shape && d_z && n_unsat && first_unsat, "null argument");
         const R1csShape& sh = shape->sh;
         LURK_REQUIRE(current_device() == sh.device, "the shape is resident on another device than the current one");
-        if (sh.field_id == 0) is_sat<PallasFp>(sh, d_z, d_e, n_unsat, first_unsat, (hipStream_t)stream);
-        else if (sh.field_id == 1) is_sat<PallasFq>(sh, d_z, d_e, n_unsat, first_unsat, (hipStream_t)stream);
-        else is_sat<Bn254Fr>(sh, d_z, d_e, n_unsat, first_unsat, (hipStream_t)stream);
+        with_field(sh.field_id, [&](auto F) { is_sat<decltype(F)>(sh, d_z, d_e, n_unsat, first_unsat, (hipStream_t)stream); });
     });
 }
 

@@ -33,18 +33,18 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
     LURK_HIP_CHECK(hipMemsetAsync(z.p, 0, 2 * nv * 32, s));
     LURK_HIP_CHECK(hipMemcpyAsync(z.p, d_w, nv * 32, hipMemcpyDeviceToDevice, s));
     LURK_HIP_CHECK(hipMemcpyAsync((char*)z.p + nv * 32, ux.data(), (1 + nio) * 32, hipMemcpyHostToDevice, s));
-    sp_ok(lurk_hip_r1cs_multiply_vec_dev(shape, z.p, az.p, bz.p, cz.p, vs));
+    nested_ok(lurk_hip_r1cs_multiply_vec_dev(shape, z.p, az.p, bz.p, cz.p, vs));
     std::vector<Fe<F>> tau(ell_x);
     for (int j = 0; j < ell_x; j++) tau[j] = sp_squeeze<F>(tr.t, splabel::TAU, field_id);
     SpScratch d_tau(nc * 32, s), ucze(nc * 32, s);
     sp_eq<F>(field_id, tau, d_tau.p, s);
-    sp_ok(lurk_hip_fold_vec_dev(field_id, d_e, cz.p, ux[0].l, nc, ucze.p, vs));  // E + u Cz
+    nested_ok(lurk_hip_fold_vec_dev(field_id, d_e, cz.p, ux[0].l, nc, ucze.p, vs));  // E + u Cz
     // ---- outer sum-check: eq(tau) (Az Bz - (u Cz + E)), claim 0; Az and Bz are consumed, Cz and E are needed afterwards
     const uint64_t zero32[4] = {0, 0, 0, 0};
     std::vector<Fe<F>> r_x, r_y, r_z;
     auto challenges = [&](const std::vector<uint64_t>& buf, int rounds, std::vector<Fe<F>>& into) {
         into.resize(rounds);
-        for (int j = 0; j < rounds; j++) into[j] = SpField<F>::from_canonical(buf.data() + 4 * j);
+        for (int j = 0; j < rounds; j++) into[j] = fe_read_canonical<F>(buf.data() + 4 * j);
     };
     auto binding = [&](std::vector<uint64_t>& keep, int rounds, const char* absorb, const char* absorb2, const char* squeeze) {
         return sp_round_binding(tr.t, field_id, curve, keep, rounds, absorb, absorb2, squeeze, 0);
@@ -55,15 +55,15 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
         std::vector<uint64_t> keep;
         lurk_hip_keccak_round_binding b = binding(keep, ell_x, splabel::POLY, nullptr, splabel::CHALLENGE);
         b.n_scalars = 4;
-        sp_ok(lurk_hip_sumcheck_prove_dev(field_id, 3, tabs, nc, zero32, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_outer, finals4, claim_out, vs));
+        nested_ok(lurk_hip_sumcheck_prove_dev(field_id, 3, tabs, nc, zero32, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_outer, finals4, claim_out, vs));
         challenges(keep, ell_x, r_x);
     }
-    const Fe<F> claim_az = SpField<F>::from_canonical(finals4 + 4), claim_bz = SpField<F>::from_canonical(finals4 + 8);
+    const Fe<F> claim_az = fe_read_canonical<F>(finals4 + 4), claim_bz = fe_read_canonical<F>(finals4 + 8);
     const Fe<F> claim_cz = sp_mle<F>(field_id, cz.p, r_x, s), eval_e = sp_mle<F>(field_id, d_e, r_x, s);
-    SpField<F>::to_canonical(claim_az, (char*)out->claims_outer);
-    SpField<F>::to_canonical(claim_bz, (char*)out->claims_outer + 32);
-    SpField<F>::to_canonical(claim_cz, (char*)out->claims_outer + 64);
-    SpField<F>::to_canonical(eval_e, out->eval_e);
+    fe_write_canonical<F>((char*)out->claims_outer, claim_az);
+    fe_write_canonical<F>((char*)out->claims_outer + 32, claim_bz);
+    fe_write_canonical<F>((char*)out->claims_outer + 64, claim_cz);
+    fe_write_canonical<F>(out->eval_e, eval_e);
     sp_absorb<F>(tr.t, splabel::CLAIMS_OUTER, {claim_az, claim_bz, claim_cz, eval_e});
     const Fe<F> r = sp_squeeze<F>(tr.t, splabel::R, field_id), r2 = fe_mul<F>(r, r);
     const Fe<F> claim_inner = fe_add<F>(fe_add<F>(claim_az, fe_mul<F>(r, claim_bz)), fe_mul<F>(r2, claim_cz));
@@ -72,24 +72,24 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
     {
         SpScratch eq_rx(nc * 32, s), ea(2 * nv * 32, s), eb(2 * nv * 32, s), ec(2 * nv * 32, s), ab(2 * nv * 32, s);
         sp_eq<F>(field_id, r_x, eq_rx.p, s);
-        sp_ok(lurk_hip_r1cs_multiply_vec_dev(shape_t, eq_rx.p, ea.p, eb.p, ec.p, vs));
-        sp_ok(lurk_hip_fold_vec_dev(field_id, ea.p, eb.p, r.l, 2 * nv, ab.p, vs));
-        sp_ok(lurk_hip_fold_vec_dev(field_id, ab.p, ec.p, r2.l, 2 * nv, abc.p, vs));  // (the block's scratch is released in stream order)
+        nested_ok(lurk_hip_r1cs_multiply_vec_dev(shape_t, eq_rx.p, ea.p, eb.p, ec.p, vs));
+        nested_ok(lurk_hip_fold_vec_dev(field_id, ea.p, eb.p, r.l, 2 * nv, ab.p, vs));
+        nested_ok(lurk_hip_fold_vec_dev(field_id, ab.p, ec.p, r2.l, 2 * nv, abc.p, vs));  // (the block's scratch is released in stream order)
     }
     {
         void* tabs[2] = {abc.p, z.p};  // (z is consumed: W itself is read below, not z)
         uint64_t claim_can[4];
-        SpField<F>::to_canonical(claim_inner, claim_can);
+        fe_write_canonical<F>(claim_can, claim_inner);
         std::vector<uint64_t> keep;
         lurk_hip_keccak_round_binding b = binding(keep, ell_y, splabel::POLY, nullptr, splabel::CHALLENGE);
         b.n_scalars = 3;
         uint64_t fin2[8];
-        sp_ok(lurk_hip_sumcheck_prove_dev(field_id, 2, tabs, 2 * nv, claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_inner, fin2, claim_out, vs));
+        nested_ok(lurk_hip_sumcheck_prove_dev(field_id, 2, tabs, 2 * nv, claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_inner, fin2, claim_out, vs));
         challenges(keep, ell_y, r_y);
     }
     const std::vector<Fe<F>> r_y_tail(r_y.begin() + 1, r_y.end());
     const Fe<F> eval_w = sp_mle<F>(field_id, d_w, r_y_tail, s);
-    SpField<F>::to_canonical(eval_w, out->eval_w);
+    fe_write_canonical<F>(out->eval_w, eval_w);
     sp_absorb<F>(tr.t, splabel::EVAL_W, {eval_w});
     // ---- the two evaluation claims -> one point: W and E zero-padded to N, their points padded with leading zeros
     SpScratch p1(N * 32, s), p2(N * 32, s);
@@ -111,30 +111,30 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
         void* tabs[4] = {e1.p, q1.p, e2.p, q2.p};
         uint64_t coeffs[8], claim_can[4];
         const Fe<F> one = fe_one<F>();
-        SpField<F>::to_canonical(one, coeffs);
-        SpField<F>::to_canonical(rho, coeffs + 4);
-        SpField<F>::to_canonical(fe_add<F>(eval_w, fe_mul<F>(rho, eval_e)), claim_can);
+        fe_write_canonical<F>(coeffs, one);
+        fe_write_canonical<F>(coeffs + 4, rho);
+        fe_write_canonical<F>(claim_can, fe_add<F>(eval_w, fe_mul<F>(rho, eval_e)));
         std::vector<uint64_t> keep;
         lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::POLY, nullptr, splabel::CHALLENGE);
         b.n_scalars = 3;
-        sp_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 2, 2, tabs, N, coeffs, claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_batch, fin_batch,
-                                                claim_out, vs));
+        nested_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 2, 2, tabs, N, coeffs, claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_batch, fin_batch,
+                                                    claim_out, vs));
         challenges(keep, ell, r_z);
     }
-    const Fe<F> ev1 = SpField<F>::from_canonical(fin_batch + 4), ev2 = SpField<F>::from_canonical(fin_batch + 12);  // (A_i(r), B_i(r)) per instance: the B's
-    SpField<F>::to_canonical(ev1, (char*)out->evals_batch);
-    SpField<F>::to_canonical(ev2, (char*)out->evals_batch + 32);
+    const Fe<F> ev1 = fe_read_canonical<F>(fin_batch + 4), ev2 = fe_read_canonical<F>(fin_batch + 12);  // (A_i(r), B_i(r)) per instance: the B's
+    fe_write_canonical<F>((char*)out->evals_batch, ev1);
+    fe_write_canonical<F>((char*)out->evals_batch + 32, ev2);
     sp_absorb<F>(tr.t, splabel::EVALS_BATCH, {ev1, ev2});
     const Fe<F> gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
     SpScratch joint(N * 32, s), eq_rz(N * 32, s);
-    sp_ok(lurk_hip_fold_vec_dev(field_id, p1.p, p2.p, gamma.l, N, joint.p, vs));
+    nested_ok(lurk_hip_fold_vec_dev(field_id, p1.p, p2.p, gamma.l, N, joint.p, vs));
     const Fe<F> r0 = sp_squeeze<F>(tr.t, splabel::IPA_R0, field_id);
     uint64_t ck_c_scaled[12], ck_hat[8];
-    sp_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
+    nested_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
     sp_eq<F>(field_id, r_z, eq_rz.p, s);
     std::vector<uint64_t> keep;
     lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::IPA_L, splabel::IPA_R, splabel::IPA_CHALLENGE);
-    sp_ok(lurk_hip_ipa_prove_dev(key, joint.p, eq_rz.p, N, ck_c_scaled, lurk_hip_keccak_ipa_challenge, &b, out->ipa_l, out->ipa_r, out->ipa_a, ck_hat, vs));
+    nested_ok(lurk_hip_ipa_prove_dev(key, joint.p, eq_rz.p, N, ck_c_scaled, lurk_hip_keccak_ipa_challenge, &b, out->ipa_l, out->ipa_r, out->ipa_a, ck_hat, vs));
     LURK_HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -171,12 +171,12 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
     };
     auto canon = [](const std::vector<Fe<F>>& v) {
         std::vector<uint64_t> c(4 * v.size());
-        for (size_t k = 0; k < v.size(); k++) SpField<F>::to_canonical(v[k], c.data() + 4 * k);
+        for (size_t k = 0; k < v.size(); k++) fe_write_canonical<F>(c.data() + 4 * k, v[k]);
         return c;
     };
     auto challenges = [&](const std::vector<uint64_t>& buf, int rounds, std::vector<Fe<F>>& into) {
         into.resize(rounds);
-        for (int j = 0; j < rounds; j++) into[j] = SpField<F>::from_canonical(buf.data() + 4 * j);
+        for (int j = 0; j < rounds; j++) into[j] = fe_read_canonical<F>(buf.data() + 4 * j);
     };
     auto binding = [&](std::vector<uint64_t>& keep, int rounds, const char* absorb, const char* absorb2, const char* squeeze, int n_scalars) {
         return sp_round_binding(tr.t, field_id, curve, keep, rounds, absorb, absorb2, squeeze, n_scalars);
@@ -213,8 +213,8 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
                 LURK_HIP_CHECK(hipMemsetAsync((char*)bz->p + nc * 32, 0, (LX - nc) * 32, s));
                 LURK_HIP_CHECK(hipMemsetAsync((char*)ucze->p + nc * 32, 0, (LX - nc) * 32, s));
             }
-            sp_ok(lurk_hip_r1cs_multiply_vec_dev(inst[i].shape, zs[i]->p, az->p, bz->p, czs[i]->p, vs));
-            sp_ok(lurk_hip_fold_vec_dev(field_id, inst[i].d_e32_mont, czs[i]->p, ux[i][0].l, nc, ucze->p, vs));
+            nested_ok(lurk_hip_r1cs_multiply_vec_dev(inst[i].shape, zs[i]->p, az->p, bz->p, czs[i]->p, vs));
+            nested_ok(lurk_hip_fold_vec_dev(field_id, inst[i].d_e32_mont, czs[i]->p, ux[i][0].l, nc, ucze->p, vs));
             LURK_HIP_CHECK(hipMemcpyAsync(tau_i->p, d_tau->p, LX * 32, hipMemcpyDeviceToDevice, s));  // (every instance binds its own copy)
             for (Buf* b : {&tau_i, &az, &bz, &ucze}) {
                 tabs.push_back((*b)->p);
@@ -224,8 +224,8 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         const std::vector<uint64_t> coeffs = canon(powers(rho_o, n));
         std::vector<uint64_t> keep;
         lurk_hip_keccak_round_binding b = binding(keep, ell_x, splabel::POLY, nullptr, splabel::CHALLENGE, 4);
-        sp_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 3, n, tabs.data(), LX, coeffs.data(), zero32, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_outer,
-                                                fin_outer.data(), claim_out, vs));
+        nested_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 3, n, tabs.data(), LX, coeffs.data(), zero32, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_outer,
+                                                    fin_outer.data(), claim_out, vs));
         challenges(keep, ell_x, r_x);
     }
     Buf eq_rx = mk(LX);
@@ -236,14 +236,14 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         for (size_t i = 0; i < n; i++) {
             const size_t nc = inst[i].num_cons;
             const int px = ell_x - sp_log2(nc);
-            cl_a[i] = SpField<F>::from_canonical(fin_outer.data() + 16 * i + 4);
-            cl_b[i] = SpField<F>::from_canonical(fin_outer.data() + 16 * i + 8);
-            sp_ok(lurk_hip_inner_product_dev(field_id, czs[i]->p, eq_rx->p, nc, cl_c[i].l, vs));  // Cz_i (padded) at r_x: the leading entries of eq(r_x)
+            cl_a[i] = fe_read_canonical<F>(fin_outer.data() + 16 * i + 4);
+            cl_b[i] = fe_read_canonical<F>(fin_outer.data() + 16 * i + 8);
+            nested_ok(lurk_hip_inner_product_dev(field_id, czs[i]->p, eq_rx->p, nc, cl_c[i].l, vs));  // Cz_i (padded) at r_x: the leading entries of eq(r_x)
             ev_e[i] = sp_mle<F>(field_id, inst[i].d_e32_mont, std::vector<Fe<F>>(r_x.begin() + px, r_x.end()), s);
-            SpField<F>::to_canonical(cl_a[i], (char*)out->claims_outer + 96 * i);
-            SpField<F>::to_canonical(cl_b[i], (char*)out->claims_outer + 96 * i + 32);
-            SpField<F>::to_canonical(cl_c[i], (char*)out->claims_outer + 96 * i + 64);
-            SpField<F>::to_canonical(ev_e[i], (char*)out->evals_e + 32 * i);
+            fe_write_canonical<F>((char*)out->claims_outer + 96 * i, cl_a[i]);
+            fe_write_canonical<F>((char*)out->claims_outer + 96 * i + 32, cl_b[i]);
+            fe_write_canonical<F>((char*)out->claims_outer + 96 * i + 64, cl_c[i]);
+            fe_write_canonical<F>((char*)out->evals_e + 32 * i, ev_e[i]);
             flat.push_back(cl_a[i]);
             flat.push_back(cl_b[i]);
             flat.push_back(cl_c[i]);
@@ -264,9 +264,9 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
             Buf abc = mk(LY), zp = padded_copy(zs[i]->p, 2 * nv, LY);
             {
                 SpScratch ea(2 * nv * 32, s), eb(2 * nv * 32, s), ec(2 * nv * 32, s), ab(2 * nv * 32, s);
-                sp_ok(lurk_hip_r1cs_multiply_vec_dev(inst[i].shape_t, eq_rx->p, ea.p, eb.p, ec.p, vs));  // eq(r_x)'s first num_cons entries
-                sp_ok(lurk_hip_fold_vec_dev(field_id, ea.p, eb.p, r.l, 2 * nv, ab.p, vs));
-                sp_ok(lurk_hip_fold_vec_dev(field_id, ab.p, ec.p, r2.l, 2 * nv, abc->p, vs));
+                nested_ok(lurk_hip_r1cs_multiply_vec_dev(inst[i].shape_t, eq_rx->p, ea.p, eb.p, ec.p, vs));  // eq(r_x)'s first num_cons entries
+                nested_ok(lurk_hip_fold_vec_dev(field_id, ea.p, eb.p, r.l, 2 * nv, ab.p, vs));
+                nested_ok(lurk_hip_fold_vec_dev(field_id, ab.p, ec.p, r2.l, 2 * nv, abc->p, vs));
             }
             if (LY > 2 * nv) LURK_HIP_CHECK(hipMemsetAsync((char*)abc->p + 2 * nv * 32, 0, (LY - 2 * nv) * 32, s));
             const Fe<F> ci = fe_add<F>(fe_add<F>(cl_a[i], fe_mul<F>(r, cl_b[i])), fe_mul<F>(r2, cl_c[i]));
@@ -278,17 +278,17 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         }
         const std::vector<uint64_t> coeffs = canon(pw);
         uint64_t claim_can[4];
-        SpField<F>::to_canonical(claim, claim_can);
+        fe_write_canonical<F>(claim_can, claim);
         std::vector<uint64_t> keep, fin(n * 8);
         lurk_hip_keccak_round_binding b = binding(keep, ell_y, splabel::POLY, nullptr, splabel::CHALLENGE, 3);
-        sp_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 2, n, tabs.data(), LY, coeffs.data(), claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_inner,
-                                                fin.data(), claim_out, vs));
+        nested_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 2, n, tabs.data(), LY, coeffs.data(), claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_inner,
+                                                    fin.data(), claim_out, vs));
         challenges(keep, ell_y, r_y);
     }
     for (size_t i = 0; i < n; i++) {
         const int py = ell_y - (sp_log2(inst[i].num_vars) + 1);
         ev_w[i] = sp_mle<F>(field_id, inst[i].d_w32_mont, std::vector<Fe<F>>(r_y.begin() + py + 1, r_y.end()), s);
-        SpField<F>::to_canonical(ev_w[i], (char*)out->evals_w + 32 * i);
+        fe_write_canonical<F>((char*)out->evals_w + 32 * i, ev_w[i]);
     }
     sp_absorb<F>(tr.t, splabel::EVALS_W, ev_w);
     // ---- all 2 n evaluation claims -> one point
@@ -325,17 +325,17 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
         }
         const std::vector<uint64_t> coeffs = canon(pw);
         uint64_t claim_can[4];
-        SpField<F>::to_canonical(claim, claim_can);
+        fe_write_canonical<F>(claim_can, claim);
         std::vector<uint64_t> keep;
         lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::POLY, nullptr, splabel::CHALLENGE, 3);
-        sp_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 2, 2 * n, tabs.data(), N, coeffs.data(), claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_batch,
-                                                fin_batch.data(), claim_out, vs));
+        nested_ok(lurk_hip_sumcheck_prove_batch_dev(field_id, 2, 2 * n, tabs.data(), N, coeffs.data(), claim_can, lurk_hip_keccak_sumcheck_challenge, &b, out->polys_batch,
+                                                    fin_batch.data(), claim_out, vs));
         challenges(keep, ell, r_z);
     }
     std::vector<Fe<F>> evals_batch(2 * n);
     for (size_t k = 0; k < 2 * n; k++) {
-        evals_batch[k] = SpField<F>::from_canonical(fin_batch.data() + 8 * k + 4);  // (eq_k(r_z), poly_k(r_z)): the polynomial's
-        SpField<F>::to_canonical(evals_batch[k], (char*)out->evals_batch + 32 * k);
+        evals_batch[k] = fe_read_canonical<F>(fin_batch.data() + 8 * k + 4);  // (eq_k(r_z), poly_k(r_z)): the polynomial's
+        fe_write_canonical<F>((char*)out->evals_batch + 32 * k, evals_batch[k]);
     }
     sp_absorb<F>(tr.t, splabel::EVALS_BATCH, evals_batch);
     const Fe<F> gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
@@ -343,17 +343,17 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
     {
         Fe<F> g = gamma;
         for (size_t k = 1; k < 2 * n; k++) {
-            sp_ok(lurk_hip_fold_vec_dev(field_id, joint->p, polys[k]->p, g.l, N, joint->p, vs));  // joint += gamma^k poly_k (element-wise: in place)
+            nested_ok(lurk_hip_fold_vec_dev(field_id, joint->p, polys[k]->p, g.l, N, joint->p, vs));  // joint += gamma^k poly_k (element-wise: in place)
             g = fe_mul<F>(g, gamma);
         }
     }
     const Fe<F> r0 = sp_squeeze<F>(tr.t, splabel::IPA_R0, field_id);
     uint64_t ck_c_scaled[12], ck_hat[8];
-    sp_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
+    nested_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
     sp_eq<F>(field_id, r_z, eq_rz->p, s);
     std::vector<uint64_t> keep;
     lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::IPA_L, splabel::IPA_R, splabel::IPA_CHALLENGE, 0);
-    sp_ok(lurk_hip_ipa_prove_dev(key, joint->p, eq_rz->p, N, ck_c_scaled, lurk_hip_keccak_ipa_challenge, &b, out->ipa_l, out->ipa_r, out->ipa_a, ck_hat, vs));
+    nested_ok(lurk_hip_ipa_prove_dev(key, joint->p, eq_rz->p, N, ck_c_scaled, lurk_hip_keccak_ipa_challenge, &b, out->ipa_l, out->ipa_r, out->ipa_a, ck_hat, vs));
     LURK_HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -396,12 +396,11 @@ int lurk_hip_spartan_prove_dev(const lurk_hip_r1cs* shape, const lurk_hip_r1cs* 
             LURK_REQUIRE(f == want_field && ft == want_field, "the shapes are not over the scalar field of the key's curve");
         }
         DeviceGuard dg(device);
-        if (curve == LURK_CURVE_PALLAS)
-            spartan_prove<PallasFq>(curve, LURK_FIELD_PALLAS_FQ, shape, shape_t, num_cons, num_vars, num_io, key, ck_c_jacobian96, x32_canonical, u32_canonical, d_w, d_e,
-                                    comm_w_jacobian96, comm_e_jacobian96, label, label_len, out, (hipStream_t)stream);
-        else
-            spartan_prove<PallasFp>(curve, LURK_FIELD_PALLAS_FP, shape, shape_t, num_cons, num_vars, num_io, key, ck_c_jacobian96, x32_canonical, u32_canonical, d_w, d_e,
-                                    comm_w_jacobian96, comm_e_jacobian96, label, label_len, out, (hipStream_t)stream);
+        with_pasta_curve(curve, [&](auto, auto SF) {
+            using F = decltype(SF);
+            spartan_prove<F>(curve, F::ID, shape, shape_t, num_cons, num_vars, num_io, key, ck_c_jacobian96, x32_canonical, u32_canonical, d_w, d_e, comm_w_jacobian96,
+                             comm_e_jacobian96, label, label_len, out, (hipStream_t)stream);
+        });
     });
 }
 
@@ -436,10 +435,10 @@ int lurk_hip_spartan_prove_batch_dev(const lurk_hip_spartan_instance* instances,
             LURK_REQUIRE(f == want_field && ft == want_field, "the shapes are not over the scalar field of the key's curve");
         }
         DeviceGuard dg(device);
-        if (curve == LURK_CURVE_PALLAS)
-            spartan_prove_batch<PallasFq>(curve, LURK_FIELD_PALLAS_FQ, instances, n_instances, key, ck_c_jacobian96, label, label_len, out, (hipStream_t)stream);
-        else
-            spartan_prove_batch<PallasFp>(curve, LURK_FIELD_PALLAS_FP, instances, n_instances, key, ck_c_jacobian96, label, label_len, out, (hipStream_t)stream);
+        with_pasta_curve(curve, [&](auto, auto SF) {
+            using F = decltype(SF);
+            spartan_prove_batch<F>(curve, F::ID, instances, n_instances, key, ck_c_jacobian96, label, label_len, out, (hipStream_t)stream);
+        });
     });
 }
 }

@@ -6,7 +6,7 @@
 #include <vector>
 
 #include "common.hpp"
-#include "field.cuh"
+#include "dispatch.hpp"
 
 namespace lurk {
 
@@ -34,10 +34,6 @@ constexpr const char* IPA_R = "R";
 constexpr const char* IPA_CHALLENGE = "r";
 }  // namespace splabel
 
-static void sp_ok(int rc) {
-    if (rc != 0) throw HipFailure{rc, lurk_hip_last_error()};
-}
-
 using SpScratch = ArenaBuf;  // scratch vectors come off the stream's arena (common.hpp): a push, not a hipMallocAsync
 
 struct SpTranscript {
@@ -48,36 +44,22 @@ struct SpTranscript {
 };
 
 template <class F>
-struct SpField {
-    static Fe<F> from_canonical(const void* p) {
-        Fe<F> x;
-        memcpy(x.l, p, 32);
-        LURK_REQUIRE(!fe_canonical_ge_mod<F>(x.l), "a field element is not reduced modulo the field order");
-        return fe_to_mont<F>(x);
-    }
-    static void to_canonical(const Fe<F>& m, void* out) {
-        const Fe<F> c = fe_from_mont<F>(m);
-        memcpy(out, c.l, 32);
-    }
-};
-
-template <class F>
 static Fe<F> sp_squeeze(lurk_hip_keccak_transcript* t, const char* label, int field_id) {
     uint64_t r[4];
-    sp_ok(lurk_hip_keccak_transcript_squeeze(t, label, strlen(label), field_id, r));
-    return SpField<F>::from_canonical(r);
+    nested_ok(lurk_hip_keccak_transcript_squeeze(t, label, strlen(label), field_id, r));
+    return fe_read_canonical<F>(r);
 }
 template <class F>
 static void sp_absorb(lurk_hip_keccak_transcript* t, const char* label, const std::vector<Fe<F>>& mont_vals) {
     std::vector<uint64_t> can(4 * mont_vals.size());
-    for (size_t i = 0; i < mont_vals.size(); i++) SpField<F>::to_canonical(mont_vals[i], can.data() + 4 * i);
-    sp_ok(lurk_hip_keccak_transcript_absorb_scalars(t, label, strlen(label), can.data(), mont_vals.size()));
+    for (size_t i = 0; i < mont_vals.size(); i++) fe_write_canonical<F>(can.data() + 4 * i, mont_vals[i]);
+    nested_ok(lurk_hip_keccak_transcript_absorb_scalars(t, label, strlen(label), can.data(), mont_vals.size()));
 }
 // eq(point) as 2^|point| Montgomery elements on the device
 template <class F>
 static void sp_eq(int field_id, const std::vector<Fe<F>>& point, void* d_out, hipStream_t s) {
     // (the point is copied out of pageable memory before the call returns; every caller's vector outlives the proof anyway)
-    sp_ok(lurk_hip_eq_evals_dev(field_id, point.empty() ? nullptr : (const void*)point.data(), (int)point.size(), d_out, (void*)s));
+    nested_ok(lurk_hip_eq_evals_dev(field_id, point.empty() ? nullptr : (const void*)point.data(), (int)point.size(), d_out, (void*)s));
 }
 // the multilinear extension of a device table at `point` (Montgomery): <table, eq(point)>
 template <class F>
@@ -85,7 +67,7 @@ static Fe<F> sp_mle(int field_id, const void* d_table, const std::vector<Fe<F>>&
     SpScratch eq(((size_t)32) << point.size(), s);
     sp_eq<F>(field_id, point, eq.p, s);
     Fe<F> out;
-    sp_ok(lurk_hip_inner_product_dev(field_id, d_table, eq.p, (size_t)1 << point.size(), out.l, (void*)s));
+    nested_ok(lurk_hip_inner_product_dev(field_id, d_table, eq.p, (size_t)1 << point.size(), out.l, (void*)s));
     return out;
 }
 static int sp_log2(size_t n) {
@@ -99,30 +81,30 @@ static int sp_log2(size_t n) {
 template <class F>
 static void sp_prologue(SpTranscript& tr, int curve, const void* label, size_t label_len, const void* comm_w_jac96, const void* comm_e_jac96,
                         const void* u_canonical, const void* x_canonical, size_t nio, std::vector<Fe<F>>& ux) {
-    sp_ok(lurk_hip_keccak_transcript_new(&tr.t, label, label_len));
-    sp_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, splabel::COMM_W, strlen(splabel::COMM_W), curve, comm_w_jac96));
-    sp_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, splabel::COMM_E, strlen(splabel::COMM_E), curve, comm_e_jac96));
+    nested_ok(lurk_hip_keccak_transcript_new(&tr.t, label, label_len));
+    nested_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, splabel::COMM_W, strlen(splabel::COMM_W), curve, comm_w_jac96));
+    nested_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, splabel::COMM_E, strlen(splabel::COMM_E), curve, comm_e_jac96));
     ux.resize(1 + nio);
-    ux[0] = SpField<F>::from_canonical(u_canonical);
-    for (size_t i = 0; i < nio; i++) ux[1 + i] = SpField<F>::from_canonical((const char*)x_canonical + 32 * i);
+    ux[0] = fe_read_canonical<F>(u_canonical);
+    for (size_t i = 0; i < nio; i++) ux[1 + i] = fe_read_canonical<F>((const char*)x_canonical + 32 * i);
     sp_absorb<F>(tr.t, splabel::UX, ux);
 }
 // batched: the number of instances, then every instance's comm_W, comm_E, (u, X)
 template <class F>
 static void sp_prologue_batch(SpTranscript& tr, int curve, const void* label, size_t label_len, const lurk_hip_spartan_instance* inst, size_t n,
                               std::vector<std::vector<Fe<F>>>& ux) {
-    sp_ok(lurk_hip_keccak_transcript_new(&tr.t, label, label_len));
+    nested_ok(lurk_hip_keccak_transcript_new(&tr.t, label, label_len));
     {
         Fe<F> nn = fe_from_u64<F>((uint64_t)n);
         sp_absorb<F>(tr.t, splabel::N, {nn});
     }
     ux.resize(n);
     for (size_t i = 0; i < n; i++) {
-        sp_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, splabel::COMM_W, strlen(splabel::COMM_W), curve, inst[i].comm_w_jacobian96));
-        sp_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, splabel::COMM_E, strlen(splabel::COMM_E), curve, inst[i].comm_e_jacobian96));
+        nested_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, splabel::COMM_W, strlen(splabel::COMM_W), curve, inst[i].comm_w_jacobian96));
+        nested_ok(lurk_hip_keccak_transcript_absorb_point(tr.t, splabel::COMM_E, strlen(splabel::COMM_E), curve, inst[i].comm_e_jacobian96));
         ux[i].resize(1 + inst[i].num_io);
-        ux[i][0] = SpField<F>::from_canonical(inst[i].u32_canonical);
-        for (size_t k = 0; k < inst[i].num_io; k++) ux[i][1 + k] = SpField<F>::from_canonical((const char*)inst[i].x32_canonical + 32 * k);
+        ux[i][0] = fe_read_canonical<F>(inst[i].u32_canonical);
+        for (size_t k = 0; k < inst[i].num_io; k++) ux[i][1 + k] = fe_read_canonical<F>((const char*)inst[i].x32_canonical + 32 * k);
         sp_absorb<F>(tr.t, splabel::UX, ux[i]);
     }
 }

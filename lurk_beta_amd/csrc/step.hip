@@ -16,14 +16,10 @@
 #include <vector>
 
 #include "common.hpp"
-#include "field.cuh"
+#include "dispatch.hpp"
 #include "nifs_pre.hpp"
 
 namespace lurk {
-
-static void ok(int rc) {
-    if (rc != 0) throw HipFailure{rc, lurk_hip_last_error()};
-}
 
 // acc <- acc + x (Montgomery elements in host memory; r * 1 in Montgomery form is r itself)
 template <class F>
@@ -166,14 +162,6 @@ struct lurk_hip_fold_ctx {
 
 namespace lurk {
 
-// f(pack) for the scalar field of the context's curve (Pallas: Fq, Vesta: Fp, BN254: Fr)
-template <class Fn>
-static void with_scalar_field(int field_id, Fn&& f) {
-    if (field_id == LURK_FIELD_PALLAS_FQ) f(PallasFq{});
-    else if (field_id == LURK_FIELD_PALLAS_FP) f(PallasFp{});
-    else if (field_id == LURK_FIELD_BN254_FR) f(Bn254Fr{});
-    else LURK_REQUIRE(false, "the folding context's field is none of the three scalar fields it is offered over");
-}
 // the calls that need the random oracle over the curve's base field: Poseidon constants over the BN254 base field do not exist yet
 static void require_transcript(const lurk_hip_fold_ctx* c, const char* what) {
     if (c->curve == LURK_CURVE_BN254)
@@ -204,13 +192,13 @@ static void fold_instance_settle(lurk_hip_fold_ctx* c) {
     // witness was folded by finish(r) already, so a half-updated instance would silently diverge from it)
     uint64_t pair[24], new_w[12], new_e[12];
     memcpy(pair, c->comm_w, 96);
-    ok(lurk_hip_point_mul(c->curve, pair + 12, c->open_cw, c->owed_r, 1));
-    ok(lurk_hip_point_sum(c->curve, new_w, pair, 2));
+    nested_ok(lurk_hip_point_mul(c->curve, pair + 12, c->open_cw, c->owed_r, 1));
+    nested_ok(lurk_hip_point_sum(c->curve, new_w, pair, 2));
     memcpy(pair, c->comm_e, 96);
-    ok(lurk_hip_point_mul(c->curve, pair + 12, c->open_ct, c->owed_r, 1));
-    ok(lurk_hip_point_sum(c->curve, new_e, pair, 2));
+    nested_ok(lurk_hip_point_mul(c->curve, pair + 12, c->open_ct, c->owed_r, 1));
+    nested_ok(lurk_hip_point_sum(c->curve, new_e, pair, 2));
     std::vector<uint64_t> new_ux = c->ux;
-    with_scalar_field(c->field_id, [&](auto F) { fold_ux_host<decltype(F)>(new_ux, c->open_x2, c->owed_r); });
+    with_field(c->field_id, [&](auto F) { fold_ux_host<decltype(F)>(new_ux, c->open_x2, c->owed_r); });
     memcpy(c->comm_w, new_w, 96);
     memcpy(c->comm_e, new_e, 96);
     c->ux.swap(new_ux);
@@ -235,8 +223,8 @@ static void fold_challenge_finish(lurk_hip_fold_ctx* c, void* r32_mont) {
         return;
     }
     LURK_REQUIRE(c->has_pp, "no pp_digest: call lurk_hip_fold_ctx_set_pp_digest first");
-    ok(lurk_hip_nifs_challenge(c->curve, c->pp_digest, c->comm_w, c->comm_e, c->ux.data(), c->ux.data() + 4, c->open_cw, c->open_x2.data(), c->num_io,
-                               c->open_ct, r32_mont));
+    nested_ok(lurk_hip_nifs_challenge(c->curve, c->pp_digest, c->comm_w, c->comm_e, c->ux.data(), c->ux.data() + 4, c->open_cw, c->open_x2.data(), c->num_io,
+                                      c->open_ct, r32_mont));
 }
 
 // the key and the slot the staged commitment of buffer b runs on
@@ -272,9 +260,9 @@ static void fold_submit_staged(lurk_hip_fold_ctx* c, int b, int mode) {
             LURK_HIP_CHECK(hipStreamWaitEvent(h.stream[b], c->staged_ev[b], 0));
             LURK_HIP_CHECK(hipMemcpyPeerAsync(h.buf[b].p, h.device, src, c->device, c->num_vars * 32, h.stream[b]));
         }
-        ok(lurk_hip_msm_ctx_submit_dev_mode(h.key, 2 * b, h.buf[b].p, c->num_vars, 1, h.stream[b], LURK_MSM_SUBMIT_DEFAULT));
+        nested_ok(lurk_hip_msm_ctx_submit_dev_mode(h.key, 2 * b, h.buf[b].p, c->num_vars, 1, h.stream[b], LURK_MSM_SUBMIT_DEFAULT));
     } else {
-        ok(lurk_hip_msm_ctx_submit_dev_mode(c->key, 2 * b, src, c->num_vars, 1, c->stage_stream[b], mode));  // zero digits cost the sort nothing
+        nested_ok(lurk_hip_msm_ctx_submit_dev_mode(c->key, 2 * b, src, c->num_vars, 1, c->stage_stream[b], mode));  // zero digits cost the sort nothing
     }
     c->submitted[b] = true;
 }
@@ -369,12 +357,12 @@ static void fold_cross_term(lurk_hip_fold_ctx* c, const void* z2) {
         const int k = c->tcur;
         if (c->efold_valid[k]) LURK_HIP_CHECK(hipStreamWaitEvent(c->stream, c->efold_ev[k], 0));  // the fold of E two steps back read t[k]
         const DevBuf* prev = c->abc_pending ? c->abc2[c->abc_buf] : nullptr;
-        ok(lurk_hip_r1cs_cross_term_cached_dev(c->shape, z2, c->abc1[0].p, c->abc1[1].p, c->abc1[2].p, c->u_host, prev ? prev[0].p : nullptr,
-                                               prev ? prev[1].p : nullptr, prev ? prev[2].p : nullptr, prev ? c->abc_r : nullptr, c->t[k].p, c->abc2[k][0].p,
-                                               c->abc2[k][1].p, c->abc2[k][2].p, c->stream));
+        nested_ok(lurk_hip_r1cs_cross_term_cached_dev(c->shape, z2, c->abc1[0].p, c->abc1[1].p, c->abc1[2].p, c->u_host, prev ? prev[0].p : nullptr,
+                                                      prev ? prev[1].p : nullptr, prev ? prev[2].p : nullptr, prev ? c->abc_r : nullptr, c->t[k].p, c->abc2[k][0].p,
+                                                      c->abc2[k][1].p, c->abc2[k][2].p, c->stream));
         c->abc_pending = false;  // the launch is in the stream: a begin that fails later and is repeated must not fold the cache twice
     } else {
-        ok(lurk_hip_r1cs_cross_term_dev(c->shape, c->z[c->cur].p, z2, c->t[c->tcur].p, c->stream));
+        nested_ok(lurk_hip_r1cs_cross_term_dev(c->shape, c->z[c->cur].p, z2, c->t[c->tcur].p, c->stream));
     }
     LURK_HIP_CHECK(hipEventRecord(c->t_ev, c->stream));  // T (and the step's products) are complete
 }
@@ -448,7 +436,7 @@ static void fold_begin(lurk_hip_fold_ctx* c, const lurk_hip_w2_patch* patches, s
         LURK_HIP_CHECK(hipHostMalloc((void**)&c->pin, need + need / 2, hipHostMallocDefault));
         c->pin_cap = need + need / 2;
     }
-    with_scalar_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
+    with_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
     if (c->num_io) memcpy(c->pin + 32, x2_mont, c->num_io * 32);
     LURK_HIP_CHECK(hipMemcpyAsync(z2 + c->num_vars * 32, c->pin, (1 + c->num_io) * 32, hipMemcpyHostToDevice, c->stage_stream[b]));
     const bool late_own_key = patched && fold_late_key(c, patches, n_patches, patched, c->stage_stream[b]);
@@ -488,11 +476,11 @@ static void fold_begin(lurk_hip_fold_ctx* c, const lurk_hip_w2_patch* patches, s
     step_mark("cross term launched");
     fold_submit_staged(c, b, fg);
     tt[1] = now();
-    ok(lurk_hip_msm_ctx_submit_dev_mode(c->key, 1, c->t[c->tcur].p, c->num_cons, 1, c->stream, fg));  // ... commit(T): what the host waits for
+    nested_ok(lurk_hip_msm_ctx_submit_dev_mode(c->key, 1, c->t[c->tcur].p, c->num_cons, 1, c->stream, fg));  // ... commit(T): what the host waits for
     rollback.t_in_flight = true;
     if (patched) {  // commitment of the late ranges: under their own key, or as a num_vars-long vector that is zero elsewhere
-        if (late_own_key) ok(lurk_hip_msm_ctx_submit_dev_mode(c->late_key, 0, c->late_vals.p, patched, 1, c->stage_stream[b], fg));
-        else ok(lurk_hip_msm_ctx_submit_dev_mode(c->key, 3, c->zpatch.p, c->num_vars, 1, c->stage_stream[b], fg));
+        if (late_own_key) nested_ok(lurk_hip_msm_ctx_submit_dev_mode(c->late_key, 0, c->late_vals.p, patched, 1, c->stage_stream[b], fg));
+        else nested_ok(lurk_hip_msm_ctx_submit_dev_mode(c->key, 3, c->zpatch.p, c->num_vars, 1, c->stage_stream[b], fg));
         rollback.late_in_flight = true;
     }
     tt[2] = now();
@@ -503,13 +491,13 @@ static void fold_begin(lurk_hip_fold_ctx* c, const lurk_hip_w2_patch* patches, s
     fold_challenge_begin(c);  // ... and the part of this step's transcript that needs no commitment of this step
     if (patched) {
         c->submitted[b] = false;  // (a wait consumes the slot's commitment whether it succeeds or not)
-        ok(lurk_hip_msm_ctx_wait(fold_staged_key(c, b), 2 * b, body));
+        nested_ok(lurk_hip_msm_ctx_wait(fold_staged_key(c, b), 2 * b, body));
         rollback.late_in_flight = false;
-        ok(late_own_key ? lurk_hip_msm_ctx_wait(c->late_key, 0, late) : lurk_hip_msm_ctx_wait(c->key, 3, late));
+        nested_ok(late_own_key ? lurk_hip_msm_ctx_wait(c->late_key, 0, late) : lurk_hip_msm_ctx_wait(c->key, 3, late));
         uint64_t two[24];
         memcpy(two, body, 96);
         memcpy(two + 12, late, 96);
-        ok(lurk_hip_point_sum(c->curve, comm_w2_jac96, two, 2));  // commit is linear: body + late ranges
+        nested_ok(lurk_hip_point_sum(c->curve, comm_w2_jac96, two, 2));  // commit is linear: body + late ranges
         if (!late_own_key) {
             for (size_t k = 0; k < n_patches; k++)
                 if (patches[k].count) LURK_HIP_CHECK(hipMemsetAsync((char*)c->zpatch.p + patches[k].offset * 32, 0, patches[k].count * 32, c->stage_stream[b]));
@@ -518,12 +506,12 @@ static void fold_begin(lurk_hip_fold_ctx* c, const lurk_hip_w2_patch* patches, s
         }
     } else {
         c->submitted[b] = false;
-        ok(lurk_hip_msm_ctx_wait(fold_staged_key(c, b), 2 * b, comm_w2_jac96));
+        nested_ok(lurk_hip_msm_ctx_wait(fold_staged_key(c, b), 2 * b, comm_w2_jac96));
     }
     if (c->pre) nifs_pre_fresh(c->pre, comm_w2_jac96, x2_mont);  // U2, while commit(T) is still running
     tt[4] = now();
     rollback.t_in_flight = false;
-    ok(lurk_hip_msm_ctx_wait(c->key, 1, comm_t_jac96));
+    nested_ok(lurk_hip_msm_ctx_wait(c->key, 1, comm_t_jac96));
     rollback.armed = false;
     tt[5] = now();
     step_mark("T collected");
@@ -591,7 +579,7 @@ static void fold_submit_multi(lurk_hip_fold_ctx* c, int which, const void* d_vec
         LURK_HIP_CHECK(hipStreamWaitEvent(sb.copy_stream[which], ready, 0));
         LURK_HIP_CHECK(hipMemcpyPeerAsync(sb.buf[which].p, sb.device, (const char*)d_vec + sb.first * 32, c->device, cnt * 32, sb.copy_stream[which]));
     }
-    ok(lurk_hip_msm_multi_submit_dev(c->mkey, which, ptrs.data(), streams.data(), ptrs.size(), n, 1, LURK_MSM_SUBMIT_FOREGROUND));
+    nested_ok(lurk_hip_msm_multi_submit_dev(c->mkey, which, ptrs.data(), streams.data(), ptrs.size(), n, 1, LURK_MSM_SUBMIT_FOREGROUND));
 }
 
 static void fold_begin_multi(lurk_hip_fold_ctx* c, const void* w2, int on_device, void* w2_stream, const void* x2_mont, void* comm_w2_jac96,
@@ -612,7 +600,7 @@ static void fold_begin_multi(lurk_hip_fold_ctx* c, const void* w2, int on_device
         LURK_HIP_CHECK(hipHostMalloc((void**)&c->pin, need * 2, hipHostMallocDefault));
         c->pin_cap = need * 2;
     }
-    with_scalar_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
+    with_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
     if (c->num_io) memcpy(c->pin + 32, x2_mont, c->num_io * 32);
     LURK_HIP_CHECK(hipMemcpyAsync(z2 + c->num_vars * 32, c->pin, need, hipMemcpyHostToDevice, c->stage_stream[0]));
     LURK_HIP_CHECK(hipEventRecord(c->staged_ev[b], c->stage_stream[0]));
@@ -628,10 +616,10 @@ static void fold_begin_multi(lurk_hip_fold_ctx* c, const void* w2, int on_device
         fold_instance_settle(c);  // the previous step's instance fold, while the devices work on this step
         fold_challenge_begin(c);
         w_in_flight = false;
-        ok(lurk_hip_msm_multi_wait(c->mkey, 0, comm_w2_jac96));
+        nested_ok(lurk_hip_msm_multi_wait(c->mkey, 0, comm_w2_jac96));
         if (c->pre) nifs_pre_fresh(c->pre, comm_w2_jac96, x2_mont);
         t_in_flight = false;
-        ok(lurk_hip_msm_multi_wait(c->mkey, 1, comm_t_jac96));
+        nested_ok(lurk_hip_msm_multi_wait(c->mkey, 1, comm_t_jac96));
     } catch (...) {  // nothing stays in flight: the context and the key remain usable, the same begin can be repeated
         uint64_t junk[12];
         if (w_in_flight) (void)lurk_hip_msm_multi_wait(c->mkey, 0, junk);
@@ -659,7 +647,7 @@ static void fold_finish(lurk_hip_fold_ctx* c, const void* r32_mont) {
         // off the chain: the next cross term reads the cached products (folded inside its own launch) and u (a kernel argument), not z or E
         LURK_HIP_CHECK(hipStreamWaitEvent(c->fold_stream, c->t_ev, 0));  // T of this step is complete (the cross term ran on the context's stream)
         LURK_HIP_CHECK(hipStreamWaitEvent(c->fold_stream, c->staged_ev[c->open_buf], 0));  // ... and so is z2 (staged on its own stream)
-        ok(lurk_hip_fold_vecs_dev(c->field_id, 2, a, b, n, o, r32_mont, c->fold_stream));
+        nested_ok(lurk_hip_fold_vecs_dev(c->field_id, 2, a, b, n, o, r32_mont, c->fold_stream));
         LURK_HIP_CHECK(hipEventRecord(c->folded_ev[c->open_buf], c->fold_stream));
         LURK_HIP_CHECK(hipEventRecord(c->efold_ev[c->tcur], c->fold_stream));
         LURK_HIP_CHECK(hipEventRecord(c->zfold_ev, c->fold_stream));
@@ -668,9 +656,9 @@ static void fold_finish(lurk_hip_fold_ctx* c, const void* r32_mont) {
         c->abc_buf = c->tcur;
         c->abc_pending = true;
         c->tcur ^= 1;
-        with_scalar_field(c->field_id, [&](auto F) { host_add_mont<decltype(F)>(c->u_host, r32_mont); });  // u <- u + r u2, u2 = 1 (a fresh instance is strict)
+        with_field(c->field_id, [&](auto F) { host_add_mont<decltype(F)>(c->u_host, r32_mont); });  // u <- u + r u2, u2 = 1 (a fresh instance is strict)
     } else {
-        ok(lurk_hip_fold_vecs_dev(c->field_id, 2, a, b, n, o, r32_mont, c->stream));
+        nested_ok(lurk_hip_fold_vecs_dev(c->field_id, 2, a, b, n, o, r32_mont, c->stream));
         LURK_HIP_CHECK(hipEventRecord(c->folded_ev[c->open_buf], c->stream));
     }
     c->folded_valid[c->open_buf] = true;
@@ -696,7 +684,7 @@ static void fold_ctx_create(lurk_hip_fold_ctx** out, int curve, lurk_hip_r1cs* s
     auto c = std::make_unique<lurk_hip_fold_ctx>();
     c->curve = curve;
     int shape_field = 0;
-    ok(lurk_hip_r1cs_dims(shape, &shape_field, &c->num_cons, &c->num_vars, &c->num_io));
+    nested_ok(lurk_hip_r1cs_dims(shape, &shape_field, &c->num_cons, &c->num_vars, &c->num_io));
     c->field_id = curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : curve == LURK_CURVE_VESTA ? LURK_FIELD_PALLAS_FP : LURK_FIELD_BN254_FR;  // the curve's scalar field
     {   // four curves share the 64-byte point layout: a key over another curve would commit to garbage without a word
         const int key_curve = key ? msm_ctx_table_view(key).curve : msm_multi_curve(mkey);
@@ -709,10 +697,10 @@ static void fold_ctx_create(lurk_hip_fold_ctx** out, int curve, lurk_hip_r1cs* s
     c->ncols = c->num_vars + 1 + c->num_io;
     // the context lives where its shape lives; a single-device key must be there too (every other handle records its device as well)
     int shape_device = 0;
-    ok(lurk_hip_r1cs_device(shape, &shape_device));
+    nested_ok(lurk_hip_r1cs_device(shape, &shape_device));
     if (key) {
         int key_device = 0;
-        ok(lurk_hip_msm_ctx_device(key, &key_device));
+        nested_ok(lurk_hip_msm_ctx_device(key, &key_device));
         LURK_REQUIRE(key_device == shape_device, "the R1CS shape and the commitment key live on different devices");
     }
     c->device = shape_device;
@@ -722,7 +710,7 @@ static void fold_ctx_create(lurk_hip_fold_ctx** out, int curve, lurk_hip_r1cs* s
         size_t total = 0;
         for (int i = 0; i < ns; i++) {
             auto sb = std::make_unique<lurk_hip_fold_ctx::ShardBuf>();
-            ok(lurk_hip_msm_multi_shard(mkey, i, &sb->device, &sb->first, &sb->count));
+            nested_ok(lurk_hip_msm_multi_shard(mkey, i, &sb->device, &sb->first, &sb->count));
             total += sb->count;
             DeviceGuard sg(sb->device);
             for (int k = 0; k < 2; k++) {
@@ -753,7 +741,7 @@ static void fold_ctx_create(lurk_hip_fold_ctx** out, int curve, lurk_hip_r1cs* s
     c->ux.assign(4 * (1 + c->num_io), 0);
     if (curve != LURK_CURVE_BN254) {  // the transcript's width-25 Poseidon constants are generated on first use (~0.15 s): now, not inside the first step
         uint64_t one[4] = {1, 0, 0, 0}, out[4];
-        ok(lurk_hip_nova_ro_squeeze(c->field_id == LURK_FIELD_PALLAS_FQ ? LURK_FIELD_PALLAS_FP : LURK_FIELD_PALLAS_FQ, one, 1, 128, out));
+        nested_ok(lurk_hip_nova_ro_squeeze(c->field_id == LURK_FIELD_PALLAS_FQ ? LURK_FIELD_PALLAS_FP : LURK_FIELD_PALLAS_FQ, one, 1, 128, out));
     }
     LURK_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     if (c->cached) {
@@ -800,8 +788,8 @@ int lurk_hip_fold_ctx_add_helper(lurk_hip_fold_ctx* c, lurk_hip_msm_ctx* helper_
         LURK_REQUIRE(!c->begun && c->n_staged == 0, "add helper keys before the first step");
         int curve = 0, device = 0;
         size_t npoints = 0;
-        ok(lurk_hip_msm_ctx_info(helper_key, &curve, &npoints, nullptr, nullptr));
-        ok(lurk_hip_msm_ctx_device(helper_key, &device));
+        nested_ok(lurk_hip_msm_ctx_info(helper_key, &curve, &npoints, nullptr, nullptr));
+        nested_ok(lurk_hip_msm_ctx_device(helper_key, &device));
         LURK_REQUIRE(curve == c->curve, "the helper key is over another curve");
         LURK_REQUIRE(npoints >= c->num_vars, "the helper key has fewer points than the witness has elements");
         auto h = std::make_unique<lurk_hip_fold_ctx::Helper>();
@@ -838,7 +826,7 @@ int lurk_hip_fold_ctx_set_running(lurk_hip_fold_ctx* c, const void* z1, const vo
         LURK_HIP_CHECK(hipMemcpyAsync(c->z[c->cur].p, z1, c->ncols * 32, hipMemcpyHostToDevice, c->stream));
         LURK_HIP_CHECK(hipMemcpyAsync(c->e[c->cur].p, e1, c->num_cons * 32, hipMemcpyHostToDevice, c->stream));
         if (c->cached) {  // the cache of the new running instance, whole; whatever fold of the old one was pending is void
-            ok(lurk_hip_r1cs_multiply_vec_dev(c->shape, c->z[c->cur].p, c->abc1[0].p, c->abc1[1].p, c->abc1[2].p, c->stream));
+            nested_ok(lurk_hip_r1cs_multiply_vec_dev(c->shape, c->z[c->cur].p, c->abc1[0].p, c->abc1[1].p, c->abc1[2].p, c->stream));
             c->abc_pending = false;
             memcpy(c->u_host, (const char*)z1 + c->num_vars * 32, 32);
         }

@@ -23,6 +23,7 @@
 #include <memory>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "field.cuh"
 #include "host_poseidon.hpp"
 
@@ -99,9 +100,7 @@ static void store_hash_node_host(int field_id, const NodeDev& nd, const uint64_t
             digest(2, nd.child_pos[0]);
             break;
     }
-    if (field_id == 0) poseidon_hash_host<PallasFp>(poseidon_host<PallasFp>((int)nd.arity), pre, out4);
-    else if (field_id == 1) poseidon_hash_host<PallasFq>(poseidon_host<PallasFq>((int)nd.arity), pre, out4);
-    else poseidon_hash_host<Bn254Fr>(poseidon_host<Bn254Fr>((int)nd.arity), pre, out4);
+    with_field(field_id, [&](auto F) { poseidon_hash_host<decltype(F)>(poseidon_host<decltype(F)>((int)nd.arity), pre, out4); });
 }
 
 static int kind_arity(uint32_t kind) {
@@ -236,22 +235,15 @@ extern "C" int lurk_hip_store_hydrate(int field_id, const lurk_hip_store_node* n
 
 // pure host computation: usable without a device (the CPU tests run the reference's golden vectors through it)
 extern "C" int lurk_hip_poseidon_hash_host(int field_id, int arity, const void* preimages, size_t n, void* digests) {
-    try {
+    return host_guarded([&] {
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
         LURK_REQUIRE(arity == 3 || arity == 4 || arity == 6 || arity == 8, "unsupported arity (3, 4, 6 or 8)");  // src/hash.rs:19-29
         LURK_REQUIRE(n == 0 || (preimages && digests), "null buffer");
         for (size_t i = 0; i < n; i++) {
             uint64_t pre[8 * 4], out[4];
             memcpy(pre, (const char*)preimages + i * (size_t)arity * 32, (size_t)arity * 32);  // caller memory carries no alignment promise
-            if (field_id == 0) poseidon_hash_host<PallasFp>(poseidon_host<PallasFp>(arity), pre, out);
-            else if (field_id == 1) poseidon_hash_host<PallasFq>(poseidon_host<PallasFq>(arity), pre, out);
-            else poseidon_hash_host<Bn254Fr>(poseidon_host<Bn254Fr>(arity), pre, out);
+            with_field(field_id, [&](auto F) { poseidon_hash_host<decltype(F)>(poseidon_host<decltype(F)>(arity), pre, out); });
             memcpy((char*)digests + i * 32, out, 32);
         }
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    }
+    });
 }

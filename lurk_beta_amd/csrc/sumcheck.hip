@@ -13,6 +13,7 @@
 #include <memory>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "field.cuh"
 #include "sumcheck_host.hpp"
 
@@ -374,9 +375,7 @@ int lurk_hip_sumcheck_round_dev(int field_id, int degree, void* const* d_polys, 
         for (int k = 0; k < np; k++) LURK_REQUIRE(d_polys[k], "null table");
         LURK_REQUIRE(evals_out || bind_r32_mont, "nothing to do");
         LURK_REQUIRE(evals_out == nullptr || bind_r32_mont == nullptr || len >= 4, "after the last bind (len = 2) there is nothing to sum: pass evals_out = NULL");
-        if (field_id == 0) sumcheck_round<PallasFp>(np, d_polys, len, bind_r32_mont, evals_out, (hipStream_t)stream);
-        else if (field_id == 1) sumcheck_round<PallasFq>(np, d_polys, len, bind_r32_mont, evals_out, (hipStream_t)stream);
-        else sumcheck_round<Bn254Fr>(np, d_polys, len, bind_r32_mont, evals_out, (hipStream_t)stream);
+        with_field(field_id, [&](auto F) { sumcheck_round<decltype(F)>(np, d_polys, len, bind_r32_mont, evals_out, (hipStream_t)stream); });
     });
 }
 
@@ -389,9 +388,10 @@ int lurk_hip_sumcheck_prove_dev(int field_id, int degree, void* const* d_polys, 
         LURK_REQUIRE(len >= 2 && (len & (len - 1)) == 0, "table length must be a power of two >= 2");
         const int np = degree == 3 ? 4 : 2;
         for (int k = 0; k < np; k++) LURK_REQUIRE(d_polys[k], "null table");
-        if (field_id == 0) sumcheck_prove<PallasFp>(np, 1, d_polys, len, nullptr, claim32_canonical, challenge, user, (uint64_t*)out_polys, (uint64_t*)out_finals, out_claim32, (hipStream_t)stream);
-        else if (field_id == 1) sumcheck_prove<PallasFq>(np, 1, d_polys, len, nullptr, claim32_canonical, challenge, user, (uint64_t*)out_polys, (uint64_t*)out_finals, out_claim32, (hipStream_t)stream);
-        else sumcheck_prove<Bn254Fr>(np, 1, d_polys, len, nullptr, claim32_canonical, challenge, user, (uint64_t*)out_polys, (uint64_t*)out_finals, out_claim32, (hipStream_t)stream);
+        with_field(field_id, [&](auto F) {
+            sumcheck_prove<decltype(F)>(np, 1, d_polys, len, nullptr, claim32_canonical, challenge, user, (uint64_t*)out_polys, (uint64_t*)out_finals, out_claim32,
+                                        (hipStream_t)stream);
+        });
     });
 }
 
@@ -406,9 +406,10 @@ int lurk_hip_sumcheck_prove_batch_dev(int field_id, int degree, size_t n_instanc
         LURK_REQUIRE(len >= 2 && (len & (len - 1)) == 0, "table length must be a power of two >= 2");
         const int np = degree == 3 ? 4 : 2;
         for (size_t k = 0; k < n_instances * (size_t)np; k++) LURK_REQUIRE(d_polys[k], "null table");
-        if (field_id == 0) sumcheck_prove<PallasFp>(np, n_instances, d_polys, len, coeffs32_canonical, claim32_canonical, challenge, user, (uint64_t*)out_polys, (uint64_t*)out_finals, out_claim32, (hipStream_t)stream);
-        else if (field_id == 1) sumcheck_prove<PallasFq>(np, n_instances, d_polys, len, coeffs32_canonical, claim32_canonical, challenge, user, (uint64_t*)out_polys, (uint64_t*)out_finals, out_claim32, (hipStream_t)stream);
-        else sumcheck_prove<Bn254Fr>(np, n_instances, d_polys, len, coeffs32_canonical, claim32_canonical, challenge, user, (uint64_t*)out_polys, (uint64_t*)out_finals, out_claim32, (hipStream_t)stream);
+        with_field(field_id, [&](auto F) {
+            sumcheck_prove<decltype(F)>(np, n_instances, d_polys, len, coeffs32_canonical, claim32_canonical, challenge, user, (uint64_t*)out_polys,
+                                        (uint64_t*)out_finals, out_claim32, (hipStream_t)stream);
+        });
     });
 }
 
@@ -426,9 +427,10 @@ int lurk_hip_eq_evals_dev(int field_id, const void* r32_mont, int ell, void* d_o
         if (blocks > cap) blocks = cap;
         const size_t lds = ((size_t)1 << lo) * 32;
         ProfScope ps("eq_evals", s);
-        if (field_id == 0) hipLaunchKernelGGL((eq_evals_kernel<PallasFp>), dim3(blocks), dim3(SC_BLOCK), lds, s, (const Fe<PallasFp>*)d_r, ell, (Fe<PallasFp>*)d_out);
-        else if (field_id == 1) hipLaunchKernelGGL((eq_evals_kernel<PallasFq>), dim3(blocks), dim3(SC_BLOCK), lds, s, (const Fe<PallasFq>*)d_r, ell, (Fe<PallasFq>*)d_out);
-        else hipLaunchKernelGGL((eq_evals_kernel<Bn254Fr>), dim3(blocks), dim3(SC_BLOCK), lds, s, (const Fe<Bn254Fr>*)d_r, ell, (Fe<Bn254Fr>*)d_out);
+        with_field(field_id, [&](auto tag) {
+            using F = decltype(tag);
+            hipLaunchKernelGGL((eq_evals_kernel<F>), dim3(blocks), dim3(SC_BLOCK), lds, s, (const Fe<F>*)d_r, ell, (Fe<F>*)d_out);
+        });
         LURK_HIP_CHECK(hipGetLastError());
     });
 }

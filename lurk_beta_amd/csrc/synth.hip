@@ -7,6 +7,7 @@
 // tests compare the two implementations element by element.
 #include "common.hpp"
 #include "curve.cuh"
+#include "dispatch.hpp"
 
 namespace lurk {
 
@@ -157,10 +158,12 @@ int lurk_hip_synth_scalars_dev(int field_id, uint64_t stream_id, int dist, size_
         LURK_REQUIRE(d_out, "null buffer");
         hipStream_t s = (hipStream_t)stream;
         dim3 grid(div_up(n, 256)), block(256);
-        if (field_id == 0) hipLaunchKernelGGL((synth_scalars_kernel<PallasFp>), grid, block, 0, s, stream_id, dist, first, n, (Fe<PallasFp>*)d_out, out_mont);
-        else if (field_id == 1) hipLaunchKernelGGL((synth_scalars_kernel<PallasFq>), grid, block, 0, s, stream_id, dist, first, n, (Fe<PallasFq>*)d_out, out_mont);
-        else if (field_id == 2) hipLaunchKernelGGL((synth_scalars_kernel<Bn254Fr>), grid, block, 0, s, stream_id, dist, first, n, (Fe<Bn254Fr>*)d_out, out_mont);
-        else hipLaunchKernelGGL((synth_scalars_kernel<Bn254Fq>), grid, block, 0, s, stream_id, dist, first, n, (Fe<Bn254Fq>*)d_out, out_mont);
+        auto launch = [&](auto tag) {
+            using F = decltype(tag);
+            hipLaunchKernelGGL((synth_scalars_kernel<F>), grid, block, 0, s, stream_id, dist, first, n, (Fe<F>*)d_out, out_mont);
+        };
+        if (field_id == LURK_FIELD_BN254_FQ) launch(Bn254Fq{});  // the fourth field is served here only
+        else with_field(field_id, launch);
         LURK_HIP_CHECK(hipGetLastError());
     });
 }
@@ -172,19 +175,11 @@ int lurk_hip_synth_bases_dev(int curve, size_t first, size_t n, void* d_out, voi
         LURK_REQUIRE(d_out, "null buffer");
         hipStream_t s = (hipStream_t)stream;
         dim3 grid(div_up(n, 256)), block(256);
-        if (curve == LURK_CURVE_PALLAS) {
-            const Affine<PallasFp>* tab = get_table<PallasFp>(0, s);
-            hipLaunchKernelGGL((synth_bases_kernel<PallasFp, PallasFq>), grid, block, 0, s, tab, first, n, (Affine<PallasFp>*)d_out);
-        } else if (curve == LURK_CURVE_VESTA) {
-            const Affine<PallasFq>* tab = get_table<PallasFq>(1, s);
-            hipLaunchKernelGGL((synth_bases_kernel<PallasFq, PallasFp>), grid, block, 0, s, tab, first, n, (Affine<PallasFq>*)d_out);
-        } else if (curve == LURK_CURVE_BN254) {
-            const Affine<Bn254Fq>* tab = get_table<Bn254Fq>(LURK_CURVE_BN254, s);
-            hipLaunchKernelGGL((synth_bases_kernel<Bn254Fq, Bn254Fr>), grid, block, 0, s, tab, first, n, (Affine<Bn254Fq>*)d_out);
-        } else {
-            const Affine<Bn254Fr>* tab = get_table<Bn254Fr>(LURK_CURVE_GRUMPKIN, s);
-            hipLaunchKernelGGL((synth_bases_kernel<Bn254Fr, Bn254Fq>), grid, block, 0, s, tab, first, n, (Affine<Bn254Fr>*)d_out);
-        }
+        with_curve(curve, [&](auto base, auto scalar) {
+            using P = decltype(base);
+            const Affine<P>* tab = get_table<P>(curve, s);
+            hipLaunchKernelGGL((synth_bases_kernel<P, decltype(scalar)>), grid, block, 0, s, tab, first, n, (Affine<P>*)d_out);
+        });
         LURK_HIP_CHECK(hipGetLastError());
     });
 }

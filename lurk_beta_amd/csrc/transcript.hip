@@ -23,6 +23,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 #include "host_poseidon.hpp"
 #include "keccak.hpp"
 
@@ -167,9 +168,7 @@ static void ro_squeeze(int field_id, const uint64_t* elems, size_t n, unsigned n
     LURK_REQUIRE(num_bits >= 1 && num_bits <= 250, "num_bits must be in 1..250");
     LURK_REQUIRE(n >= 1 && n < ((size_t)1 << 31), "absorb count out of range");
     uint32_t w[8];
-    if (field_id == 0) memcpy(w, ro_squeeze_host<PallasFp>(elems, n).l, 32);
-    else if (field_id == 1) memcpy(w, ro_squeeze_host<PallasFq>(elems, n).l, 32);
-    else memcpy(w, ro_squeeze_host<Bn254Fr>(elems, n).l, 32);
+    with_field(field_id, [&](auto F) { memcpy(w, ro_squeeze_host<decltype(F)>(elems, n).l, 32); });
     for (unsigned b = num_bits; b < 256; b++) w[b >> 5] &= ~(1u << (b & 31));
     memcpy(out4, w, 32);
 }
@@ -394,22 +393,6 @@ struct lurk_hip_keccak_transcript {
 
 using namespace lurk;
 
-// host-only entry points: no device is needed (the CPU tests compare them with oracle/pyref.py)
-template <class F>
-static int host_guarded(F&& f) {
-    try {
-        f();
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    } catch (const std::exception& e) {
-        set_error(LURK_HIP_ERR_HIP, e.what());
-        return LURK_HIP_ERR_HIP;
-    }
-}
-
 extern "C" {
 
 int lurk_hip_nova_ro_squeeze(int field_id, const void* elems32, size_t n, unsigned num_bits, void* out32) {
@@ -455,19 +438,13 @@ int lurk_hip_nifs_absorb_list(int curve, const void* pp_digest32, const void* co
         LURK_REQUIRE(num_io == 0 || (x1_mont && x2_mont), "null public IO");
         std::vector<uint64_t> el;
         uint64_t r[4];
-        if (curve == LURK_CURVE_PALLAS) {
-            NifsStages<PallasFq, PallasFp> st;
+        with_pasta_curve(curve, [&](auto base, auto scalar) {
+            NifsStages<decltype(scalar), decltype(base)> st;
             st.begin(curve, pp_digest32, comm_w1_jac96, comm_e1_jac96, u1_mont, x1_mont, num_io);
             st.fresh(comm_w2_jac96, x2_mont);
             st.finish(comm_t_jac96, r);
             el = st.absorb_list();
-        } else {
-            NifsStages<PallasFp, PallasFq> st;
-            st.begin(curve, pp_digest32, comm_w1_jac96, comm_e1_jac96, u1_mont, x1_mont, num_io);
-            st.fresh(comm_w2_jac96, x2_mont);
-            st.finish(comm_t_jac96, r);
-            el = st.absorb_list();
-        }
+        });
         *count = el.size() / 4;
         if (out_elems32) {
             LURK_REQUIRE(cap >= *count, "the output buffer is shorter than the absorb list");
@@ -483,12 +460,10 @@ int lurk_hip_nifs_challenge(int curve, const void* pp_digest32, const void* comm
         require_pasta_curve(curve, "lurk_hip_nifs_challenge (Nova's random oracle)");
         LURK_REQUIRE(pp_digest32 && comm_w1_jac96 && comm_e1_jac96 && u1_mont && comm_w2_jac96 && comm_t_jac96 && r32_mont, "null argument");
         LURK_REQUIRE(num_io == 0 || (x1_mont && x2_mont), "null public IO");
-        if (curve == LURK_CURVE_PALLAS)
-            nifs_challenge<PallasFq, PallasFp>(curve, LURK_FIELD_PALLAS_FP, pp_digest32, comm_w1_jac96, comm_e1_jac96, u1_mont, x1_mont, comm_w2_jac96,
-                                               x2_mont, num_io, comm_t_jac96, r32_mont);
-        else
-            nifs_challenge<PallasFp, PallasFq>(curve, LURK_FIELD_PALLAS_FQ, pp_digest32, comm_w1_jac96, comm_e1_jac96, u1_mont, x1_mont, comm_w2_jac96,
-                                               x2_mont, num_io, comm_t_jac96, r32_mont);
+        with_pasta_curve(curve, [&](auto base, auto scalar) {
+            nifs_challenge<decltype(scalar), decltype(base)>(curve, decltype(base)::ID, pp_digest32, comm_w1_jac96, comm_e1_jac96, u1_mont, x1_mont, comm_w2_jac96, x2_mont,
+                                                             num_io, comm_t_jac96, r32_mont);
+        });
     });
 }
 
@@ -568,9 +543,7 @@ int lurk_hip_keccak_transcript_squeeze(lurk_hip_keccak_transcript* t, const void
         memcpy(t->state, out, 64);
         t->hasher = Keccak256();
         uint64_t r[4];
-        if (field_id == 0) from_uniform64<PallasFp>(out, r);
-        else if (field_id == 1) from_uniform64<PallasFq>(out, r);
-        else from_uniform64<Bn254Fr>(out, r);
+        with_field(field_id, [&](auto F) { from_uniform64<decltype(F)>(out, r); });
         memcpy(out32_canonical, r, 32);
     });
 }

@@ -332,12 +332,14 @@ static bool point_wellformed(const void* jac96) {
     return fe_eq<B>(fe_sqr<B>(j.y), rhs);
 }
 static bool point_wellformed(int curve, const void* jac96) {
-    return curve == LURK_CURVE_PALLAS ? point_wellformed<PallasFp>(jac96) : point_wellformed<PallasFq>(jac96);
+    bool wf = false;
+    with_pasta_curve(curve, [&](auto B, auto) { wf = point_wellformed<decltype(B)>(jac96); });
+    return wf;
 }
 static bool points_equal(int curve, const void* a96, const void* b96) {
     uint64_t a[8], b[8];
-    sp_ok(lurk_hip_point_to_affine_canonical(curve, a, a96));
-    sp_ok(lurk_hip_point_to_affine_canonical(curve, b, b96));
+    nested_ok(lurk_hip_point_to_affine_canonical(curve, a, a96));
+    nested_ok(lurk_hip_point_to_affine_canonical(curve, b, b96));
     return memcmp(a, b, 64) == 0;
 }
 // acc += [k] pt (k Montgomery)
@@ -345,8 +347,8 @@ template <class F>
 static void point_mul_add(int curve, uint64_t* acc12, const void* pt96, const Fe<F>& k) {
     uint64_t two[24];
     memcpy(two, acc12, 96);
-    sp_ok(lurk_hip_point_mul(curve, two + 12, pt96, k.l, 1));
-    sp_ok(lurk_hip_point_sum(curve, acc12, two, 2));
+    nested_ok(lurk_hip_point_mul(curve, two + 12, pt96, k.l, 1));
+    nested_ok(lurk_hip_point_sum(curve, acc12, two, 2));
 }
 
 // SumcheckProof::verify: polys = rounds x (degree + 1) canonical coefficients; false when a round's p(0) + p(1) misses the claim
@@ -356,7 +358,7 @@ static bool sumcheck_verify(int degree, size_t rounds, Fe<F> claim, const void* 
     bool ok = true;
     for (size_t j = 0; j < rounds; j++) {
         Fe<F> c[4];
-        for (int k = 0; k < nc; k++) c[k] = SpField<F>::from_canonical((const char*)polys + 32 * (j * nc + k));
+        for (int k = 0; k < nc; k++) c[k] = fe_read_canonical<F>((const char*)polys + 32 * (j * nc + k));
         Fe<F> at1 = c[0];
         for (int k = 1; k < nc; k++) at1 = fe_add<F>(at1, c[k]);
         if (!fe_eq<F>(fe_add<F>(c[0], at1), claim)) ok = false;
@@ -412,7 +414,7 @@ template <class F>
 static std::vector<Fe<F>> replay_rounds(lurk_hip_keccak_transcript* t, int field_id, const void* polys, size_t rounds, int n_scalars) {
     std::vector<Fe<F>> rs(rounds);
     for (size_t j = 0; j < rounds; j++) {
-        sp_ok(lurk_hip_keccak_transcript_absorb_scalars(t, splabel::POLY, strlen(splabel::POLY), (const char*)polys + 32 * j * n_scalars, (size_t)n_scalars));
+        nested_ok(lurk_hip_keccak_transcript_absorb_scalars(t, splabel::POLY, strlen(splabel::POLY), (const char*)polys + 32 * j * n_scalars, (size_t)n_scalars));
         rs[j] = sp_squeeze<F>(t, splabel::CHALLENGE, field_id);
     }
     return rs;
@@ -435,7 +437,7 @@ static int ipa_verify(lurk_hip_msm_ctx* key, int curve, int field_id, size_t n, 
         if (challenge(user, j, (const char*)l96 + 96 * j, (const char*)r96 + 96 * j, rc) != 0)
             throw HipFailure{LURK_HIP_ERR_INVALID_ARG, "lurk_hip_ipa_verify_dev: the challenge callback failed"};
         if (!scalars_reduced<F>(rc, 1) || !(rc[0] | rc[1] | rc[2] | rc[3])) return LURK_VERIFY_MALFORMED;  // a zero challenge has no inverse
-        r[j] = SpField<F>::from_canonical(rc);
+        r[j] = fe_read_canonical<F>(rc);
     }
     const std::vector<Fe<F>> rinv = batch_invert<F>(r);
     for (int j = 0; j < ell; j++) {
@@ -446,7 +448,7 @@ static int ipa_verify(lurk_hip_msm_ctx* key, int curve, int field_id, size_t n, 
     ipa_s_vector<F>(r, rinv, d_s.p, s);
     Fe<F> b_hat;
     if (d_b) {
-        sp_ok(lurk_hip_inner_product_dev(field_id, d_s.p, d_b, n, b_hat.l, (void*)s));
+        nested_ok(lurk_hip_inner_product_dev(field_id, d_s.p, d_b, n, b_hat.l, (void*)s));
     } else {
         b_hat = fe_one<F>();
         for (int j = 0; j < ell; j++) {
@@ -455,10 +457,10 @@ static int ipa_verify(lurk_hip_msm_ctx* key, int curve, int field_id, size_t n, 
         }
     }
     uint64_t ck_hat[12];
-    sp_ok(lurk_hip_msm_ctx_run_dev(key, ck_hat, d_s.p, n, 1, (void*)s));  // (synchronises: the result is on the host)
-    const Fe<F> a_hat = SpField<F>::from_canonical(a_hat32);
+    nested_ok(lurk_hip_msm_ctx_run_dev(key, ck_hat, d_s.p, n, 1, (void*)s));  // (synchronises: the result is on the host)
+    const Fe<F> a_hat = fe_read_canonical<F>(a_hat32);
     uint64_t rhs[12];
-    sp_ok(lurk_hip_point_mul(curve, rhs, ck_hat, a_hat.l, 1));
+    nested_ok(lurk_hip_point_mul(curve, rhs, ck_hat, a_hat.l, 1));
     point_mul_add<F>(curve, rhs, ck_c96, fe_mul<F>(a_hat, b_hat));
     return points_equal(curve, p96, rhs) ? LURK_VERIFY_ACCEPTED : LURK_VERIFY_OPENING;
 }
@@ -469,7 +471,7 @@ static int open_joint(SpTranscript& tr, lurk_hip_msm_ctx* key, int curve, int fi
                       const std::vector<Fe<F>>& r_z, const void* ipa_l, const void* ipa_r, const void* ipa_a, hipStream_t s) {
     const Fe<F> r0 = sp_squeeze<F>(tr.t, splabel::IPA_R0, field_id);
     uint64_t ck_c_scaled[12];
-    sp_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
+    nested_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
     point_mul_add<F>(curve, comm_joint, ck_c_scaled, c);
     std::vector<uint64_t> keep;
     lurk_hip_keccak_round_binding b = sp_round_binding(tr.t, field_id, curve, keep, sp_log2(N), splabel::IPA_L, splabel::IPA_R, splabel::IPA_CHALLENGE, 0);
@@ -479,7 +481,7 @@ static int open_joint(SpTranscript& tr, lurk_hip_msm_ctx* key, int curve, int fi
 template <class F>
 static std::vector<Fe<F>> load_scalars(const void* p, size_t n) {
     std::vector<Fe<F>> v(n);
-    for (size_t i = 0; i < n; i++) v[i] = SpField<F>::from_canonical((const char*)p + 32 * i);
+    for (size_t i = 0; i < n; i++) v[i] = fe_read_canonical<F>((const char*)p + 32 * i);
     return v;
 }
 
@@ -511,7 +513,7 @@ static int spartan_verify(int curve, int field_id, const lurk_hip_r1cs* shape, s
     Fe<F> fin;
     bool ok = sumcheck_verify<F>(3, ell_x, fe_zero<F>(), pf->polys_outer, r_x, fin);
     const std::vector<Fe<F>> co = load_scalars<F>(pf->claims_outer, 3);
-    const Fe<F> eval_e = SpField<F>::from_canonical(pf->eval_e);
+    const Fe<F> eval_e = fe_read_canonical<F>(pf->eval_e);
     {
         const Fe<F> inner = fe_sub<F>(fe_sub<F>(fe_mul<F>(co[0], co[1]), fe_mul<F>(ux[0], co[2])), eval_e);
         if (!ok || !fe_eq<F>(fin, fe_mul<F>(eq_at<F>(tau, r_x), inner))) return LURK_VERIFY_OUTER;
@@ -522,7 +524,7 @@ static int spartan_verify(int curve, int field_id, const lurk_hip_r1cs* shape, s
     // ---- check 3: the inner sum-check against the matrices at (r_x, r_y)
     const std::vector<Fe<F>> r_y = replay_rounds<F>(tr.t, field_id, pf->polys_inner, ell_y, 3);
     ok = sumcheck_verify<F>(2, ell_y, claim_inner, pf->polys_inner, r_y, fin);
-    const Fe<F> eval_w = SpField<F>::from_canonical(pf->eval_w);
+    const Fe<F> eval_w = fe_read_canonical<F>(pf->eval_w);
     {
         Fe<F> abc3[3];
         {
@@ -676,22 +678,6 @@ static int spartan_verify_batch(int curve, int field_id, const lurk_hip_spartan_
     return open_joint<F>(tr, key, curve, field_id, N, comm_joint, c, ck_c_jac96, r_z, pf->ipa_l, pf->ipa_r, pf->ipa_a, s);
 }
 
-// host-only entry points report like lurk_hip_slot_constraints_size: no device needed
-template <class Fn>
-static int verify_host_guarded(Fn&& f) {
-    try {
-        f();
-        set_error(0, "");
-        return 0;
-    } catch (const HipFailure& e) {
-        set_error(e.code, e.msg);
-        return e.code;
-    } catch (const std::exception& e) {
-        set_error(LURK_HIP_ERR_HIP, e.what());
-        return LURK_HIP_ERR_HIP;
-    }
-}
-
 struct KeyInfo {
     int curve = 0, field_id = 0, device = 0;
     size_t points = 0;
@@ -731,9 +717,7 @@ int lurk_hip_r1cs_sparse_mle_dev(const lurk_hip_r1cs* shape, const void* d_eq_x,
         const R1csShape& sh = shape->sh;
         DeviceGuard dg(sh.device);
         alignas(16) uint64_t out[12];
-        if (sh.field_id == 0) sparse_mle<PallasFp>(sh, d_eq_x, n_x, d_eq_y, n_y, (Fe<PallasFp>*)out, (hipStream_t)stream);
-        else if (sh.field_id == 1) sparse_mle<PallasFq>(sh, d_eq_x, n_x, d_eq_y, n_y, (Fe<PallasFq>*)out, (hipStream_t)stream);
-        else sparse_mle<Bn254Fr>(sh, d_eq_x, n_x, d_eq_y, n_y, (Fe<Bn254Fr>*)out, (hipStream_t)stream);
+        with_field(sh.field_id, [&](auto F) { sparse_mle<decltype(F)>(sh, d_eq_x, n_x, d_eq_y, n_y, (Fe<decltype(F)>*)out, (hipStream_t)stream); });
         memcpy(out_abc96_mont, out, 96);
     });
 }
@@ -743,40 +727,34 @@ int lurk_hip_ipa_s_vector_dev(int field_id, const void* challenges32_canonical, 
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
         LURK_REQUIRE(ell >= 0 && ell <= 30, "ell out of range (0 .. 30)");
         LURK_REQUIRE(d_out32_mont && (ell == 0 || challenges32_canonical), "null argument");
-        auto run = [&](auto tag) {
+        with_field(field_id, [&](auto tag) {
             using F = decltype(tag);
             LURK_REQUIRE(scalars_reduced<F>(challenges32_canonical, (size_t)ell), "a challenge is not reduced modulo the field order");
             std::vector<Fe<F>> r = load_scalars<F>(challenges32_canonical, (size_t)ell);
             for (const Fe<F>& x : r) LURK_REQUIRE(!fe_is_zero<F>(x), "a zero challenge has no inverse");
             ipa_s_vector<F>(r, batch_invert<F>(r), d_out32_mont, (hipStream_t)stream);
-        };
-        if (field_id == 0) run(PallasFp{});
-        else if (field_id == 1) run(PallasFq{});
-        else run(Bn254Fr{});
+        });
     });
 }
 
 int lurk_hip_sumcheck_verify(int field_id, int degree, size_t rounds, const void* claim32_canonical, const void* polys, const void* challenges32_canonical,
                              void* out_final32_canonical, int* ok) {
-    return verify_host_guarded([&] {
+    return host_guarded([&] {
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
         LURK_REQUIRE(degree == 2 || degree == 3, "degree must be 2 or 3");
         LURK_REQUIRE(claim32_canonical && out_final32_canonical && ok && (rounds == 0 || (polys && challenges32_canonical)), "null argument");
-        auto run = [&](auto tag) {
+        with_field(field_id, [&](auto tag) {
             using F = decltype(tag);
             *ok = 0;
             memset(out_final32_canonical, 0, 32);
             if (!scalars_reduced<F>(claim32_canonical, 1) || !scalars_reduced<F>(polys, rounds * (degree + 1)) || !scalars_reduced<F>(challenges32_canonical, rounds))
                 return;
             Fe<F> fin;
-            const bool good = sumcheck_verify<F>(degree, rounds, SpField<F>::from_canonical(claim32_canonical), polys, load_scalars<F>(challenges32_canonical, rounds), fin);
+            const bool good = sumcheck_verify<F>(degree, rounds, fe_read_canonical<F>(claim32_canonical), polys, load_scalars<F>(challenges32_canonical, rounds), fin);
             if (!good) return;
-            SpField<F>::to_canonical(fin, out_final32_canonical);
+            fe_write_canonical<F>(out_final32_canonical, fin);
             *ok = 1;
-        };
-        if (field_id == 0) run(PallasFp{});
-        else if (field_id == 1) run(PallasFq{});
-        else run(Bn254Fr{});
+        });
     });
 }
 
@@ -796,18 +774,17 @@ int lurk_hip_ipa_verify_dev(lurk_hip_msm_ctx* key, size_t n, const void* p_jacob
         stream_pool_retain();
         uint64_t p[12];
         memcpy(p, p_jacobian96, 96);
-        int failed;
-        auto run = [&](auto tag) {
-            using F = decltype(tag);
+        int failed = LURK_VERIFY_MALFORMED;
+        with_pasta_curve(k.curve, [&](auto, auto SF) {
+            using F = decltype(SF);
             std::vector<Fe<F>> z;
             if (!d_b32_mont) {
-                if (!scalars_reduced<F>(eq_point32_canonical, (size_t)sp_log2(n))) return (int)LURK_VERIFY_MALFORMED;
+                if (!scalars_reduced<F>(eq_point32_canonical, (size_t)sp_log2(n))) return;
                 z = load_scalars<F>(eq_point32_canonical, (size_t)sp_log2(n));
             }
-            return ipa_verify<F>(key, k.curve, k.field_id, n, p, ck_c_jacobian96, d_b32_mont, &z, l_jacobian96, r_jacobian96, a_hat32, challenge, user,
-                                 (hipStream_t)stream);
-        };
-        failed = k.curve == LURK_CURVE_PALLAS ? run(PallasFq{}) : run(PallasFp{});
+            failed = ipa_verify<F>(key, k.curve, k.field_id, n, p, ck_c_jacobian96, d_b32_mont, &z, l_jacobian96, r_jacobian96, a_hat32, challenge, user,
+                                   (hipStream_t)stream);
+        });
         *accepted = failed == LURK_VERIFY_ACCEPTED;
         if (failed_check) *failed_check = failed;
     });
@@ -828,13 +805,11 @@ int lurk_hip_spartan_verify_dev(const lurk_hip_r1cs* shape, size_t num_cons, siz
         const KeyInfo k = key_info(key);
         check_instance_shape(shape, num_cons, num_vars, num_io, k);
         DeviceGuard dg(k.device);
-        int failed;
-        if (k.curve == LURK_CURVE_PALLAS)
-            failed = spartan_verify<PallasFq>(k.curve, k.field_id, shape, num_cons, num_vars, num_io, key, ck_c_jacobian96, x32_canonical, u32_canonical,
-                                              comm_w_jacobian96, comm_e_jacobian96, label, label_len, proof, (hipStream_t)stream);
-        else
-            failed = spartan_verify<PallasFp>(k.curve, k.field_id, shape, num_cons, num_vars, num_io, key, ck_c_jacobian96, x32_canonical, u32_canonical,
-                                              comm_w_jacobian96, comm_e_jacobian96, label, label_len, proof, (hipStream_t)stream);
+        int failed = LURK_VERIFY_MALFORMED;
+        with_pasta_curve(k.curve, [&](auto, auto SF) {
+            failed = spartan_verify<decltype(SF)>(k.curve, k.field_id, shape, num_cons, num_vars, num_io, key, ck_c_jacobian96, x32_canonical, u32_canonical,
+                                                  comm_w_jacobian96, comm_e_jacobian96, label, label_len, proof, (hipStream_t)stream);
+        });
         *accepted = failed == LURK_VERIFY_ACCEPTED;
         if (failed_check) *failed_check = failed;
     });
@@ -859,11 +834,10 @@ int lurk_hip_spartan_verify_batch_dev(const lurk_hip_spartan_instance* instances
             check_instance_shape(it.shape, it.num_cons, it.num_vars, it.num_io, k);
         }
         DeviceGuard dg(k.device);
-        int failed;
-        if (k.curve == LURK_CURVE_PALLAS)
-            failed = spartan_verify_batch<PallasFq>(k.curve, k.field_id, instances, n_instances, key, ck_c_jacobian96, label, label_len, proof, (hipStream_t)stream);
-        else
-            failed = spartan_verify_batch<PallasFp>(k.curve, k.field_id, instances, n_instances, key, ck_c_jacobian96, label, label_len, proof, (hipStream_t)stream);
+        int failed = LURK_VERIFY_MALFORMED;
+        with_pasta_curve(k.curve, [&](auto, auto SF) {
+            failed = spartan_verify_batch<decltype(SF)>(k.curve, k.field_id, instances, n_instances, key, ck_c_jacobian96, label, label_len, proof, (hipStream_t)stream);
+        });
         *accepted = failed == LURK_VERIFY_ACCEPTED;
         if (failed_check) *failed_check = failed;
     });
