@@ -50,7 +50,8 @@ extern "C" {
  * Offered: every lurk_hip_msm_* / lurk_hip_msm_ctx_* / lurk_hip_msm_multi_* commitment path, the point helpers,
  * lurk_hip_synth_bases_dev (generators (1, 2) and (1, sqrt(-16))) and lurk_hip_fold_ctx_* on BN254 with a caller-supplied challenge;
  * on BN254 G1 alone the HyperKZG opening argument (lurk_hip_hyperkzg_prove_dev, lurk_hip_hyperkzg_pairing_inputs) and the powers-of-tau
- * test key (lurk_hip_synth_kzg_bases_dev), which refuse Grumpkin and the Pasta curves by name.
+ * test key (lurk_hip_synth_kzg_bases_dev), which refuse Grumpkin and the Pasta curves by name, and the compressing SNARK whose opening
+ * is that argument (lurk_hip_spartan_kzg_prove*_dev, lurk_hip_spartan_kzg_verify*_dev; the Pasta / IPA calls keep refusing BN254).
  * Refused by name (non-zero, the curve named in lurk_hip_last_error()): lurk_hip_msm_ctx_from_label and the other hash-to-curve calls,
  * lurk_hip_msm_ctx_fold_key_dev, the IPA / Spartan / verify calls, lurk_hip_fold_step, _set_pp_digest, _challenge and
  * lurk_hip_nifs_* (no Poseidon constants over Fq yet), and a folding context on Grumpkin. */
@@ -491,6 +492,15 @@ int lurk_hip_fold_vecs_dev(int field_id, int count, const void* const* d_a, cons
 int lurk_hip_r1cs_multiply_vec(const lurk_hip_r1cs* shape, const void* z, void* az, void* bz, void* cz);
 int lurk_hip_r1cs_cross_term(lurk_hip_r1cs* shape, const void* z1, const void* z2, void* t);
 int lurk_hip_fold_vec(int field_id, const void* a, const void* b, const void* r32_mont, size_t n, void* out);
+/* A linear combination of up to 128 vectors of DIFFERENT lengths, each read as if zero-padded to n_out, in ONE launch:
+ *     d_out[j] = sum_k c_k (j < lens[k] ? d_vecs[k][j] : 0),   j < n_out
+ * - the joint polynomial W + gamma E (or sum_k gamma^k P_k over a batch) that the BN254 compressing provers open, without the padded
+ * copies: every input is read once, the output written once, nothing is cleared first.  d_vecs / lens: host arrays of `count` device
+ * pointers / element counts (the shape of lurk_hip_sumcheck_prove_dev's d_polys); coeffs: count x 32 B Montgomery, host.  Refused:
+ * count = 0, a NULL vector with a non-zero length (a zero-length vector may be NULL), lens[k] > n_out, d_out overlapping an input.
+ * The call synchronises the stream once (its table of pointers is staged from the caller's memory). */
+int lurk_hip_fold_padded_dev(int field_id, int count, const void* const* d_vecs, const size_t* lens, const void* coeffs32_mont, size_t n_out,
+                             void* d_out, void* stream);
 
 /* ---- one folding step on one curve of the cycle ----------------------------------------------
  * What RecursiveSNARK::prove_step (/root/reference/src/proof/nova.rs:282-295, SuperNova /root/reference/src/proof/
@@ -886,7 +896,7 @@ int lurk_hip_spartan_prove_batch_dev(const lurk_hip_spartan_instance* instances,
 #define LURK_VERIFY_OUTER 2     /* outer sum-check: a round, or its final claim against claims_outer / eval_e */
 #define LURK_VERIFY_INNER 3     /* inner sum-check: a round, or its final claim against the matrices at (r_x, r_y) and eval_w */
 #define LURK_VERIFY_BATCH 4     /* the sum-check that batches the evaluation claims to one point */
-#define LURK_VERIFY_OPENING 5   /* the inner-product argument's final point equation */
+#define LURK_VERIFY_OPENING 5   /* the inner-product argument's final point equation; the _kzg_ verifiers: HyperKZG's scalar checks */
 /* Building block: the sparse multilinear evaluation of a resident shape, M~ = sum_i eq_x[i] sum_{k in row i} val[k] eq_y[col[k]] for
  * M = A, B, C in ONE launch over the shape's non-empty rows (SparsePolynomial::evaluate of arecibo's Spartan verifier).  d_eq_x (n_x
  * elements), d_eq_y (n_y): Montgomery, device memory - whole eq tables or their leading parts (the batched verifier passes truncated
@@ -931,6 +941,68 @@ int lurk_hip_spartan_verify_dev(const lurk_hip_r1cs* shape, size_t num_cons, siz
 int lurk_hip_spartan_verify_batch_dev(const lurk_hip_spartan_instance* instances, size_t n_instances, lurk_hip_msm_ctx* key,
                                       const void* ck_c_jacobian96, const void* label, size_t label_len,
                                       const lurk_hip_spartan_batch_proof* proof, int* accepted, int* failed_check, void* stream);
+
+/* ---- the compressing SNARK on BN254 G1: the same sum-checks, opened by HyperKZG -----------------------------------------------------
+ * lurk-beta's default cycle is BN254 / Grumpkin, whose CompressedSNARK puts a HyperKZG evaluation engine under the Spartan sum-checks
+ * (/root/reference/src/proof/nova.rs:65-71).  The protocol is lurk_hip_spartan_prove_dev's (or _prove_batch_dev's) step for step up to and
+ * including the squeeze of gamma - same prologue, labels, absorb order, sum-checks, zero padding to N = max(num_cons, num_vars) - over
+ * LURK_FIELD_BN254_FR; tests/spartan_kzg_ref.py restates it in Python integers.  From there nothing of the inner-product argument is
+ * squeezed.  joint = sum_k gamma^k pad_N(P_k) over P = (W, E) (batched: W_0, E_0, W_1, ...; lurk_hip_fold_padded_dev), the claim is
+ * y = sum_k gamma^k evals_batch[k] at x = r_z (x_0 <-> the most significant index bit on both sides: r_z passes through unchanged),
+ * and lurk_hip_hyperkzg_prove_dev opens joint at x with its challenges bound to the same transcript:
+ *     stage 0: com_1 .. com_{ell-1} absorbed as points under "kzg_com", r squeezed under "kzg_r"  (r = 0 fails the call)
+ *     stage 1: the 3 ell values v (t-major) absorbed under "kzg_v", q squeezed under "kzg_q"
+ *     stage 2 (verifier only): W_0, W_1, W_2 absorbed under "kzg_W", d squeezed under "kzg_d"
+ * The prover compares the y of the opening with the claim: a mismatch is an internal error.  N >= 2; N = 1 cannot occur (num_cons and
+ * num_vars are at least 2) and is refused by name.
+ *   key: a resident BN254 G1 key - the powers-of-tau key that committed W and E - with at least N points; any other curve is refused by
+ *   name.  The shapes must be over LURK_FIELD_BN254_FR.  There is no inner-product base.  Every other argument as for the Pasta calls.
+ *   Outputs: the seven sum-check fields as lurk_hip_spartan_proof / _batch_proof; kzg_com (log2 N - 1) x 96 B Jacobians (may be NULL
+ *   when N = 2), kzg_v 3 log2 N x 32 B canonical (t-major), kzg_w 3 x 96 B Jacobians. */
+typedef struct lurk_hip_spartan_kzg_proof {
+    void* polys_outer;
+    void* claims_outer;
+    void* eval_e;
+    void* polys_inner;
+    void* eval_w;
+    void* polys_batch;
+    void* evals_batch;
+    void* kzg_com;
+    void* kzg_v;
+    void* kzg_w;
+} lurk_hip_spartan_kzg_proof;
+typedef struct lurk_hip_spartan_kzg_batch_proof {
+    void* polys_outer;
+    void* claims_outer;
+    void* evals_e;
+    void* polys_inner;
+    void* evals_w;
+    void* polys_batch;
+    void* evals_batch;
+    void* kzg_com;
+    void* kzg_v;
+    void* kzg_w;
+} lurk_hip_spartan_kzg_batch_proof;
+int lurk_hip_spartan_kzg_prove_dev(const lurk_hip_r1cs* shape, const lurk_hip_r1cs* shape_t, size_t num_cons, size_t num_vars, size_t num_io,
+                                   lurk_hip_msm_ctx* key, const void* x32_canonical, const void* u32_canonical, const void* d_w32_mont,
+                                   const void* d_e32_mont, const void* comm_w_jacobian96, const void* comm_e_jacobian96, const void* label,
+                                   size_t label_len, lurk_hip_spartan_kzg_proof* out, void* stream);
+int lurk_hip_spartan_kzg_prove_batch_dev(const lurk_hip_spartan_instance* instances, size_t n_instances, lurk_hip_msm_ctx* key, const void* label,
+                                         size_t label_len, lurk_hip_spartan_kzg_batch_proof* out, void* stream);
+/* The verifiers UP TO THE PAIRING, as lurk_hip_hyperkzg_pairing_inputs: the transcript replayed, the checks of lurk_hip_spartan_verify_dev /
+ * _verify_batch_dev through the batch sum-check, then on the host C = comm_W + gamma comm_E (batched: sum_k gamma^k comm_k), y, HyperKZG's
+ * scalar checks and the pairing's two G1 inputs L and R (96-byte Jacobians): the proof is valid iff *accepted and e(L, H) = e(R, [tau] H),
+ * the caller's pairing.  *accepted = 1: accepted SO FAR.  *failed_check (may be NULL): LURK_VERIFY_OUTER / INNER / BATCH as above,
+ * LURK_VERIFY_OPENING for HyperKZG's scalar checks, LURK_VERIFY_MALFORMED before any arithmetic for a scalar not below the group order or
+ * a point off the curve, and for r = 0; L and R are then the identity.  No key: HyperKZG's verifier needs only G = (1, 2).  Device work
+ * (on the shape's device): two eq tables and one sparse evaluation per shape.  The shapes must be over LURK_FIELD_BN254_FR. */
+int lurk_hip_spartan_kzg_verify_dev(const lurk_hip_r1cs* shape, size_t num_cons, size_t num_vars, size_t num_io, const void* x32_canonical,
+                                    const void* u32_canonical, const void* comm_w_jacobian96, const void* comm_e_jacobian96, const void* label,
+                                    size_t label_len, const lurk_hip_spartan_kzg_proof* proof, void* out_l_jacobian96, void* out_r_jacobian96,
+                                    int* accepted, int* failed_check, void* stream);
+int lurk_hip_spartan_kzg_verify_batch_dev(const lurk_hip_spartan_instance* instances, size_t n_instances, const void* label, size_t label_len,
+                                          const lurk_hip_spartan_kzg_batch_proof* proof, void* out_l_jacobian96, void* out_r_jacobian96,
+                                          int* accepted, int* failed_check, void* stream);
 
 /* ---- synthetic inputs (bench / tests) -------------------------------------
  * SplitMix64 counter mode, seed 0x4C55524B.  dist 0 = uniform, 1 = witness-like. */

@@ -199,6 +199,14 @@ SIGNATURES = {
     "lurk_hip_poly_div_linear_dev": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_int, ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
     "lurk_hip_hyperkzg_prove_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lurk_hip_hyperkzg_pairing_inputs": (c_int, [c_int, c_int] + [c_void_p] * 11 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "lurk_hip_fold_padded_dev": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lurk_hip_spartan_kzg_prove_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lurk_hip_spartan_kzg_prove_batch_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lurk_hip_spartan_kzg_verify_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]),
+    "lurk_hip_spartan_kzg_verify_batch_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int),
+                                                      ctypes.POINTER(c_int), c_void_p]),
 }
 
 
@@ -268,6 +276,16 @@ class SpartanInstanceStruct(ctypes.Structure):
 class SpartanBatchProofStruct(ctypes.Structure):
     """lurk_hip_spartan_batch_proof"""
     _fields_ = [(k, ctypes.c_void_p) for k in ("polys_outer", "claims_outer", "evals_e", "polys_inner", "evals_w", "polys_batch", "evals_batch", "ipa_l", "ipa_r", "ipa_a")]
+
+
+class SpartanKzgProofStruct(ctypes.Structure):
+    """lurk_hip_spartan_kzg_proof"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("polys_outer", "claims_outer", "eval_e", "polys_inner", "eval_w", "polys_batch", "evals_batch", "kzg_com", "kzg_v", "kzg_w")]
+
+
+class SpartanKzgBatchProofStruct(ctypes.Structure):
+    """lurk_hip_spartan_kzg_batch_proof"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("polys_outer", "claims_outer", "evals_e", "polys_inner", "evals_w", "polys_batch", "evals_batch", "kzg_com", "kzg_v", "kzg_w")]
 
 
 class KeccakRounds:

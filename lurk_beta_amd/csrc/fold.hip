@@ -400,6 +400,61 @@ __global__ __launch_bounds__(FOLD_BLOCK) void fold_vecs_kernel(FoldVecs v, Fe<P>
     }
 }
 
+// out[j] = sum_k c_k (j < len_k ? P_k[j] : 0) for j < n_out: the joint polynomial of the BN254 compressing provers (spartan.hip) out of
+// vectors of different lengths, without their zero-padded copies.  A pure stream bound by HBM: 32 B (sum_k len_k + n_out) per launch,
+// every input read once, the output written once, nothing cleared - W + gamma E at 2^20 x 2^20 moves 96 MiB where two memsets, two
+// copies and fold_vec move 288 MiB in five launches.  The conventions of fold_vec_kernel: a lane takes FOLD_PADDED_E elements
+// FOLD_BLOCK apart and issues the 128-bit loads of one term for all of them before the first product (8 in flight per lane), the grid
+// covers the output exactly once; like fold_vecs_kernel it adds canonically (fe_add), no lazy accumulation.  The terms (pointer,
+// length, Montgomery coefficient) are uniform reads of a small device table: up to 2 x 64 instances do not fit the kernel arguments.
+constexpr int FOLD_PADDED_E = 4;
+constexpr int FOLD_PADDED_MAX = 128;
+struct FoldPaddedTerm {
+    const uint4* p;
+    uint64_t len;
+    uint32_t c[8];
+};
+template <class P>
+__global__ __launch_bounds__(FOLD_BLOCK) void fold_padded_kernel(const FoldPaddedTerm* __restrict__ terms, int count, size_t n_out, uint4* __restrict__ out) {
+    fold_wave_prio();
+    const size_t block0 = (size_t)blockIdx.x * (FOLD_BLOCK * FOLD_PADDED_E), base = block0 + threadIdx.x;
+    Fe<P> acc[FOLD_PADDED_E];
+#pragma unroll
+    for (int e = 0; e < FOLD_PADDED_E; e++) acc[e] = fe_zero<P>();
+    for (int k = 0; k < count; k++) {
+        const size_t len = terms[k].len;
+        if (block0 >= len) continue;  // (uniform over the workgroup: this stretch of the term is padding)
+        const uint4* __restrict__ p = terms[k].p;
+        Fe<P> c;
+#pragma unroll
+        for (int i = 0; i < 8; i++) c.l[i] = terms[k].c[i];
+        uint4 lo[FOLD_PADDED_E], hi[FOLD_PADDED_E];
+#pragma unroll
+        for (int e = 0; e < FOLD_PADDED_E; e++) {
+            const size_t i = base + (size_t)e * FOLD_BLOCK;
+            if (i < len) {
+                lo[e] = p[2 * i];
+                hi[e] = p[2 * i + 1];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < FOLD_PADDED_E; e++) {
+            const size_t i = base + (size_t)e * FOLD_BLOCK;
+            if (i >= len) continue;
+            Fe<P> y;
+            y.l[0] = lo[e].x; y.l[1] = lo[e].y; y.l[2] = lo[e].z; y.l[3] = lo[e].w; y.l[4] = hi[e].x; y.l[5] = hi[e].y; y.l[6] = hi[e].z; y.l[7] = hi[e].w;
+            acc[e] = fe_add<P>(acc[e], fe_mul<P>(c, y));
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < FOLD_PADDED_E; e++) {
+        const size_t i = base + (size_t)e * FOLD_BLOCK;
+        if (i >= n_out) continue;
+        out[2 * i] = make_uint4(acc[e].l[0], acc[e].l[1], acc[e].l[2], acc[e].l[3]);
+        out[2 * i + 1] = make_uint4(acc[e].l[4], acc[e].l[5], acc[e].l[6], acc[e].l[7]);
+    }
+}
+
 // grid of the one-lane-per-row kernels: a multiple of FOLD_XCDS workgroups, so that fold_row_block is a bijection onto [0, grid)
 static unsigned fold_grid(size_t rows) {
     const unsigned nb = div_up(rows, FOLD_BLOCK);
@@ -542,6 +597,29 @@ static void fold_vec(const void* a, const void* b, const void* r32, size_t n, vo
     LURK_HIP_CHECK(hipGetLastError());
 }
 
+// the terms are staged through the stream's arena; the stream is synchronised once (pageable source: the table leaves this frame)
+template <class P>
+static void fold_padded(int count, const void* const* vecs, const size_t* lens, const void* coeffs32, size_t n_out, void* out, hipStream_t s) {
+    std::vector<FoldPaddedTerm> terms;
+    for (int k = 0; k < count; k++) {
+        if (!lens[k]) continue;  // a zero-length vector is all padding
+        FoldPaddedTerm t;
+        t.p = (const uint4*)vecs[k];
+        t.len = lens[k];
+        memcpy(t.c, (const char*)coeffs32 + 32 * (size_t)k, 32);
+        terms.push_back(t);
+    }
+    ArenaBuf d_terms((terms.size() + 1) * sizeof(FoldPaddedTerm), s);
+    if (!terms.empty()) {
+        LURK_HIP_CHECK(hipMemcpyAsync(d_terms.p, terms.data(), terms.size() * sizeof(FoldPaddedTerm), hipMemcpyHostToDevice, s));
+        LURK_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    ProfScope ps("fold_padded", s);
+    const unsigned blocks = div_up(n_out, (size_t)FOLD_BLOCK * FOLD_PADDED_E);
+    hipLaunchKernelGGL((fold_padded_kernel<P>), dim3(blocks), dim3(FOLD_BLOCK), 0, s, (const FoldPaddedTerm*)d_terms.p, (int)terms.size(), n_out, (uint4*)out);
+    LURK_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace lurk
 
 using namespace lurk;
@@ -679,6 +757,25 @@ int lurk_hip_fold_vecs_dev(int field_id, int count, const void* const* d_a, cons
         }
         LURK_REQUIRE(blocks < ((size_t)1 << 31), "too many elements for one launch");
         with_field(field_id, [&](auto F) { fold_vecs<decltype(F)>(count, d_a, d_b, n, d_out, r32_mont, (hipStream_t)stream); });
+    });
+}
+
+int lurk_hip_fold_padded_dev(int field_id, int count, const void* const* d_vecs, const size_t* lens, const void* coeffs32_mont, size_t n_out, void* d_out,
+                             void* stream) {
+    return guarded([&] {
+        LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
+        LURK_REQUIRE(count >= 1, "count must be at least 1");
+        LURK_REQUIRE(count <= FOLD_PADDED_MAX, "at most 128 vectors per launch");
+        LURK_REQUIRE(d_vecs && lens && coeffs32_mont && d_out, "null argument");
+        LURK_REQUIRE(n_out >= 1 && div_up(n_out, (size_t)FOLD_BLOCK * FOLD_PADDED_E) < (1u << 31) && n_out < ((size_t)1 << 40), "n_out out of range");
+        const char* o = (const char*)d_out;
+        for (int k = 0; k < count; k++) {
+            LURK_REQUIRE(lens[k] == 0 || d_vecs[k], "a null vector with a non-zero length");
+            LURK_REQUIRE(lens[k] <= n_out, "a vector is longer than n_out");
+            const char* v = (const char*)d_vecs[k];
+            LURK_REQUIRE(lens[k] == 0 || o + n_out * 32 <= v || v + lens[k] * 32 <= o, "the output may not overlap an input");
+        }
+        with_field(field_id, [&](auto F) { fold_padded<decltype(F)>(count, d_vecs, lens, coeffs32_mont, n_out, d_out, (hipStream_t)stream); });
     });
 }
 

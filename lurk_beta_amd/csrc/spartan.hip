@@ -11,15 +11,94 @@
 // inner products, the sum-check and inner-product round loops with the Keccak round bindings - with the vectors resident and the
 // field arithmetic of the claims on the host: lurk_beta_amd/spartan.py: SpartanProver.prove did the same from Python (0.4 ms of
 // interpreter between the sum-checks, 0.8 ms between proofs).
+#include <algorithm>
+
 #include "spartan_transcript.hpp"
 
 namespace lurk {
 
+// ---- the opening step: what the provers run after the squeeze of gamma -----------------------------------------------------------------
+// Both provers end with `count` polynomials of different lengths (raw / raw_len; `padded`: the same zero-padded to N), the powers of
+// gamma, their evaluations at r_z; the opening proves  (sum_k gamma^k pad_N(P_k))(r_z) = sum_k gamma^k evals[k].
 template <class F>
+struct SpOpenArgs {
+    SpTranscript& tr;
+    int curve, field_id;
+    size_t N;
+    size_t count;
+    const void* const* raw;
+    const size_t* raw_len;
+    const void* const* padded;
+    const Fe<F>& gamma;
+    const std::vector<Fe<F>>& evals;
+    const std::vector<Fe<F>>& r_z;
+    hipStream_t s;
+};
+
+// the inner-product argument under the resident key (the Pasta provers): joint from the padded copies by count - 1 fold_vec passes
+template <class F>
+struct IpaOpening {
+    lurk_hip_msm_ctx* key;
+    const void* ck_c_jac96;
+    void *ipa_l, *ipa_r, *ipa_a;
+    void operator()(const SpOpenArgs<F>& a) const {
+        void* vs = (void*)a.s;
+        const int ell = sp_log2(a.N);
+        SpScratch joint(a.N * 32, a.s), eq_rz(a.N * 32, a.s);
+        {
+            Fe<F> g = a.gamma;
+            for (size_t k = 1; k < a.count; k++) {  // joint = P_0 + gamma P_1, then joint += gamma^k P_k (element-wise: in place)
+                nested_ok(lurk_hip_fold_vec_dev(a.field_id, k == 1 ? a.padded[0] : joint.p, a.padded[k], g.l, a.N, joint.p, vs));
+                g = fe_mul<F>(g, a.gamma);
+            }
+        }
+        const Fe<F> r0 = sp_squeeze<F>(a.tr.t, splabel::IPA_R0, a.field_id);
+        uint64_t ck_c_scaled[12], ck_hat[8];
+        nested_ok(lurk_hip_point_mul(a.curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
+        sp_eq<F>(a.field_id, a.r_z, eq_rz.p, a.s);
+        std::vector<uint64_t> keep;
+        lurk_hip_keccak_round_binding b = sp_round_binding(a.tr.t, a.field_id, a.curve, keep, ell, splabel::IPA_L, splabel::IPA_R, splabel::IPA_CHALLENGE, 0);
+        nested_ok(lurk_hip_ipa_prove_dev(key, joint.p, eq_rz.p, a.N, ck_c_scaled, lurk_hip_keccak_ipa_challenge, &b, ipa_l, ipa_r, ipa_a, ck_hat, vs));
+    }
+};
+
+// HyperKZG under a resident BN254 G1 key: joint straight from the unpadded vectors in one pass (fold_padded_kernel), the opening's two
+// prover challenges over the same transcript (spartan_transcript.hpp: sp_kzg_stage)
+static int sp_kzg_challenge(void* user, int stage, const void* data, size_t count, void* out32_canonical) {
+    return host_guarded([&] {
+        LURK_REQUIRE(stage == 0 || stage == 1, "unknown stage");
+        const Fe<Bn254Fr> c = sp_kzg_stage<Bn254Fr>(((SpTranscript*)user)->t, stage, data, count);
+        fe_write_canonical<Bn254Fr>(out32_canonical, c);
+    });
+}
+template <class F>
+struct KzgOpening {
+    lurk_hip_msm_ctx* key;
+    void *kzg_com, *kzg_v, *kzg_w;
+    void operator()(const SpOpenArgs<F>& a) const {
+        LURK_REQUIRE(a.N >= 2, "the HyperKZG opening needs N = max(num_cons, num_vars) >= 2: N = 1 has no variable to fold");
+        SpScratch joint(a.N * 32, a.s);
+        std::vector<Fe<F>> pw(a.count);
+        Fe<F> g = fe_one<F>(), claim = fe_zero<F>();
+        for (size_t k = 0; k < a.count; k++) {
+            pw[k] = g;
+            claim = fe_add<F>(claim, fe_mul<F>(g, a.evals[k]));
+            g = fe_mul<F>(g, a.gamma);
+        }
+        nested_ok(lurk_hip_fold_padded_dev(a.field_id, (int)a.count, a.raw, a.raw_len, pw.data(), a.N, joint.p, (void*)a.s));
+        uint64_t y[4], want[4];
+        nested_ok(lurk_hip_hyperkzg_prove_dev(key, joint.p, a.N, a.r_z.data(), sp_kzg_challenge, &a.tr, kzg_com, kzg_v, kzg_w, y, (void*)a.s));
+        fe_write_canonical<F>(want, claim);
+        if (memcmp(y, want, 32) != 0)
+            throw HipFailure{LURK_HIP_ERR_HIP, "spartan_kzg: the opening's value differs from the batched evaluation claim (point order or padding)"};
+    }
+};
+
+template <class F, class Proof, class Opening>
 static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, const lurk_hip_r1cs* shape_t, size_t nc, size_t nv, size_t nio,
-                          lurk_hip_msm_ctx* key, const void* ck_c_jac96, const void* x_canonical, const void* u_canonical, const void* d_w,
+                          const void* x_canonical, const void* u_canonical, const void* d_w,
                           const void* d_e, const void* comm_w_jac96, const void* comm_e_jac96, const void* label, size_t label_len,
-                          lurk_hip_spartan_proof* out, hipStream_t s) {
+                          Proof* out, const Opening& open, hipStream_t s) {
     const int ell_x = sp_log2(nc), ell_y = sp_log2(nv) + 1;
     const size_t N = nc > nv ? nc : nv;
     const int ell = sp_log2(N);
@@ -126,15 +205,13 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
     fe_write_canonical<F>((char*)out->evals_batch + 32, ev2);
     sp_absorb<F>(tr.t, splabel::EVALS_BATCH, {ev1, ev2});
     const Fe<F> gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
-    SpScratch joint(N * 32, s), eq_rz(N * 32, s);
-    nested_ok(lurk_hip_fold_vec_dev(field_id, p1.p, p2.p, gamma.l, N, joint.p, vs));
-    const Fe<F> r0 = sp_squeeze<F>(tr.t, splabel::IPA_R0, field_id);
-    uint64_t ck_c_scaled[12], ck_hat[8];
-    nested_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
-    sp_eq<F>(field_id, r_z, eq_rz.p, s);
-    std::vector<uint64_t> keep;
-    lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::IPA_L, splabel::IPA_R, splabel::IPA_CHALLENGE);
-    nested_ok(lurk_hip_ipa_prove_dev(key, joint.p, eq_rz.p, N, ck_c_scaled, lurk_hip_keccak_ipa_challenge, &b, out->ipa_l, out->ipa_r, out->ipa_a, ck_hat, vs));
+    {
+        const void* raw[2] = {d_w, d_e};
+        const size_t raw_len[2] = {nv, nc};
+        const void* padded[2] = {p1.p, p2.p};
+        const std::vector<Fe<F>> evals = {ev1, ev2};
+        open(SpOpenArgs<F>{tr, curve, field_id, N, 2, raw, raw_len, padded, gamma, evals, r_z, s});
+    }
     LURK_HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -144,9 +221,9 @@ static void spartan_prove(int curve, int field_id, const lurk_hip_r1cs* shape, c
 // through powers of a challenge, every instance's two evaluation claims batched to one point, one opening under the resident key.
 // = lurk_beta_amd/spartan.py: BatchedSpartanProver.prove call for call (which stays as the test mirror) = oracle/spartan_fast.py:
 // prove_batched element for element; instances shorter than the largest are zero-padded, their points padded with leading zeros.
-template <class F>
-static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_instance* inst, size_t n, lurk_hip_msm_ctx* key, const void* ck_c_jac96,
-                                const void* label, size_t label_len, lurk_hip_spartan_batch_proof* out, hipStream_t s) {
+template <class F, class Proof, class Opening>
+static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_instance* inst, size_t n, const void* label, size_t label_len, Proof* out,
+                                const Opening& open, hipStream_t s) {
     void* vs = (void*)s;
     size_t max_nc = 0, max_nv = 0;
     for (size_t i = 0; i < n; i++) {
@@ -339,22 +416,64 @@ static void spartan_prove_batch(int curve, int field_id, const lurk_hip_spartan_
     }
     sp_absorb<F>(tr.t, splabel::EVALS_BATCH, evals_batch);
     const Fe<F> gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
-    Buf joint = padded_copy(polys[0]->p, N, N), eq_rz = mk(N);
     {
-        Fe<F> g = gamma;
-        for (size_t k = 1; k < 2 * n; k++) {
-            nested_ok(lurk_hip_fold_vec_dev(field_id, joint->p, polys[k]->p, g.l, N, joint->p, vs));  // joint += gamma^k poly_k (element-wise: in place)
-            g = fe_mul<F>(g, gamma);
+        std::vector<const void*> raw(2 * n), padded(2 * n);
+        std::vector<size_t> raw_len(2 * n);
+        for (size_t i = 0; i < n; i++) {
+            raw[2 * i] = inst[i].d_w32_mont;
+            raw_len[2 * i] = inst[i].num_vars;
+            raw[2 * i + 1] = inst[i].d_e32_mont;
+            raw_len[2 * i + 1] = inst[i].num_cons;
         }
+        for (size_t k = 0; k < 2 * n; k++) padded[k] = polys[k]->p;
+        open(SpOpenArgs<F>{tr, curve, field_id, N, 2 * n, raw.data(), raw_len.data(), padded.data(), gamma, evals_batch, r_z, s});
     }
-    const Fe<F> r0 = sp_squeeze<F>(tr.t, splabel::IPA_R0, field_id);
-    uint64_t ck_c_scaled[12], ck_hat[8];
-    nested_ok(lurk_hip_point_mul(curve, ck_c_scaled, ck_c_jac96, r0.l, 1));
-    sp_eq<F>(field_id, r_z, eq_rz->p, s);
-    std::vector<uint64_t> keep;
-    lurk_hip_keccak_round_binding b = binding(keep, ell, splabel::IPA_L, splabel::IPA_R, splabel::IPA_CHALLENGE, 0);
-    nested_ok(lurk_hip_ipa_prove_dev(key, joint->p, eq_rz->p, N, ck_c_scaled, lurk_hip_keccak_ipa_challenge, &b, out->ipa_l, out->ipa_r, out->ipa_a, ck_hat, vs));
     LURK_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// ---- what the entry points check before anything is launched ---------------------------------------------------------------------------
+struct SpKey {
+    int curve = 0, device = 0;
+    size_t points = 0;
+};
+static SpKey sp_key_info(const lurk_hip_msm_ctx* key) {
+    SpKey k;
+    int bits = 0;
+    if (lurk_hip_msm_ctx_info(key, &k.curve, &k.points, &bits, nullptr) != 0 || lurk_hip_msm_ctx_device(key, &k.device) != 0)
+        throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
+    return k;
+}
+// the HyperKZG provers: a key on BN254 G1, in the wording of lurk_hip_hyperkzg_prove_dev
+static void require_bn254_key(const SpKey& k, const char* what) {
+    if (k.curve != LURK_CURVE_BN254) throw HipFailure{LURK_HIP_ERR_INVALID_ARG, std::string(what) + " needs a key on BN254 G1: this key is on " + curve_name(k.curve)};
+}
+// every scratch vector of a prover is sized from (num_cons, num_vars, num_io) while the mat-vecs write what the shapes say: the two must agree
+// (the transposed shape is 2 num_vars rows over the num_cons columns, stored as num_vars = num_cons - 1, num_io = 0), and the shapes' field
+// must be the scalar field of the key's curve
+static void sp_check_instance(const lurk_hip_r1cs* shape, const lurk_hip_r1cs* shape_t, size_t num_cons, size_t num_vars, size_t num_io, const SpKey& k, int want_field,
+                              const char* whose) {
+    LURK_REQUIRE(num_cons >= 2 && (num_cons & (num_cons - 1)) == 0 && num_vars >= 2 && (num_vars & (num_vars - 1)) == 0, "num_cons and num_vars must be powers of two >= 2");
+    LURK_REQUIRE(1 + num_io <= num_vars, "the public IO does not fit the second half of z");
+    LURK_REQUIRE(k.points >= (num_cons > num_vars ? num_cons : num_vars), "the key has fewer points than the padded polynomials have elements");
+    int f = -1, ft = -1;
+    size_t c = 0, v = 0, io = 0, ct = 0, vt = 0, iot = 0;
+    if (lurk_hip_r1cs_dims(shape, &f, &c, &v, &io) != 0 || lurk_hip_r1cs_dims(shape_t, &ft, &ct, &vt, &iot) != 0)
+        throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
+    LURK_REQUIRE(c == num_cons && v == num_vars && io == num_io, std::string("shape: its (num_cons, num_vars, num_io) differ from the ") + whose);
+    LURK_REQUIRE(ct == 2 * num_vars && vt + 1 + iot == num_cons, "shape_t: not the transpose of the shape (2 num_vars rows over num_cons columns)");
+    if (want_field == LURK_FIELD_BN254_FR) {
+        LURK_REQUIRE(f == want_field && ft == want_field, "the shapes are not over LURK_FIELD_BN254_FR, the scalar field of BN254 G1");
+    } else {
+        LURK_REQUIRE(f == want_field && ft == want_field, "the shapes are not over the scalar field of the key's curve");
+    }
+}
+static void sp_check_batch(const lurk_hip_spartan_instance* instances, size_t n_instances, const SpKey& k, int want_field) {
+    for (size_t i = 0; i < n_instances; i++) {
+        const lurk_hip_spartan_instance& it = instances[i];
+        LURK_REQUIRE(it.shape && it.shape_t && it.u32_canonical && it.d_w32_mont && it.d_e32_mont && it.comm_w_jacobian96 && it.comm_e_jacobian96, "null instance field");
+        LURK_REQUIRE(it.num_io == 0 || it.x32_canonical, "null public IO");
+        sp_check_instance(it.shape, it.shape_t, it.num_cons, it.num_vars, it.num_io, k, want_field, "instance's");
+    }
 }
 
 }  // namespace lurk
@@ -371,35 +490,17 @@ int lurk_hip_spartan_prove_dev(const lurk_hip_r1cs* shape, const lurk_hip_r1cs* 
         LURK_REQUIRE(shape && shape_t && key && ck_c_jacobian96 && u32_canonical && d_w && d_e && comm_w_jacobian96 && comm_e_jacobian96 && out, "null argument");
         LURK_REQUIRE(num_io == 0 || x32_canonical, "null public IO");
         LURK_REQUIRE(label || label_len == 0, "null label");
-        LURK_REQUIRE(num_cons >= 2 && (num_cons & (num_cons - 1)) == 0 && num_vars >= 2 && (num_vars & (num_vars - 1)) == 0, "num_cons and num_vars must be powers of two >= 2");
-        LURK_REQUIRE(1 + num_io <= num_vars, "the public IO does not fit the second half of z");
         LURK_REQUIRE(out->polys_outer && out->claims_outer && out->eval_e && out->polys_inner && out->eval_w && out->polys_batch && out->evals_batch && out->ipa_l &&
                          out->ipa_r && out->ipa_a,
                      "null output buffer");
-        int curve = 0, bits = 0, device = 0;
-        size_t points = 0;
-        if (lurk_hip_msm_ctx_info(key, &curve, &points, &bits, nullptr) != 0 || lurk_hip_msm_ctx_device(key, &device) != 0)
-            throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
-        require_pasta_curve(curve, "lurk_hip_spartan_prove_dev");
-        LURK_REQUIRE(points >= (num_cons > num_vars ? num_cons : num_vars), "the key has fewer points than the padded polynomials have elements");
-        // every scratch vector below is sized from (num_cons, num_vars, num_io) while the mat-vecs write what the shapes say: the two must agree
-        // (the transposed shape is 2 num_vars rows over the num_cons columns, stored as num_vars = num_cons - 1, num_io = 0), and the shapes'
-        // field must be the scalar field of the key's curve
-        {
-            const int want_field = curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : LURK_FIELD_PALLAS_FP;
-            int f = -1, ft = -1;
-            size_t c = 0, v = 0, io = 0, ct = 0, vt = 0, iot = 0;
-            if (lurk_hip_r1cs_dims(shape, &f, &c, &v, &io) != 0 || lurk_hip_r1cs_dims(shape_t, &ft, &ct, &vt, &iot) != 0)
-                throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
-            LURK_REQUIRE(c == num_cons && v == num_vars && io == num_io, "shape: its (num_cons, num_vars, num_io) differ from the arguments");
-            LURK_REQUIRE(ct == 2 * num_vars && vt + 1 + iot == num_cons, "shape_t: not the transpose of the shape (2 num_vars rows over num_cons columns)");
-            LURK_REQUIRE(f == want_field && ft == want_field, "the shapes are not over the scalar field of the key's curve");
-        }
-        DeviceGuard dg(device);
-        with_pasta_curve(curve, [&](auto, auto SF) {
+        const SpKey k = sp_key_info(key);
+        require_pasta_curve(k.curve, "lurk_hip_spartan_prove_dev");
+        sp_check_instance(shape, shape_t, num_cons, num_vars, num_io, k, k.curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : LURK_FIELD_PALLAS_FP, "arguments");
+        DeviceGuard dg(k.device);
+        with_pasta_curve(k.curve, [&](auto, auto SF) {
             using F = decltype(SF);
-            spartan_prove<F>(curve, F::ID, shape, shape_t, num_cons, num_vars, num_io, key, ck_c_jacobian96, x32_canonical, u32_canonical, d_w, d_e, comm_w_jacobian96,
-                             comm_e_jacobian96, label, label_len, out, (hipStream_t)stream);
+            spartan_prove<F>(k.curve, F::ID, shape, shape_t, num_cons, num_vars, num_io, x32_canonical, u32_canonical, d_w, d_e, comm_w_jacobian96, comm_e_jacobian96,
+                             label, label_len, out, IpaOpening<F>{key, ck_c_jacobian96, out->ipa_l, out->ipa_r, out->ipa_a}, (hipStream_t)stream);
         });
     });
 }
@@ -412,33 +513,56 @@ int lurk_hip_spartan_prove_batch_dev(const lurk_hip_spartan_instance* instances,
         LURK_REQUIRE(out->polys_outer && out->claims_outer && out->evals_e && out->polys_inner && out->evals_w && out->polys_batch && out->evals_batch && out->ipa_l &&
                          out->ipa_r && out->ipa_a,
                      "null output buffer");
-        int curve = 0, bits = 0, device = 0;
-        size_t points = 0;
-        if (lurk_hip_msm_ctx_info(key, &curve, &points, &bits, nullptr) != 0 || lurk_hip_msm_ctx_device(key, &device) != 0)
-            throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
-        require_pasta_curve(curve, "lurk_hip_spartan_prove_batch_dev");
-        const int want_field = curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : LURK_FIELD_PALLAS_FP;
-        for (size_t i = 0; i < n_instances; i++) {
-            const lurk_hip_spartan_instance& it = instances[i];
-            LURK_REQUIRE(it.shape && it.shape_t && it.u32_canonical && it.d_w32_mont && it.d_e32_mont && it.comm_w_jacobian96 && it.comm_e_jacobian96, "null instance field");
-            LURK_REQUIRE(it.num_io == 0 || it.x32_canonical, "null public IO");
-            LURK_REQUIRE(it.num_cons >= 2 && (it.num_cons & (it.num_cons - 1)) == 0 && it.num_vars >= 2 && (it.num_vars & (it.num_vars - 1)) == 0,
-                         "num_cons and num_vars must be powers of two >= 2");
-            LURK_REQUIRE(1 + it.num_io <= it.num_vars, "the public IO does not fit the second half of z");
-            LURK_REQUIRE(points >= (it.num_cons > it.num_vars ? it.num_cons : it.num_vars), "the key has fewer points than the padded polynomials have elements");
-            int f = -1, ft = -1;
-            size_t c = 0, v = 0, io = 0, ct = 0, vt = 0, iot = 0;
-            if (lurk_hip_r1cs_dims(it.shape, &f, &c, &v, &io) != 0 || lurk_hip_r1cs_dims(it.shape_t, &ft, &ct, &vt, &iot) != 0)
-                throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
-            LURK_REQUIRE(c == it.num_cons && v == it.num_vars && io == it.num_io, "shape: its (num_cons, num_vars, num_io) differ from the instance's");
-            LURK_REQUIRE(ct == 2 * it.num_vars && vt + 1 + iot == it.num_cons, "shape_t: not the transpose of the shape (2 num_vars rows over num_cons columns)");
-            LURK_REQUIRE(f == want_field && ft == want_field, "the shapes are not over the scalar field of the key's curve");
-        }
-        DeviceGuard dg(device);
-        with_pasta_curve(curve, [&](auto, auto SF) {
+        const SpKey k = sp_key_info(key);
+        require_pasta_curve(k.curve, "lurk_hip_spartan_prove_batch_dev");
+        sp_check_batch(instances, n_instances, k, k.curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : LURK_FIELD_PALLAS_FP);
+        DeviceGuard dg(k.device);
+        with_pasta_curve(k.curve, [&](auto, auto SF) {
             using F = decltype(SF);
-            spartan_prove_batch<F>(curve, F::ID, instances, n_instances, key, ck_c_jacobian96, label, label_len, out, (hipStream_t)stream);
+            spartan_prove_batch<F>(k.curve, F::ID, instances, n_instances, label, label_len, out, IpaOpening<F>{key, ck_c_jacobian96, out->ipa_l, out->ipa_r, out->ipa_a},
+                                   (hipStream_t)stream);
         });
+    });
+}
+
+int lurk_hip_spartan_kzg_prove_dev(const lurk_hip_r1cs* shape, const lurk_hip_r1cs* shape_t, size_t num_cons, size_t num_vars, size_t num_io, lurk_hip_msm_ctx* key,
+                                   const void* x32_canonical, const void* u32_canonical, const void* d_w, const void* d_e, const void* comm_w_jacobian96,
+                                   const void* comm_e_jacobian96, const void* label, size_t label_len, lurk_hip_spartan_kzg_proof* out, void* stream) {
+    return guarded([&] {
+        LURK_REQUIRE(shape && shape_t && key && u32_canonical && d_w && d_e && comm_w_jacobian96 && comm_e_jacobian96 && out, "null argument");
+        LURK_REQUIRE(num_io == 0 || x32_canonical, "null public IO");
+        LURK_REQUIRE(label || label_len == 0, "null label");
+        const SpKey k = sp_key_info(key);
+        require_bn254_key(k, "lurk_hip_spartan_kzg_prove_dev");
+        LURK_REQUIRE((num_cons > num_vars ? num_cons : num_vars) != 1, "N = max(num_cons, num_vars) = 1: the HyperKZG opening needs N >= 2");
+        sp_check_instance(shape, shape_t, num_cons, num_vars, num_io, k, LURK_FIELD_BN254_FR, "arguments");
+        LURK_REQUIRE(out->polys_outer && out->claims_outer && out->eval_e && out->polys_inner && out->eval_w && out->polys_batch && out->evals_batch && out->kzg_v &&
+                         out->kzg_w && (out->kzg_com || (num_cons == 2 && num_vars == 2)),
+                     "null output buffer");
+        DeviceGuard dg(k.device);
+        using F = Bn254Fr;
+        spartan_prove<F>(k.curve, F::ID, shape, shape_t, num_cons, num_vars, num_io, x32_canonical, u32_canonical, d_w, d_e, comm_w_jacobian96, comm_e_jacobian96, label,
+                         label_len, out, KzgOpening<F>{key, out->kzg_com, out->kzg_v, out->kzg_w}, (hipStream_t)stream);
+    });
+}
+
+int lurk_hip_spartan_kzg_prove_batch_dev(const lurk_hip_spartan_instance* instances, size_t n_instances, lurk_hip_msm_ctx* key, const void* label, size_t label_len,
+                                         lurk_hip_spartan_kzg_batch_proof* out, void* stream) {
+    return guarded([&] {
+        LURK_REQUIRE(instances && n_instances >= 1 && n_instances <= 64 && key && out, "null argument, or not 1..64 instances");
+        LURK_REQUIRE(label || label_len == 0, "null label");
+        const SpKey k = sp_key_info(key);
+        require_bn254_key(k, "lurk_hip_spartan_kzg_prove_batch_dev");
+        size_t N = 0;
+        for (size_t i = 0; i < n_instances; i++) N = std::max(N, std::max(instances[i].num_cons, instances[i].num_vars));
+        LURK_REQUIRE(N != 1, "N = max(num_cons, num_vars) = 1: the HyperKZG opening needs N >= 2");
+        sp_check_batch(instances, n_instances, k, LURK_FIELD_BN254_FR);
+        LURK_REQUIRE(out->polys_outer && out->claims_outer && out->evals_e && out->polys_inner && out->evals_w && out->polys_batch && out->evals_batch && out->kzg_v &&
+                         out->kzg_w && (out->kzg_com || N == 2),
+                     "null output buffer");
+        DeviceGuard dg(k.device);
+        using F = Bn254Fr;
+        spartan_prove_batch<F>(k.curve, F::ID, instances, n_instances, label, label_len, out, KzgOpening<F>{key, out->kzg_com, out->kzg_v, out->kzg_w}, (hipStream_t)stream);
     });
 }
 }

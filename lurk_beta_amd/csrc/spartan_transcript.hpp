@@ -32,6 +32,13 @@ constexpr const char* IPA_R0 = "ipa_r0";
 constexpr const char* IPA_L = "L";
 constexpr const char* IPA_R = "R";
 constexpr const char* IPA_CHALLENGE = "r";
+// the HyperKZG opening of the BN254 provers (tests/spartan_kzg_ref.py)
+constexpr const char* KZG_COM = "kzg_com";
+constexpr const char* KZG_R = "kzg_r";
+constexpr const char* KZG_V = "kzg_v";
+constexpr const char* KZG_Q = "kzg_q";
+constexpr const char* KZG_W = "kzg_W";
+constexpr const char* KZG_D = "kzg_d";
 }  // namespace splabel
 
 using SpScratch = ArenaBuf;  // scratch vectors come off the stream's arena (common.hpp): a push, not a hipMallocAsync
@@ -74,6 +81,21 @@ static int sp_log2(size_t n) {
     int k = 0;
     while (((size_t)1 << k) < n) k++;
     return k;
+}
+
+// the challenge of a stage of the HyperKZG opening over the transcript: stage 0 absorbs `count` 96-byte Jacobians of BN254 G1 (com_1 ..
+// com_{ell-1}), stage 1 `count` canonical scalars (v, t-major), stage 2 (the verifier's) the three W_t; prover and verifier both come here
+template <class F>
+static Fe<F> sp_kzg_stage(lurk_hip_keccak_transcript* t, int stage, const void* data, size_t count) {
+    const char* absorb = stage == 0 ? splabel::KZG_COM : stage == 1 ? splabel::KZG_V : splabel::KZG_W;
+    const char* squeeze = stage == 0 ? splabel::KZG_R : stage == 1 ? splabel::KZG_Q : splabel::KZG_D;
+    if (stage == 1) {
+        nested_ok(lurk_hip_keccak_transcript_absorb_scalars(t, absorb, strlen(absorb), data, count));
+    } else {
+        for (size_t i = 0; i < count; i++)
+            nested_ok(lurk_hip_keccak_transcript_absorb_point(t, absorb, strlen(absorb), LURK_CURVE_BN254, (const char*)data + 96 * i));
+    }
+    return sp_squeeze<F>(t, squeeze, F::ID);
 }
 
 // ---- the prologues: everything absorbed before the first challenge ---------------------------------------------------------------

@@ -320,20 +320,22 @@ static bool scalars_reduced(const void* p, size_t n) {
     }
     return true;
 }
-// a 96-byte Jacobian over the base field B: the identity (z = 0), or reduced coordinates with Y^2 = X^3 + 5 Z^6 (both Pasta curves)
+// a 96-byte Jacobian over the base field B: the identity (z = 0), or reduced coordinates with Y^2 = X^3 + b Z^6 (b = 5 on both Pasta
+// curves, 3 on BN254 G1)
 template <class B>
-static bool point_wellformed(const void* jac96) {
+static bool point_wellformed(const void* jac96, uint64_t b) {
     Jacobian<B> j;
     memcpy(&j, jac96, 96);
     if (fe_canonical_ge_mod<B>(j.x.l) || fe_canonical_ge_mod<B>(j.y.l) || fe_canonical_ge_mod<B>(j.z.l)) return false;
     if (fe_is_zero<B>(j.z)) return true;
     const Fe<B> z2 = fe_sqr<B>(j.z), z6 = fe_mul<B>(fe_sqr<B>(z2), z2);
-    const Fe<B> rhs = fe_add<B>(fe_mul<B>(fe_sqr<B>(j.x), j.x), fe_mul<B>(fe_from_u64<B>(5), z6));
+    const Fe<B> rhs = fe_add<B>(fe_mul<B>(fe_sqr<B>(j.x), j.x), fe_mul<B>(fe_from_u64<B>(b), z6));
     return fe_eq<B>(fe_sqr<B>(j.y), rhs);
 }
 static bool point_wellformed(int curve, const void* jac96) {
+    if (curve == LURK_CURVE_BN254) return point_wellformed<Bn254Fq>(jac96, 3);
     bool wf = false;
-    with_pasta_curve(curve, [&](auto B, auto) { wf = point_wellformed<decltype(B)>(jac96); });
+    with_pasta_curve(curve, [&](auto B, auto) { wf = point_wellformed<decltype(B)>(jac96, 5); });
     return wf;
 }
 static bool points_equal(int curve, const void* a96, const void* b96) {
@@ -485,25 +487,32 @@ static std::vector<Fe<F>> load_scalars(const void* p, size_t n) {
     return v;
 }
 
-// oracle/spartan_fast.py: verify.  Returns the failed check.
+// What a verifier holds when the transcript has given gamma: the point r_z and the claimed evaluations of the polynomials there.  The
+// two openings (the inner-product argument on the Pasta curves, HyperKZG on BN254 G1) continue from here over the same transcript.
 template <class F>
-static int spartan_verify(int curve, int field_id, const lurk_hip_r1cs* shape, size_t nc, size_t nv, size_t nio, lurk_hip_msm_ctx* key, const void* ck_c_jac96,
-                          const void* x_canonical, const void* u_canonical, const void* comm_w_jac96, const void* comm_e_jac96, const void* label, size_t label_len,
-                          const lurk_hip_spartan_proof* pf, hipStream_t s) {
+struct SpFront {
+    SpTranscript tr;
+    Fe<F> gamma;
+    std::vector<Fe<F>> r_z, eb;
+};
+
+// oracle/spartan_fast.py: verify, checks 1 to 4 (the opening's own fields are checked for form by the caller, before this).  Returns
+// the failed check.
+template <class F, class Proof>
+static int spartan_verify_front(int curve, int field_id, const lurk_hip_r1cs* shape, size_t nc, size_t nv, size_t nio, const void* x_canonical,
+                                const void* u_canonical, const void* comm_w_jac96, const void* comm_e_jac96, const void* label, size_t label_len, const Proof* pf,
+                                SpFront<F>& fr, hipStream_t s) {
     const int ell_x = sp_log2(nc), ell_y = sp_log2(nv) + 1;
     const size_t N = nc > nv ? nc : nv;
     const int ell = sp_log2(N);
+    SpTranscript& tr = fr.tr;
     // ---- check 1: nothing malformed enters the arithmetic
     if (!scalars_reduced<F>(u_canonical, 1) || !scalars_reduced<F>(x_canonical, nio) || !scalars_reduced<F>(pf->polys_outer, (size_t)ell_x * 4) ||
         !scalars_reduced<F>(pf->claims_outer, 3) || !scalars_reduced<F>(pf->eval_e, 1) || !scalars_reduced<F>(pf->polys_inner, (size_t)ell_y * 3) ||
-        !scalars_reduced<F>(pf->eval_w, 1) || !scalars_reduced<F>(pf->polys_batch, (size_t)ell * 3) || !scalars_reduced<F>(pf->evals_batch, 2) ||
-        !scalars_reduced<F>(pf->ipa_a, 1))
+        !scalars_reduced<F>(pf->eval_w, 1) || !scalars_reduced<F>(pf->polys_batch, (size_t)ell * 3) || !scalars_reduced<F>(pf->evals_batch, 2))
         return LURK_VERIFY_MALFORMED;
     if (!point_wellformed(curve, comm_w_jac96) || !point_wellformed(curve, comm_e_jac96)) return LURK_VERIFY_MALFORMED;
-    for (int j = 0; j < ell; j++)
-        if (!point_wellformed(curve, (const char*)pf->ipa_l + 96 * j) || !point_wellformed(curve, (const char*)pf->ipa_r + 96 * j)) return LURK_VERIFY_MALFORMED;
     stream_pool_retain();
-    SpTranscript tr;
     std::vector<Fe<F>> ux;
     sp_prologue<F>(tr, curve, label, label_len, comm_w_jac96, comm_e_jac96, u_canonical, x_canonical, nio, ux);
     std::vector<Fe<F>> tau(ell_x);
@@ -544,24 +553,85 @@ static int spartan_verify(int curve, int field_id, const lurk_hip_r1cs* shape, s
     x1.insert(x1.end(), r_y.begin() + 1, r_y.end());
     x2.insert(x2.end(), r_x.begin(), r_x.end());
     const Fe<F> rho = sp_squeeze<F>(tr.t, splabel::RHO, field_id);
-    const std::vector<Fe<F>> r_z = replay_rounds<F>(tr.t, field_id, pf->polys_batch, ell, 3);
-    ok = sumcheck_verify<F>(2, ell, fe_add<F>(eval_w, fe_mul<F>(rho, eval_e)), pf->polys_batch, r_z, fin);
-    const std::vector<Fe<F>> eb = load_scalars<F>(pf->evals_batch, 2);
-    if (!ok || !fe_eq<F>(fin, fe_add<F>(fe_mul<F>(eq_at<F>(x1, r_z), eb[0]), fe_mul<F>(rho, fe_mul<F>(eq_at<F>(x2, r_z), eb[1]))))) return LURK_VERIFY_BATCH;
-    sp_absorb<F>(tr.t, splabel::EVALS_BATCH, {eb[0], eb[1]});
-    const Fe<F> gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
-    // ---- check 5: the opening of comm_W + gamma comm_E at r_z
-    uint64_t comm_joint[12];
-    memcpy(comm_joint, comm_w_jac96, 96);
-    point_mul_add<F>(curve, comm_joint, comm_e_jac96, gamma);
-    const Fe<F> c = fe_add<F>(eb[0], fe_mul<F>(gamma, eb[1]));
-    return open_joint<F>(tr, key, curve, field_id, N, comm_joint, c, ck_c_jac96, r_z, pf->ipa_l, pf->ipa_r, pf->ipa_a, s);
+    fr.r_z = replay_rounds<F>(tr.t, field_id, pf->polys_batch, ell, 3);
+    ok = sumcheck_verify<F>(2, ell, fe_add<F>(eval_w, fe_mul<F>(rho, eval_e)), pf->polys_batch, fr.r_z, fin);
+    fr.eb = load_scalars<F>(pf->evals_batch, 2);
+    if (!ok || !fe_eq<F>(fin, fe_add<F>(fe_mul<F>(eq_at<F>(x1, fr.r_z), fr.eb[0]), fe_mul<F>(rho, fe_mul<F>(eq_at<F>(x2, fr.r_z), fr.eb[1]))))) return LURK_VERIFY_BATCH;
+    sp_absorb<F>(tr.t, splabel::EVALS_BATCH, {fr.eb[0], fr.eb[1]});
+    fr.gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
+    return LURK_VERIFY_ACCEPTED;
 }
 
-// oracle/spartan_fast.py: verify_batched
+// the Pasta verifier: the front, then check 5, the opening of comm_W + gamma comm_E at r_z by the inner-product argument
 template <class F>
-static int spartan_verify_batch(int curve, int field_id, const lurk_hip_spartan_instance* inst, size_t n, lurk_hip_msm_ctx* key, const void* ck_c_jac96,
-                                const void* label, size_t label_len, const lurk_hip_spartan_batch_proof* pf, hipStream_t s) {
+static int spartan_verify(int curve, int field_id, const lurk_hip_r1cs* shape, size_t nc, size_t nv, size_t nio, lurk_hip_msm_ctx* key, const void* ck_c_jac96,
+                          const void* x_canonical, const void* u_canonical, const void* comm_w_jac96, const void* comm_e_jac96, const void* label, size_t label_len,
+                          const lurk_hip_spartan_proof* pf, hipStream_t s) {
+    const size_t N = nc > nv ? nc : nv;
+    if (!scalars_reduced<F>(pf->ipa_a, 1)) return LURK_VERIFY_MALFORMED;
+    for (int j = 0; j < sp_log2(N); j++)
+        if (!point_wellformed(curve, (const char*)pf->ipa_l + 96 * j) || !point_wellformed(curve, (const char*)pf->ipa_r + 96 * j)) return LURK_VERIFY_MALFORMED;
+    SpFront<F> fr;
+    const int failed = spartan_verify_front<F>(curve, field_id, shape, nc, nv, nio, x_canonical, u_canonical, comm_w_jac96, comm_e_jac96, label, label_len, pf, fr, s);
+    if (failed != LURK_VERIFY_ACCEPTED) return failed;
+    uint64_t comm_joint[12];
+    memcpy(comm_joint, comm_w_jac96, 96);
+    point_mul_add<F>(curve, comm_joint, comm_e_jac96, fr.gamma);
+    const Fe<F> c = fe_add<F>(fr.eb[0], fe_mul<F>(fr.gamma, fr.eb[1]));
+    return open_joint<F>(fr.tr, key, curve, field_id, N, comm_joint, c, ck_c_jac96, fr.r_z, pf->ipa_l, pf->ipa_r, pf->ipa_a, s);
+}
+
+// The HyperKZG tail shared by the two BN254 verifiers: C and y are the caller's combinations; the three challenges come off the transcript
+// in the prover's order (sp_kzg_stage), then lurk_hip_hyperkzg_pairing_inputs runs the scalar checks and forms L and R.
+static bool kzg_fields_wellformed(int ell, const void* kzg_com, const void* kzg_v, const void* kzg_w) {
+    if (!scalars_reduced<Bn254Fr>(kzg_v, (size_t)3 * ell)) return false;
+    for (int i = 0; i + 1 < ell; i++)
+        if (!point_wellformed(LURK_CURVE_BN254, (const char*)kzg_com + 96 * i)) return false;
+    for (int t = 0; t < 3; t++)
+        if (!point_wellformed(LURK_CURVE_BN254, (const char*)kzg_w + 96 * t)) return false;
+    return true;
+}
+static int kzg_open_joint(SpFront<Bn254Fr>& fr, int ell, const uint64_t* comm_joint, const Fe<Bn254Fr>& y, const void* kzg_com, const void* kzg_v, const void* kzg_w,
+                          void* out_l, void* out_r) {
+    using F = Bn254Fr;
+    const Fe<F> r = sp_kzg_stage<F>(fr.tr.t, 0, kzg_com, (size_t)(ell - 1));
+    if (fe_is_zero<F>(r)) return LURK_VERIFY_MALFORMED;
+    const Fe<F> q = sp_kzg_stage<F>(fr.tr.t, 1, kzg_v, (size_t)3 * ell), d = sp_kzg_stage<F>(fr.tr.t, 2, kzg_w, 3);
+    std::vector<uint64_t> x((size_t)4 * ell);
+    for (int i = 0; i < ell; i++) fe_write_canonical<F>(x.data() + 4 * i, fr.r_z[i]);
+    uint64_t yc[4], rc[4], qc[4], dc[4];
+    fe_write_canonical<F>(yc, y);
+    fe_write_canonical<F>(rc, r);
+    fe_write_canonical<F>(qc, q);
+    fe_write_canonical<F>(dc, d);
+    int accepted = 0, hk_failed = 0;
+    nested_ok(lurk_hip_hyperkzg_pairing_inputs(LURK_CURVE_BN254, ell, comm_joint, x.data(), yc, ell > 1 ? kzg_com : (const void*)comm_joint, kzg_v, kzg_w, rc, qc, dc,
+                                               out_l, out_r, &accepted, &hk_failed));
+    if (accepted) return LURK_VERIFY_ACCEPTED;
+    return hk_failed == LURK_HYPERKZG_MALFORMED ? LURK_VERIFY_MALFORMED : LURK_VERIFY_OPENING;
+}
+
+// tests/spartan_kzg_ref.py: verify.  L and R are the identity unless the proof is accepted so far.
+static int spartan_kzg_verify(const lurk_hip_r1cs* shape, size_t nc, size_t nv, size_t nio, const void* x_canonical, const void* u_canonical, const void* comm_w_jac96,
+                              const void* comm_e_jac96, const void* label, size_t label_len, const lurk_hip_spartan_kzg_proof* pf, void* out_l, void* out_r,
+                              hipStream_t s) {
+    using F = Bn254Fr;
+    const int curve = LURK_CURVE_BN254, ell = sp_log2(nc > nv ? nc : nv);
+    if (!kzg_fields_wellformed(ell, pf->kzg_com, pf->kzg_v, pf->kzg_w)) return LURK_VERIFY_MALFORMED;
+    SpFront<F> fr;
+    const int failed = spartan_verify_front<F>(curve, F::ID, shape, nc, nv, nio, x_canonical, u_canonical, comm_w_jac96, comm_e_jac96, label, label_len, pf, fr, s);
+    if (failed != LURK_VERIFY_ACCEPTED) return failed;
+    uint64_t comm_joint[12];
+    memcpy(comm_joint, comm_w_jac96, 96);
+    point_mul_add<F>(curve, comm_joint, comm_e_jac96, fr.gamma);
+    const Fe<F> y = fe_add<F>(fr.eb[0], fe_mul<F>(fr.gamma, fr.eb[1]));
+    return kzg_open_joint(fr, ell, comm_joint, y, pf->kzg_com, pf->kzg_v, pf->kzg_w, out_l, out_r);
+}
+
+// oracle/spartan_fast.py: verify_batched, checks 1 to 4 (as spartan_verify_front)
+template <class F, class Proof>
+static int spartan_verify_batch_front(int curve, int field_id, const lurk_hip_spartan_instance* inst, size_t n, const void* label, size_t label_len, const Proof* pf,
+                                      SpFront<F>& fr, hipStream_t s) {
     size_t max_nc = 0, max_nv = 0;
     for (size_t i = 0; i < n; i++) {
         max_nc = std::max(max_nc, inst[i].num_cons);
@@ -577,12 +647,10 @@ static int spartan_verify_batch(int curve, int field_id, const lurk_hip_spartan_
     }
     if (!scalars_reduced<F>(pf->polys_outer, (size_t)ell_x * 4) || !scalars_reduced<F>(pf->claims_outer, 3 * n) || !scalars_reduced<F>(pf->evals_e, n) ||
         !scalars_reduced<F>(pf->polys_inner, (size_t)ell_y * 3) || !scalars_reduced<F>(pf->evals_w, n) || !scalars_reduced<F>(pf->polys_batch, (size_t)ell * 3) ||
-        !scalars_reduced<F>(pf->evals_batch, 2 * n) || !scalars_reduced<F>(pf->ipa_a, 1))
+        !scalars_reduced<F>(pf->evals_batch, 2 * n))
         return LURK_VERIFY_MALFORMED;
-    for (int j = 0; j < ell; j++)
-        if (!point_wellformed(curve, (const char*)pf->ipa_l + 96 * j) || !point_wellformed(curve, (const char*)pf->ipa_r + 96 * j)) return LURK_VERIFY_MALFORMED;
     stream_pool_retain();
-    SpTranscript tr;
+    SpTranscript& tr = fr.tr;
     std::vector<std::vector<Fe<F>>> ux;
     sp_prologue_batch<F>(tr, curve, label, label_len, inst, n, ux);
     std::vector<Fe<F>> tau(ell_x);
@@ -656,26 +724,64 @@ static int spartan_verify_batch(int curve, int field_id, const lurk_hip_spartan_
     const std::vector<Fe<F>> pw = powers_of<F>(rho, 2 * n);
     Fe<F> claim = fe_zero<F>();
     for (size_t k = 0; k < 2 * n; k++) claim = fe_add<F>(claim, fe_mul<F>(pw[k], claims[k]));
-    const std::vector<Fe<F>> r_z = replay_rounds<F>(tr.t, field_id, pf->polys_batch, ell, 3);
-    ok = sumcheck_verify<F>(2, ell, claim, pf->polys_batch, r_z, fin);
-    const std::vector<Fe<F>> eb = load_scalars<F>(pf->evals_batch, 2 * n);
+    fr.r_z = replay_rounds<F>(tr.t, field_id, pf->polys_batch, ell, 3);
+    ok = sumcheck_verify<F>(2, ell, claim, pf->polys_batch, fr.r_z, fin);
+    fr.eb = load_scalars<F>(pf->evals_batch, 2 * n);
     {
         Fe<F> want = fe_zero<F>();
-        for (size_t k = 0; k < 2 * n; k++) want = fe_add<F>(want, fe_mul<F>(fe_mul<F>(pw[k], eq_at<F>(points[k], r_z)), eb[k]));
+        for (size_t k = 0; k < 2 * n; k++) want = fe_add<F>(want, fe_mul<F>(fe_mul<F>(pw[k], eq_at<F>(points[k], fr.r_z)), fr.eb[k]));
         if (!ok || !fe_eq<F>(fin, want)) return LURK_VERIFY_BATCH;
     }
-    sp_absorb<F>(tr.t, splabel::EVALS_BATCH, eb);
-    const Fe<F> gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
-    // ---- check 5
-    const std::vector<Fe<F>> pg = powers_of<F>(gamma, 2 * n);
-    uint64_t comm_joint[12];
+    sp_absorb<F>(tr.t, splabel::EVALS_BATCH, fr.eb);
+    fr.gamma = sp_squeeze<F>(tr.t, splabel::GAMMA, field_id);
+    return LURK_VERIFY_ACCEPTED;
+}
+
+// check 5 of a batch, the statement's side: comm_joint = sum_k gamma^k comm_k over (comm_W_0, comm_E_0, comm_W_1, ...), c = sum_k gamma^k evals_batch[k]
+template <class F>
+static Fe<F> batch_joint(int curve, const lurk_hip_spartan_instance* inst, size_t n, const SpFront<F>& fr, uint64_t* comm_joint) {
+    const std::vector<Fe<F>> pg = powers_of<F>(fr.gamma, 2 * n);
     memcpy(comm_joint, inst[0].comm_w_jacobian96, 96);
-    Fe<F> c = eb[0];
+    Fe<F> c = fr.eb[0];
     for (size_t k = 1; k < 2 * n; k++) {
         point_mul_add<F>(curve, comm_joint, (k & 1) ? inst[k / 2].comm_e_jacobian96 : inst[k / 2].comm_w_jacobian96, pg[k]);
-        c = fe_add<F>(c, fe_mul<F>(pg[k], eb[k]));
+        c = fe_add<F>(c, fe_mul<F>(pg[k], fr.eb[k]));
     }
-    return open_joint<F>(tr, key, curve, field_id, N, comm_joint, c, ck_c_jac96, r_z, pf->ipa_l, pf->ipa_r, pf->ipa_a, s);
+    return c;
+}
+static size_t batch_n(const lurk_hip_spartan_instance* inst, size_t n) {
+    size_t N = 0;
+    for (size_t i = 0; i < n; i++) N = std::max(N, std::max(inst[i].num_cons, inst[i].num_vars));
+    return N;
+}
+
+template <class F>
+static int spartan_verify_batch(int curve, int field_id, const lurk_hip_spartan_instance* inst, size_t n, lurk_hip_msm_ctx* key, const void* ck_c_jac96,
+                                const void* label, size_t label_len, const lurk_hip_spartan_batch_proof* pf, hipStream_t s) {
+    const size_t N = batch_n(inst, n);
+    if (!scalars_reduced<F>(pf->ipa_a, 1)) return LURK_VERIFY_MALFORMED;
+    for (int j = 0; j < sp_log2(N); j++)
+        if (!point_wellformed(curve, (const char*)pf->ipa_l + 96 * j) || !point_wellformed(curve, (const char*)pf->ipa_r + 96 * j)) return LURK_VERIFY_MALFORMED;
+    SpFront<F> fr;
+    const int failed = spartan_verify_batch_front<F>(curve, field_id, inst, n, label, label_len, pf, fr, s);
+    if (failed != LURK_VERIFY_ACCEPTED) return failed;
+    uint64_t comm_joint[12];
+    const Fe<F> c = batch_joint<F>(curve, inst, n, fr, comm_joint);
+    return open_joint<F>(fr.tr, key, curve, field_id, N, comm_joint, c, ck_c_jac96, fr.r_z, pf->ipa_l, pf->ipa_r, pf->ipa_a, s);
+}
+
+// tests/spartan_kzg_ref.py: verify_batched
+static int spartan_kzg_verify_batch(const lurk_hip_spartan_instance* inst, size_t n, const void* label, size_t label_len, const lurk_hip_spartan_kzg_batch_proof* pf,
+                                    void* out_l, void* out_r, hipStream_t s) {
+    using F = Bn254Fr;
+    const int curve = LURK_CURVE_BN254, ell = sp_log2(batch_n(inst, n));
+    if (!kzg_fields_wellformed(ell, pf->kzg_com, pf->kzg_v, pf->kzg_w)) return LURK_VERIFY_MALFORMED;
+    SpFront<F> fr;
+    const int failed = spartan_verify_batch_front<F>(curve, F::ID, inst, n, label, label_len, pf, fr, s);
+    if (failed != LURK_VERIFY_ACCEPTED) return failed;
+    uint64_t comm_joint[12];
+    const Fe<F> y = batch_joint<F>(curve, inst, n, fr, comm_joint);
+    return kzg_open_joint(fr, ell, comm_joint, y, pf->kzg_com, pf->kzg_v, pf->kzg_w, out_l, out_r);
 }
 
 struct KeyInfo {
@@ -702,6 +808,18 @@ static void check_instance_shape(const lurk_hip_r1cs* shape, size_t nc, size_t n
     LURK_REQUIRE(c == nc && v == nv && io == nio, "shape: its (num_cons, num_vars, num_io) differ from the arguments");
     LURK_REQUIRE(f == k.field_id, "the shape is not over the scalar field of the key's curve");
     LURK_REQUIRE(shape->sh.device == k.device, "the shape and the key are resident on different devices");
+}
+
+// the BN254 verifiers take no key: the device is the shape's, the field must be BN254's scalar field
+static void check_kzg_instance_shape(const lurk_hip_r1cs* shape, size_t nc, size_t nv, size_t nio, int device) {
+    LURK_REQUIRE(pow2_at_least_2(nc) && pow2_at_least_2(nv), "num_cons and num_vars must be powers of two >= 2");
+    LURK_REQUIRE(1 + nio <= nv, "the public IO does not fit the second half of z");
+    int f = -1;
+    size_t c = 0, v = 0, io = 0;
+    if (lurk_hip_r1cs_dims(shape, &f, &c, &v, &io) != 0) throw HipFailure{LURK_HIP_ERR_INVALID_ARG, lurk_hip_last_error()};
+    LURK_REQUIRE(c == nc && v == nv && io == nio, "shape: its (num_cons, num_vars, num_io) differ from the arguments");
+    LURK_REQUIRE(f == LURK_FIELD_BN254_FR, "the shape is not over LURK_FIELD_BN254_FR, the scalar field of BN254 G1");
+    LURK_REQUIRE(shape->sh.device == device, "the shapes are resident on different devices");
 }
 
 }  // namespace lurk
@@ -838,6 +956,62 @@ int lurk_hip_spartan_verify_batch_dev(const lurk_hip_spartan_instance* instances
         with_pasta_curve(k.curve, [&](auto, auto SF) {
             failed = spartan_verify_batch<decltype(SF)>(k.curve, k.field_id, instances, n_instances, key, ck_c_jacobian96, label, label_len, proof, (hipStream_t)stream);
         });
+        *accepted = failed == LURK_VERIFY_ACCEPTED;
+        if (failed_check) *failed_check = failed;
+    });
+}
+
+int lurk_hip_spartan_kzg_verify_dev(const lurk_hip_r1cs* shape, size_t num_cons, size_t num_vars, size_t num_io, const void* x32_canonical, const void* u32_canonical,
+                                    const void* comm_w_jacobian96, const void* comm_e_jacobian96, const void* label, size_t label_len,
+                                    const lurk_hip_spartan_kzg_proof* proof, void* out_l_jacobian96, void* out_r_jacobian96, int* accepted, int* failed_check,
+                                    void* stream) {
+    return guarded([&] {
+        LURK_REQUIRE(shape && u32_canonical && comm_w_jacobian96 && comm_e_jacobian96 && proof && out_l_jacobian96 && out_r_jacobian96 && accepted, "null argument");
+        LURK_REQUIRE(num_io == 0 || x32_canonical, "null public IO");
+        LURK_REQUIRE(label || label_len == 0, "null label");
+        *accepted = 0;
+        if (failed_check) *failed_check = LURK_VERIFY_MALFORMED;
+        memset(out_l_jacobian96, 0, 96);
+        memset(out_r_jacobian96, 0, 96);
+        LURK_REQUIRE((num_cons > num_vars ? num_cons : num_vars) != 1, "N = max(num_cons, num_vars) = 1: the HyperKZG opening needs N >= 2");
+        check_kzg_instance_shape(shape, num_cons, num_vars, num_io, shape->sh.device);
+        LURK_REQUIRE(proof->polys_outer && proof->claims_outer && proof->eval_e && proof->polys_inner && proof->eval_w && proof->polys_batch && proof->evals_batch &&
+                         proof->kzg_v && proof->kzg_w && (proof->kzg_com || (num_cons == 2 && num_vars == 2)),
+                     "null proof buffer");
+        DeviceGuard dg(shape->sh.device);
+        const int failed = spartan_kzg_verify(shape, num_cons, num_vars, num_io, x32_canonical, u32_canonical, comm_w_jacobian96, comm_e_jacobian96, label, label_len, proof,
+                                              out_l_jacobian96, out_r_jacobian96, (hipStream_t)stream);
+        *accepted = failed == LURK_VERIFY_ACCEPTED;
+        if (failed_check) *failed_check = failed;
+    });
+}
+
+int lurk_hip_spartan_kzg_verify_batch_dev(const lurk_hip_spartan_instance* instances, size_t n_instances, const void* label, size_t label_len,
+                                          const lurk_hip_spartan_kzg_batch_proof* proof, void* out_l_jacobian96, void* out_r_jacobian96, int* accepted,
+                                          int* failed_check, void* stream) {
+    return guarded([&] {
+        LURK_REQUIRE(instances && n_instances >= 1 && n_instances <= 64 && proof && out_l_jacobian96 && out_r_jacobian96 && accepted,
+                     "null argument, or not 1..64 instances");
+        LURK_REQUIRE(label || label_len == 0, "null label");
+        *accepted = 0;
+        if (failed_check) *failed_check = LURK_VERIFY_MALFORMED;
+        memset(out_l_jacobian96, 0, 96);
+        memset(out_r_jacobian96, 0, 96);
+        for (size_t i = 0; i < n_instances; i++) {
+            const lurk_hip_spartan_instance& it = instances[i];
+            LURK_REQUIRE(it.shape && it.u32_canonical && it.comm_w_jacobian96 && it.comm_e_jacobian96, "null instance field");
+            LURK_REQUIRE(it.num_io == 0 || it.x32_canonical, "null public IO");
+        }
+        const size_t N = batch_n(instances, n_instances);
+        LURK_REQUIRE(N != 1, "N = max(num_cons, num_vars) = 1: the HyperKZG opening needs N >= 2");
+        const int device = instances[0].shape->sh.device;
+        for (size_t i = 0; i < n_instances; i++)
+            check_kzg_instance_shape(instances[i].shape, instances[i].num_cons, instances[i].num_vars, instances[i].num_io, device);
+        LURK_REQUIRE(proof->polys_outer && proof->claims_outer && proof->evals_e && proof->polys_inner && proof->evals_w && proof->polys_batch && proof->evals_batch &&
+                         proof->kzg_v && proof->kzg_w && (proof->kzg_com || N == 2),
+                     "null proof buffer");
+        DeviceGuard dg(device);
+        const int failed = spartan_kzg_verify_batch(instances, n_instances, label, label_len, proof, out_l_jacobian96, out_r_jacobian96, (hipStream_t)stream);
         *accepted = failed == LURK_VERIFY_ACCEPTED;
         if (failed_check) *failed_check = failed;
     });

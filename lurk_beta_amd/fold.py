@@ -180,3 +180,22 @@ def fold_vecs(field_id: int, pairs, r_mont: np.ndarray, outs=None, stream=None):
     ns = (ctypes.c_size_t * max(n, 1))(*[a.shape[0] for a, _ in pairs])
     _lib.check(_lib.load().lurk_hip_fold_vecs_dev(field_id, n, pa, pb, ns, po, _lib.ptr(r), _lib.ptr(s)))
     return outs
+
+
+def fold_padded(field_id: int, vecs, coeffs_mont: np.ndarray, n_out: int, out=None, lens=None, stream=None):
+    """out[j] = sum_k c_k (j < len_k ? vecs[k][j] : 0) for j < n_out in ONE launch (``lurk_hip_fold_padded_dev``): vectors of different
+    lengths read as if zero-padded to n_out.  vecs: (len_k, 4) device tensors, or None for a zero-length vector; coeffs: (count, 4)
+    Montgomery.  ``lens`` overrides the tensors' lengths; ``out`` an (n_out, 4) device tensor to write.  Returns the output."""
+    import torch
+
+    n = len(vecs)
+    if lens is None:
+        lens = [0 if v is None else v.shape[0] for v in vecs]
+    if out is None:
+        out = torch.empty((n_out, 4), dtype=torch.int64, device="cuda")
+    c = np.ascontiguousarray(coeffs_mont, dtype=np.uint64).reshape(-1, 4)
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    pv = (ctypes.c_void_p * max(n, 1))(*[_lib.ptr(v) for v in vecs])
+    ln = (ctypes.c_size_t * max(n, 1))(*lens)
+    _lib.check(_lib.load().lurk_hip_fold_padded_dev(field_id, n, pv, ln, _lib.ptr(c), n_out, _lib.ptr(out), _lib.ptr(s)))
+    return out

@@ -23,6 +23,7 @@ pub mod dump;
 pub mod ffi;
 pub mod hyperkzg;
 pub mod params;
+pub mod spartan_kzg;
 pub mod store;
 pub use ffi::*;
 
