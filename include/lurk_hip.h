@@ -342,6 +342,57 @@ int lurk_hip_poseidon_constants(int field_id, int arity, int* rf, int* rp, void*
  * for DAG levels too narrow to be worth a kernel's dependency chain. */
 int lurk_hip_poseidon_hash_host(int field_id, int arity, const void* preimages, size_t n, void* digests);
 
+/* ---- the sparse Poseidon trie, resident on the device --------------------------------------------------------------------
+ * Replaces coprocessor::trie::Trie<F, 8, HEIGHT> (/root/reference/src/coprocessor/trie/mod.rs) for bulk work: building the trie of n
+ * (key, value) pairs, prove_lookup (:718-743) and prove_insert / modify_value_at_path (:751-800) for batches of keys, and
+ * LookupProof::verify (:349-362) / InsertProof::verify (:383-424) for batches of proofs.  Arity 8; height H = 1 .. 85 (85 is the
+ * StandardTrie, :43); fields LURK_FIELD_PALLAS_FP, _PALLAS_FQ and _BN254_FR.  Elements are canonical 32 B.
+ *   path       the low 3 H bits of the key's canonical value (its PATH VALUE) read as H 3-bit digits, top digit first (:589-608);
+ *              path order = numeric order of path values; two keys with one path value occupy one leaf
+ *   empty      the empty element is 0; empty_roots[0] = hash8([0; 8]), empty_roots[i] = hash8([empty_roots[i-1]; 8]) (:464-481)
+ *   node       hash8(children): the digests of lurk_hip_poseidon_batch, bit for bit
+ *   proof      H preimages of 8 elements, root level first, the last one holding the payloads: H * 256 B per proof.  An absent subtree
+ *              contributes [empty root below; 8] ([0; 8] at the leaf level), as the reference's init_empty registers them, so a lookup
+ *              proof exists for an absent key (value 0).
+ * Only lurk_hip_trie_path_digits runs without a device. */
+typedef struct lurk_hip_trie lurk_hip_trie;
+/* host only: the n * H path digits of n keys (key-major).  Bits at and above the field's NUM_BITS are ignored (no reduced key has them). */
+int lurk_hip_trie_path_digits(int field_id, int height, const void* keys32, size_t n, uint8_t* digits);
+/* The trie that holds exactly these n pairs.  Keys must be reduced and strictly increasing in path order: one device pass checks it, and
+ * a violation is refused with LURK_HIP_ERR_INVALID_ARG, the message naming the first offending index and whether that key is "not
+ * reduced", "out of order" or has a "duplicate path"; a refused call leaves nothing allocated.  n = 0 gives the empty trie; a value of 0
+ * is legal (the empty element: that leaf hashes as if absent).  The caller's buffers are copied; the call synchronises `stream`.
+ * The handle keeps on the device: the keys and the values (n * 32 B each), the hash of every non-empty node at every level (H arrays of
+ * n elements: H * n * 32 B), one byte per key and the H + 1 empty roots - 178 MB of node hashes at H = 85, n = 2^16 (182 MB in all).
+ * Built in at most H + 2 launches: the check, one launch in which every key hashes the part of its path it does not share with another
+ * key, and one launch per depth at which two keys still share a node (about log8(n) + 1 for random keys).  An allocation failure comes
+ * back as LURK_HIP_ERR_OOM with everything freed.  A built trie is not modified afterwards: rebuild to change it. */
+int lurk_hip_trie_build_dev(lurk_hip_trie** t, int field_id, int height, const void* d_keys32, const void* d_values32, size_t n, void* stream);
+int lurk_hip_trie_root(const lurk_hip_trie* t, void* root32);
+/* any output may be NULL */
+int lurk_hip_trie_info(const lurk_hip_trie* t, int* field_id, int* height, size_t* n, int* device);
+int lurk_hip_trie_destroy(lurk_hip_trie* t);
+/* prove_lookup for m keys, present or absent, in any order: d_paths receives m * H * 8 elements, d_values32 the m values (0 = absent).
+ * Only the low 3 H bits of a key are read.  Reads the handle only: calls on several streams may run side by side.  Does not synchronise. */
+int lurk_hip_trie_prove_lookup_dev(const lurk_hip_trie* t, const void* d_keys32, size_t m, void* d_paths, void* d_values32, void* stream);
+/* m independent prove_inserts, each against the trie as built (the handle is not modified): the old path and value as above, the new path
+ * = modify_value_at_path (the entry replaced bottom-up, H hashes), and the root after that one insertion.  d_old_paths and d_new_paths
+ * (m * H * 8 elements each) may not overlap.  Does not synchronise. */
+int lurk_hip_trie_prove_insert_dev(const lurk_hip_trie* t, const void* d_keys32, const void* d_new_values32, size_t m, void* d_old_paths, void* d_new_paths,
+                                   void* d_old_values32, void* d_new_roots32, void* stream);
+/* LookupProof::verify per proof.  root_stride: 0 = d_roots32 is one root for every proof, 1 = one root per proof.  d_codes[i]: 0 =
+ * accepted; k + 1 = the hash of preimage k is not the expected node (level 0 is checked against the root) or preimage k holds an element
+ * that is not reduced; H + 1 = the selected leaf entry is not the value.  *n_failed (host) = the number of non-zero codes; the call
+ * synchronises `stream`.  Keys and values that are not reduced are refused before anything is launched. */
+int lurk_hip_trie_verify_lookup_dev(int field_id, int height, const void* d_roots32, size_t root_stride, const void* d_keys32, const void* d_values32,
+                                    const void* d_paths, size_t m, uint32_t* d_codes, uint64_t* n_failed, void* stream);
+/* InsertProof::verify per proof, in the reference's order, the first failing check giving the code: the old proof (1 .. H + 1 as above; an
+ * absent old value is passed as 0), then at every level the two preimages equal or different in at most one position (0x100 + level + 1),
+ * then the new proof (0x200 + 1 .. H + 1). */
+int lurk_hip_trie_verify_insert_dev(int field_id, int height, const void* d_old_roots32, const void* d_new_roots32, size_t root_stride, const void* d_keys32,
+                                    const void* d_old_values32, const void* d_new_values32, const void* d_old_paths, const void* d_new_paths, size_t m,
+                                    uint32_t* d_codes, uint64_t* n_failed, void* stream);
+
 /* ---- store hydration -----------------------------------------------------------------------
  * Replaces the recursive, node-by-node hashing of StoreCore::hydrate_z_cache / hash_ptr
  * (/root/reference/src/lem/store_core.rs:256-269) with the StoreHasher preimage layouts

@@ -109,6 +109,16 @@ SIGNATURES = {
     "lurk_hip_poseidon_tree8_dev": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "lurk_hip_poseidon_constants": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p, c_void_p]),
     "lurk_hip_poseidon_hash_host": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "lurk_hip_trie_path_digits": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "lurk_hip_trie_build_dev": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lurk_hip_trie_root": (c_int, [c_void_p, c_void_p]),
+    "lurk_hip_trie_info": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_size_t), ctypes.POINTER(c_int)]),
+    "lurk_hip_trie_destroy": (c_int, [c_void_p]),
+    "lurk_hip_trie_prove_lookup_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "lurk_hip_trie_prove_insert_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lurk_hip_trie_verify_lookup_dev": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_u64), c_void_p]),
+    "lurk_hip_trie_verify_insert_dev": (c_int, [c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                                ctypes.POINTER(c_u64), c_void_p]),
     "lurk_hip_store_hydrate": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_size_t)]),
     "lurk_hip_slot_witness_size": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "lurk_hip_slot_witness_dev": (c_int, [c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),

@@ -263,6 +263,14 @@ struct ArenaBuf {
     ArenaBuf& operator=(const ArenaBuf&) = delete;
 };
 
+// The Poseidon constant image of (field, arity) on the current device (poseidon.hip; layout: poseidon29.cuh), for kernels outside
+// poseidon.hip that run the same permutation (trie.hip).  vec4: its length in 16-byte words, the slot-witness post keys included.
+struct PoseidonImageView {
+    const void* img = nullptr;
+    int vec4 = 0, rf = 0, rp = 0;
+};
+PoseidonImageView poseidon_image_view(int field_id, int arity, hipStream_t s);
+
 // curve ids by name, for messages; entry points that exist for the Pasta cycle only refuse the BN254 cycle (and anything else) with it
 inline const char* curve_name(int curve) {
     switch (curve) {

@@ -443,6 +443,12 @@ static const uint4* device_image(PoseidonConsts& pc, hipStream_t s) {
     return it->second.as<uint4>();
 }
 
+// the constants of (field, arity) as the kernels of another translation unit stage them (trie.hip): the same image, on the current device
+PoseidonImageView poseidon_image_view(int field_id, int arity, hipStream_t s) {
+    PoseidonConsts& pc = get_consts(field_id, arity);
+    return PoseidonImageView{device_image(pc, s), (int)(pc.image.size() / 4), pc.rf, pc.rp};
+}
+
 template <class P, int T>
 static void launch_batch(const void* d_pre, void* d_out, size_t n, PoseidonConsts& pc, int flags, hipStream_t s) {
     if (n == 0) return;

@@ -25,6 +25,7 @@ pub mod hyperkzg;
 pub mod params;
 pub mod spartan_kzg;
 pub mod store;
+pub mod trie;
 pub use ffi::*;
 
 use core::ffi::{c_int, c_void};
