@@ -366,7 +366,8 @@ int lurk_hip_trie_path_digits(int field_id, int height, const void* keys32, size
  * n elements: H * n * 32 B), one byte per key and the H + 1 empty roots - 178 MB of node hashes at H = 85, n = 2^16 (182 MB in all).
  * Built in at most H + 2 launches: the check, one launch in which every key hashes the part of its path it does not share with another
  * key, and one launch per depth at which two keys still share a node (about log8(n) + 1 for random keys).  An allocation failure comes
- * back as LURK_HIP_ERR_OOM with everything freed.  A built trie is not modified afterwards: rebuild to change it. */
+ * back as LURK_HIP_ERR_OOM with everything freed.  A built trie is not modified afterwards: lurk_hip_trie_insert_chain_dev gives a NEW
+ * handle for the trie after a sequence of updates. */
 int lurk_hip_trie_build_dev(lurk_hip_trie** t, int field_id, int height, const void* d_keys32, const void* d_values32, size_t n, void* stream);
 int lurk_hip_trie_root(const lurk_hip_trie* t, void* root32);
 /* any output may be NULL */
@@ -380,6 +381,31 @@ int lurk_hip_trie_prove_lookup_dev(const lurk_hip_trie* t, const void* d_keys32,
  * (m * H * 8 elements each) may not overlap.  Does not synchronise. */
 int lurk_hip_trie_prove_insert_dev(const lurk_hip_trie* t, const void* d_keys32, const void* d_new_values32, size_t m, void* d_old_paths, void* d_new_paths,
                                    void* d_old_values32, void* d_new_roots32, void* stream);
+/* A CHAIN of m dependent inserts, as a host that calls Trie::insert / Trie::prove_insert (:745-776) step after step produces them: T_0 = t,
+ * update i = (key_i, value_i) is applied to T_i and leaves T_{i+1}.  Per update: the old path (prove_lookup of key_i in T_i, laid out as
+ * above) and the old value (0 = absent), the new path (modify_value_at_path) and d_roots32[i] = the root of T_{i+1}.  Keys may repeat, be
+ * present in t or not, and share any number of leading digits; two keys with one path value are one leaf; a value of 0 is legal (that
+ * leaf then hashes as if absent); an update that changes nothing repeats the previous root.
+ *   outputs    each of d_old_paths, d_new_paths, d_old_values32, d_roots32 and out_trie may be NULL when it is not wanted; all five NULL is
+ *              refused.  d_old_paths and d_new_paths (m * H * 8 elements each) may not overlap.
+ *   out_trie   when non-NULL receives a NEW handle that holds T_m: the pairs of t merged on the device with the last update of every path
+ *              value (a value of 0 stays a pair), sorted by path value and built by lurk_hip_trie_build_dev, from which it cannot be told
+ *              apart; its root is d_roots32[m - 1].  The caller destroys it.  t itself is read only: chains on several streams may share
+ *              it.  With m = 0, out_trie holds a copy of t's pairs and nothing else is written.  Not written when the call fails.
+ *   refusals   keys and values must be reduced: both are read back and checked on the host first, a violation is LURK_HIP_ERR_INVALID_ARG
+ *              with the first offending index in the message, and nothing has been launched or allocated by then.  m <= 2^28.
+ *   work       the m * H hashes of the sequential loop at a dependency depth of H: one hashing launch per depth, bottom-up, one update
+ *              per lane.  What an update finds in a node is the node's preimage in T_0 with every child replaced by the new hash of the
+ *              latest earlier update through that child; that update is found by binary search in the updates ordered by (prefix,
+ *              sequence index), one stable sort (rocprim) and one 4-byte read-back per depth at which two different keys still share a
+ *              node - about 2 log8(m) depths for random keys, H at the most.  The number of launches does not depend on m.
+ *   scratch    freed before the call returns: 8 B per update and depth for the orders (680 B per update at H = 85), 80 B per update of
+ *              work space and hashes, the sort's temporary storage, and - ONLY when d_old_paths is NULL - the m * H * 256 B of old paths,
+ *              which the call then keeps to itself (the preimages of T_0 are written where the old paths go and patched in place; they
+ *              are not recomputed per level).  An allocation failure is LURK_HIP_ERR_OOM with everything freed and no handle written.
+ * The call synchronises `stream`. */
+int lurk_hip_trie_insert_chain_dev(const lurk_hip_trie* t, const void* d_keys32, const void* d_values32, size_t m, void* d_old_paths, void* d_new_paths,
+                                   void* d_old_values32, void* d_roots32, lurk_hip_trie** out_trie, void* stream);
 /* LookupProof::verify per proof.  root_stride: 0 = d_roots32 is one root for every proof, 1 = one root per proof.  d_codes[i]: 0 =
  * accepted; k + 1 = the hash of preimage k is not the expected node (level 0 is checked against the root) or preimage k holds an element
  * that is not reduced; H + 1 = the selected leaf entry is not the value.  *n_failed (host) = the number of non-zero codes; the call

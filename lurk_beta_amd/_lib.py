@@ -116,6 +116,7 @@ SIGNATURES = {
     "lurk_hip_trie_destroy": (c_int, [c_void_p]),
     "lurk_hip_trie_prove_lookup_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "lurk_hip_trie_prove_insert_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lurk_hip_trie_insert_chain_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p]),
     "lurk_hip_trie_verify_lookup_dev": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_u64), c_void_p]),
     "lurk_hip_trie_verify_insert_dev": (c_int, [c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
                                                 ctypes.POINTER(c_u64), c_void_p]),

@@ -18,7 +18,12 @@
 //   trie_prove_insert_kernel  the same walk, then modify_value_at_path (:778-800): H dependent hashes bottom-up in the same lane
 //   trie_verify_lookup_kernel / trie_verify_insert_kernel   LookupProof::verify (:349-362) / InsertProof::verify (:383-424), one lane
 //                             per proof, the first failing check latched and the chain run to its end
+//   trie_chain_*_kernel       a chain of m DEPENDENT inserts in O(H) launches (see "the chain" below): the updates ordered per depth by
+//                             (prefix, sequence index), then one hashing launch per depth, bottom-up, one update per lane
 #include <memory>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include "common.hpp"
 #include "dispatch.hpp"
@@ -412,6 +417,190 @@ __global__ __launch_bounds__(TRIE_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2
     trie_count_failures(code != 0, n_failed);
 }
 
+// ---- the chain: m dependent inserts, level-synchronously -------------------------------------------------------------------------------
+// Update i = (key_i, value_i) is applied to T_i and leaves T_{i+1} (insert_at_path, :760-776).  At the node that update i passes at depth d
+// the preimage it FINDS is the node's preimage in T_0 with every child entry c replaced by the new hash, one level down, of the latest
+// EARLIER update that went through child c; the preimage it LEAVES has its own child's new hash put in as well, and its new hash at depth d
+// is the hash of that.  So depth d needs depth d + 1 only: H hashing launches for m * H hashes, whatever m is.
+//
+// "The latest earlier update through child c" is three binary searches.  ord[e] (e = 1 .. D) holds the updates sorted by (top-e-digit
+// prefix, sequence index): a stable sort of ord[e - 1] by skey = 8 * label + digit e - 1, where label[q] is the position at which the
+// depth e - 1 node of entry q starts in ord[e - 1].  Along ord[e] the sorted skey[e] is non-decreasing and the updates through child c of
+// the node that starts at `node` are the run skey == 8 * node + c, in sequence order.  The splitting stops at the first depth D at which
+// every node holds updates of ONE path value: below it the order no longer changes and only an update's own child has an earlier setter,
+// its predecessor in the run.  (Random keys: D ~ 2 log8(m).  Two keys that share 84 digits: D = 84.)
+constexpr size_t TRIE_CHAIN_MAX = (size_t)1 << 28;  // 8 * label + digit is a 32-bit sort key
+
+// do the keys a and b (memory) have one path value?  a < b in path order?
+__device__ __forceinline__ int trie_path_cmp(const uint32_t* a, const uint32_t* b, int height) {
+    const uint4 alo = reinterpret_cast<const uint4*>(a)[0], ahi = reinterpret_cast<const uint4*>(a)[1];
+    const uint4 blo = reinterpret_cast<const uint4*>(b)[0], bhi = reinterpret_cast<const uint4*>(b)[1];
+    const uint32_t aw[8] = {alo.x, alo.y, alo.z, alo.w, ahi.x, ahi.y, ahi.z, ahi.w}, bw[8] = {blo.x, blo.y, blo.z, blo.w, bhi.x, bhi.y, bhi.z, bhi.w};
+    int r = 0;
+#pragma unroll
+    for (int w = 7; w >= 0; w--) {
+        const uint32_t m = trie_low_mask(w, 3 * height), x = aw[w] & m, y = bw[w] & m;
+        if (r == 0 && x != y) r = x < y ? -1 : 1;
+    }
+    return r;
+}
+
+__device__ __forceinline__ size_t trie_u32_lower_bound(const uint32_t* a, size_t lo, size_t hi, uint32_t v) {
+    while (lo < hi) {
+        const size_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the sort key of entry q of the order at depth d (ord == nullptr: the identity, every label 0), the entry itself as the sort's value, and
+// *mixed = 1 if a node of depth d holds two path values (then depth d has to be split)
+__global__ __launch_bounds__(TRIE_BLOCK) void trie_chain_key_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ ord,
+                                                                    const uint32_t* __restrict__ label, size_t m, int height, int d, uint32_t* __restrict__ skey,
+                                                                    uint32_t* __restrict__ entry, uint32_t* mixed) {
+    const size_t q = (size_t)blockIdx.x * TRIE_BLOCK + threadIdx.x;
+    if (q >= m) return;
+    const uint32_t u = ord ? ord[q] : (uint32_t)q, lab = ord ? label[q] : 0u;
+    skey[q] = lab * 8u + (uint32_t)trie_key_digit(keys + (size_t)u * 8, height, d);
+    entry[q] = u;
+    if (q > 0 && (ord ? label[q - 1] : 0u) == lab) {
+        const uint32_t v = ord ? ord[q - 1] : (uint32_t)(q - 1);
+        if (trie_path_cmp(keys + (size_t)u * 8, keys + (size_t)v * 8, height) != 0) *mixed = 1u;
+    }
+}
+
+// label[q] = where the run of skey[q] starts: the node of entry q at the next depth
+__global__ __launch_bounds__(TRIE_BLOCK) void trie_chain_label_kernel(const uint32_t* __restrict__ skey, size_t m, uint32_t* __restrict__ label) {
+    const size_t q = (size_t)blockIdx.x * TRIE_BLOCK + threadIdx.x;
+    if (q < m) label[q] = (uint32_t)trie_u32_lower_bound(skey, 0, q, skey[q]);
+}
+
+struct TrieChainLevel {
+    const uint32_t* keys;   // m x 8 words
+    const uint32_t* ord;    // the order at depth min(d + 1, D); nullptr = the identity (D = 0)
+    const uint32_t* skey;   // the sorted keys of ord when d + 1 <= D, else nullptr: then label
+    const uint32_t* label;  // where the run (one path value) of entry q starts
+    const uint4* below;     // m x 32 B by update: the new hashes of depth d + 1 (at d = H - 1: the new values)
+    uint4* here;            // m x 32 B by update: the new hashes of depth d (at d = 0: the roots)
+    uint4* old_paths;       // m x H x 8 elements: the preimages of T_0 on entry, patched in place when store_old
+    uint4* new_paths;       // or nullptr
+    uint4* old_values;      // or nullptr; written at d = H - 1
+    size_t m;
+    int height, d, store_old;
+};
+
+// One update per lane, in the order of the depth below, so that the updates of one node are neighbours.  Nothing but the update's index
+// is carried across the permutation.
+template <class P>
+__global__ __launch_bounds__(TRIE_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void trie_chain_level_kernel(TrieChainLevel a, const uint4* __restrict__ img,
+                                                                                                               int img_vec4, int rf, int rp) {
+    extern __shared__ uint4 lds[];
+    trie_stage_image(lds, img, img_vec4);
+    const TrieHasher<P> h(lds, rf, rp);
+    const size_t q = (size_t)blockIdx.x * TRIE_BLOCK + threadIdx.x;
+    if (q >= a.m) return;  // no barrier follows
+    const size_t i = a.ord ? a.ord[q] : q;
+    const int own = trie_key_digit(a.keys + i * 8, a.height, a.d);
+    uint4* oldp = a.old_paths + (i * (size_t)a.height + (size_t)a.d) * 16;
+    uint4* newp = a.new_paths ? a.new_paths + (i * (size_t)a.height + (size_t)a.d) * 16 : nullptr;
+    const size_t node = a.skey ? (size_t)(a.skey[q] >> 3) : (size_t)a.label[q];
+    F29<P> s[TRIE_T];
+    s[0] = h.tag();
+    size_t b = node;  // the run of child 0 starts where the node does
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        size_t setter = a.m;  // none
+        if (a.skey) {
+            const size_t nb = trie_u32_lower_bound(a.skey, b, a.m, (uint32_t)(node * 8 + c + 1));
+            if (c == own) {
+                if (q > b) setter = a.ord[q - 1];
+            } else if (nb > b) {
+                const size_t r = trie_u32_lower_bound(a.ord, b, nb, (uint32_t)i);  // the run is in sequence order
+                if (r > b) setter = a.ord[r - 1];
+            }
+            b = nb;
+        } else if (c == own && q > node) {
+            setter = a.ord ? a.ord[q - 1] : q - 1;
+        }
+        Fe<P> x;
+        if (setter < a.m) {
+            x = ld_fe<P>(a.below + 2 * setter);
+            if (a.store_old) st_fe<P>(oldp + 2 * c, x);
+        } else {
+            x = ld_fe<P>(oldp + 2 * c);
+        }
+        if (c == own) {
+            if (a.old_values && a.d == a.height - 1) st_fe<P>(a.old_values + 2 * i, x);
+            x = ld_fe<P>(a.below + 2 * i);
+        }
+        if (newp) st_fe<P>(newp + 2 * c, x);
+        s[c + 1] = h.in(x);
+    }
+    st_fe<P>(a.here + 2 * i, h.run(s));
+}
+
+// out_trie: the pairs of T_m.  last[q] = 1 where entry q of the final order is the last update of its path value; upd[] = those entries,
+// compacted (they are in path order); every one of them looks itself up among the trie's keys, every key of the trie among them.
+__global__ __launch_bounds__(TRIE_BLOCK) void trie_chain_last_kernel(const uint32_t* __restrict__ label, size_t m, uint32_t* __restrict__ last) {
+    const size_t q = (size_t)blockIdx.x * TRIE_BLOCK + threadIdx.x;
+    if (q < m) last[q] = (q + 1 == m || (label && label[q + 1] != label[q])) ? 1u : 0u;
+}
+__global__ __launch_bounds__(TRIE_BLOCK) void trie_chain_compact_kernel(const uint32_t* __restrict__ ord, const uint32_t* __restrict__ last,
+                                                                        const uint32_t* __restrict__ last_incl, size_t m, uint32_t* __restrict__ upd) {
+    const size_t q = (size_t)blockIdx.x * TRIE_BLOCK + threadIdx.x;
+    if (q < m && last[q]) upd[last_incl[q] - 1] = ord ? ord[q] : (uint32_t)q;
+}
+// for update entry r: below[r] = the trie's keys with a smaller path value, present[r] = 1 if the trie holds its path value
+__global__ __launch_bounds__(TRIE_BLOCK) void trie_chain_locate_kernel(const uint32_t* __restrict__ tkeys, size_t n, const uint32_t* __restrict__ ukeys,
+                                                                       const uint32_t* __restrict__ upd, size_t nu, int height, uint32_t* __restrict__ below,
+                                                                       uint32_t* __restrict__ present) {
+    const size_t r = (size_t)blockIdx.x * TRIE_BLOCK + threadIdx.x;
+    if (r >= nu) return;
+    const uint32_t* key = ukeys + (size_t)upd[r] * 8;
+    size_t lo = 0, hi = n;
+    while (lo < hi) {
+        const size_t mid = lo + ((hi - lo) >> 1);
+        if (trie_path_cmp(tkeys + mid * 8, key, height) < 0) lo = mid + 1;
+        else hi = mid;
+    }
+    below[r] = (uint32_t)lo;
+    present[r] = lo < n && trie_path_cmp(tkeys + lo * 8, key, height) == 0 ? 1u : 0u;
+}
+// lanes 0 .. n - 1: the trie's pairs that no update replaces; lanes n .. n + nu - 1: the last update of every path value
+__global__ __launch_bounds__(TRIE_BLOCK) void trie_chain_merge_kernel(const uint32_t* __restrict__ tkeys, const uint4* __restrict__ tvalues, size_t n,
+                                                                      const uint32_t* __restrict__ ukeys, const uint4* __restrict__ uvalues,
+                                                                      const uint32_t* __restrict__ upd, size_t nu, const uint32_t* __restrict__ below,
+                                                                      const uint32_t* __restrict__ present, const uint32_t* __restrict__ present_incl, int height,
+                                                                      uint4* __restrict__ out_keys, uint4* __restrict__ out_values) {
+    const size_t g = (size_t)blockIdx.x * TRIE_BLOCK + threadIdx.x;
+    if (g >= n + nu) return;
+    const uint4 *k, *v;
+    size_t pos;
+    if (g < n) {
+        const uint32_t* key = tkeys + g * 8;
+        size_t lo = 0, hi = nu;  // the update entries with a smaller path value
+        while (lo < hi) {
+            const size_t mid = lo + ((hi - lo) >> 1);
+            if (trie_path_cmp(ukeys + (size_t)upd[mid] * 8, key, height) < 0) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < nu && trie_path_cmp(ukeys + (size_t)upd[lo] * 8, key, height) == 0) return;  // replaced
+        pos = g + lo - (lo ? present_incl[lo - 1] : 0u);
+        k = reinterpret_cast<const uint4*>(key);
+        v = tvalues + 2 * g;
+    } else {
+        const size_t r = g - n;
+        pos = r + below[r] - (present_incl[r] - present[r]);
+        k = reinterpret_cast<const uint4*>(ukeys + (size_t)upd[r] * 8);
+        v = uvalues + 2 * (size_t)upd[r];
+    }
+    out_keys[2 * pos] = k[0];
+    out_keys[2 * pos + 1] = k[1];
+    out_values[2 * pos] = v[0];
+    out_values[2 * pos + 1] = v[1];
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 static void require_trie_field(int field_id) {
     with_field(field_id, [](auto) {});  // "unknown field id"
@@ -712,6 +901,143 @@ int lurk_hip_trie_verify_insert_dev(int field_id, int height, const void* d_old_
             LURK_HIP_CHECK(hipMemcpyAsync(n_failed, count.p, 8, hipMemcpyDeviceToHost, s));
             LURK_HIP_CHECK(hipStreamSynchronize(s));
         });
+    });
+}
+
+int lurk_hip_trie_insert_chain_dev(const lurk_hip_trie* t, const void* d_keys32, const void* d_values32, size_t m, void* d_old_paths, void* d_new_paths,
+                                   void* d_old_values32, void* d_roots32, lurk_hip_trie** out_trie, void* stream) {
+    return guarded([&] {
+        require_trie_here(t);
+        LURK_REQUIRE(d_old_paths || d_new_paths || d_old_values32 || d_roots32 || out_trie, "no output asked for: every output pointer is null");
+        LURK_REQUIRE(m <= TRIE_CHAIN_MAX, "a chain holds at most 2^28 updates");
+        hipStream_t s = (hipStream_t)stream;
+        const int H = t->height;
+        lurk_hip_trie* grown = nullptr;
+        if (m == 0) {
+            if (out_trie) {
+                nested_ok(lurk_hip_trie_build_dev(&grown, t->field_id, H, t->n ? t->keys.p : nullptr, t->n ? t->values.p : nullptr, t->n, stream));
+                *out_trie = grown;
+            }
+            return;
+        }
+        LURK_REQUIRE(d_keys32 && d_values32, "null buffer");
+        const size_t path_bytes = m * (size_t)H * 256;
+        if (d_old_paths && d_new_paths) {
+            const char *a = (const char*)d_old_paths, *b = (const char*)d_new_paths;
+            LURK_REQUIRE(a + path_bytes <= b || b + path_bytes <= a, "d_old_paths and d_new_paths overlap");
+        }
+        with_field(t->field_id, [&](auto F) {
+            using P = decltype(F);
+            {
+                std::vector<uint32_t> host;  // nothing is launched or allocated on the device before both have passed
+                require_reduced_dev<P>(d_keys32, m, "key", host, s);
+                require_reduced_dev<P>(d_values32, m, "value", host, s);
+            }
+            const uint32_t* keys = (const uint32_t*)d_keys32;
+            const unsigned grid = div_up(m, TRIE_BLOCK);
+            // scratch: the orders (2 x 4 B per update and depth that is split, H at the most), two rows of new hashes, the sort's storage, and the
+            // preimages of T_0 when the caller does not take the old paths
+            DevBuf orders(2 * (size_t)H * m * 4), work(4 * m * 4), hashes(2 * m * 32), flag(4), old_scratch, value_scratch;
+            uint32_t *skey_in = work.as<uint32_t>(), *entry_in = skey_in + m, *label = skey_in + 2 * m, *aux = skey_in + 3 * m;
+            auto ord_at = [&](int e) { return orders.as<uint32_t>() + (size_t)(2 * (e - 1)) * m; };       // e = 1 .. D
+            auto skey_at = [&](int e) { return orders.as<uint32_t>() + (size_t)(2 * (e - 1) + 1) * m; };
+            unsigned end_bit = 4;
+            while (end_bit < 32 && ((size_t)1 << end_bit) < 8 * m) end_bit++;
+            size_t sort_bytes = 0, scan_bytes = 0;
+            LURK_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, skey_in, skey_in, entry_in, entry_in, (unsigned)m, 0, end_bit, s));
+            LURK_HIP_CHECK(rocprim::inclusive_scan(nullptr, scan_bytes, aux, aux, m, rocprim::plus<uint32_t>(), s));
+            DevBuf temp(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
+            if (!d_old_paths) old_scratch.alloc(path_bytes);
+            if (!d_old_values32) value_scratch.alloc(m * 32);
+            uint4* oldp = d_old_paths ? (uint4*)d_old_paths : old_scratch.as<uint4>();
+            LURK_HIP_CHECK(hipMemsetAsync(label, 0, m * 4, s));
+
+            // the orders, top-down: split depth d while one of its nodes holds two path values
+            int D = 0;
+            {
+                ProfScope ps("trie_chain_order", s);
+                for (; D < H; D++) {
+                    LURK_HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
+                    hipLaunchKernelGGL(trie_chain_key_kernel, dim3(grid), dim3(TRIE_BLOCK), 0, s, keys, D ? ord_at(D) : (const uint32_t*)nullptr, label, m, H, D, skey_in,
+                                       entry_in, flag.as<uint32_t>());
+                    LURK_HIP_CHECK(hipGetLastError());
+                    uint32_t mixed = 0;
+                    LURK_HIP_CHECK(hipMemcpyAsync(&mixed, flag.p, 4, hipMemcpyDeviceToHost, s));
+                    LURK_HIP_CHECK(hipStreamSynchronize(s));
+                    if (!mixed) break;
+                    size_t bytes = temp.bytes;
+                    LURK_HIP_CHECK(rocprim::radix_sort_pairs(temp.p, bytes, skey_in, skey_at(D + 1), entry_in, ord_at(D + 1), (unsigned)m, 0, end_bit, s));
+                    hipLaunchKernelGGL(trie_chain_label_kernel, dim3(grid), dim3(TRIE_BLOCK), 0, s, skey_at(D + 1), m, label);
+                    LURK_HIP_CHECK(hipGetLastError());
+                }
+            }
+            // the preimages of T_0 along every update's path (and, for now, the values of T_0)
+            const TrieView v = t->view();
+            {
+                ProfScope ps("trie_chain_walk", s);
+                hipLaunchKernelGGL((trie_prove_lookup_kernel<P>), dim3(grid), dim3(TRIE_BLOCK), 0, s, v, keys, m, oldp,
+                                   d_old_values32 ? (uint4*)d_old_values32 : value_scratch.as<uint4>());
+                LURK_HIP_CHECK(hipGetLastError());
+            }
+            // the hashes, bottom-up
+            const TrieLaunch L(t->field_id, s);
+            auto kern = trie_chain_level_kernel<P>;
+            allow_dynamic_lds((const void*)kern, (int)L.lds_bytes);
+            const uint4* below = (const uint4*)d_values32;
+            {
+                ProfScope ps("trie_chain_levels", s);
+                for (int d = H - 1; d >= 0; d--) {
+                    TrieChainLevel a;
+                    a.keys = keys;
+                    const int e = d + 1 < D ? d + 1 : D;
+                    a.ord = e ? ord_at(e) : nullptr;
+                    a.skey = d + 1 <= D ? skey_at(e) : nullptr;
+                    a.label = label;
+                    a.below = below;
+                    a.here = d == 0 && d_roots32 ? (uint4*)d_roots32 : hashes.as<uint4>() + (size_t)(d & 1) * m * 2;
+                    a.old_paths = oldp;
+                    a.new_paths = (uint4*)d_new_paths;
+                    a.old_values = (uint4*)d_old_values32;
+                    a.m = m;
+                    a.height = H;
+                    a.d = d;
+                    a.store_old = d_old_paths ? 1 : 0;
+                    hipLaunchKernelGGL(kern, dim3(grid), dim3(TRIE_BLOCK), L.lds_bytes, s, a, L.img, L.vec4, L.rf, L.rp);
+                    LURK_HIP_CHECK(hipGetLastError());
+                    below = a.here;
+                }
+            }
+            if (out_trie) {
+                // T_m's pairs: the last update of every path value (ord[D] is in path order) merged with the pairs of t that none replaces
+                const uint32_t* ord = D ? ord_at(D) : nullptr;
+                uint32_t *last = skey_in, *last_incl = entry_in, *upd = aux;
+                size_t bytes = temp.bytes;
+                hipLaunchKernelGGL(trie_chain_last_kernel, dim3(grid), dim3(TRIE_BLOCK), 0, s, label, m, last);
+                LURK_HIP_CHECK(hipGetLastError());
+                LURK_HIP_CHECK(rocprim::inclusive_scan(temp.p, bytes, last, last_incl, m, rocprim::plus<uint32_t>(), s));
+                hipLaunchKernelGGL(trie_chain_compact_kernel, dim3(grid), dim3(TRIE_BLOCK), 0, s, ord, last, last_incl, m, upd);
+                LURK_HIP_CHECK(hipGetLastError());
+                uint32_t nu32 = 0, replaced = 0;
+                LURK_HIP_CHECK(hipMemcpyAsync(&nu32, last_incl + (m - 1), 4, hipMemcpyDeviceToHost, s));
+                LURK_HIP_CHECK(hipStreamSynchronize(s));
+                const size_t nu = nu32, n = t->n;
+                uint32_t *tbelow = skey_in, *present = entry_in, *present_incl = label;  // last / last_incl / label are done with (nu <= m)
+                hipLaunchKernelGGL(trie_chain_locate_kernel, dim3(div_up(nu, TRIE_BLOCK)), dim3(TRIE_BLOCK), 0, s, v.keys, n, keys, upd, nu, H, tbelow, present);
+                LURK_HIP_CHECK(hipGetLastError());
+                bytes = temp.bytes;
+                LURK_HIP_CHECK(rocprim::inclusive_scan(temp.p, bytes, present, present_incl, nu, rocprim::plus<uint32_t>(), s));
+                LURK_HIP_CHECK(hipMemcpyAsync(&replaced, present_incl + (nu - 1), 4, hipMemcpyDeviceToHost, s));
+                LURK_HIP_CHECK(hipStreamSynchronize(s));
+                const size_t total = n + nu - replaced;
+                DevBuf mkeys(total * 32), mvalues(total * 32);
+                hipLaunchKernelGGL(trie_chain_merge_kernel, dim3(div_up(n + nu, TRIE_BLOCK)), dim3(TRIE_BLOCK), 0, s, v.keys, v.values, n, keys, (const uint4*)d_values32, upd,
+                                   nu, tbelow, present, present_incl, H, mkeys.as<uint4>(), mvalues.as<uint4>());
+                LURK_HIP_CHECK(hipGetLastError());
+                nested_ok(lurk_hip_trie_build_dev(&grown, t->field_id, H, mkeys.p, mvalues.p, total, stream));
+            }
+            LURK_HIP_CHECK(hipStreamSynchronize(s));
+        });
+        if (out_trie) *out_trie = grown;
     });
 }
 }

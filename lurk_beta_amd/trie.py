@@ -215,6 +215,32 @@ class DeviceTrie:
                                                               _lib.ptr(new_roots), _lib.ptr(stream)))
         return old, new, old_values, new_roots
 
+    def insert_chain(self, keys, values, *, paths=True, trie=True, stream=None):
+        """A chain of dependent insertions (lurk_hip_trie_insert_chain_dev): update i is applied to the trie that update i - 1 left, as
+        ``Trie.prove_insert`` called step after step -> (old paths, new paths, old values, roots, new trie); ``roots[i]`` is the root after
+        update i and ``new trie`` a ``DeviceTrie`` of the trie after the last one (this one is not modified).  ``paths=False`` leaves the
+        two path tensors out, ``trie=False`` the new trie: what was not asked for is None."""
+        import torch
+
+        dk, dv = _elems(keys), _elems(values)
+        m = dk.numel() // 4 if hasattr(dk, "numel") else 0
+        assert (dv.numel() // 4 if hasattr(dv, "numel") else 0) == m, "as many values as keys"
+        old = torch.empty((m, self.height, 8, 4), dtype=torch.int64, device="cuda") if paths else None
+        new = torch.empty_like(old) if paths else None
+        old_values = torch.empty((m, 4), dtype=torch.int64, device="cuda")
+        roots = torch.empty((m, 4), dtype=torch.int64, device="cuda")
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().lurk_hip_trie_insert_chain_dev(self._h, _lib.ptr(dk) if m else None, _lib.ptr(dv) if m else None, m, _lib.ptr(old) if paths else None,
+                                                              _lib.ptr(new) if paths else None, _lib.ptr(old_values), _lib.ptr(roots),
+                                                              ctypes.byref(h) if trie else None, _lib.ptr(stream)))
+        grown = None
+        if trie:
+            n = ctypes.c_size_t()
+            grown = DeviceTrie(h, self.field_id, self.height, 0)  # owns the handle from here on
+            _lib.check(_lib.load().lurk_hip_trie_info(h, None, None, ctypes.byref(n), None))
+            grown.n = n.value
+        return old, new, old_values, roots, grown
+
     def verify_lookup(self, keys, values, paths, roots=None, stream=None):
         """-> (codes (m,) numpy uint32, n_failed).  ``roots``: None = this trie's root for every proof, or one root per proof."""
         return verify_lookup_batch(self.field_id, self.height, self._root_dev() if roots is None else roots, keys, values, paths, stream)

@@ -2,7 +2,8 @@
 //! form (`include/lurk_hip.h`, "the sparse Poseidon trie"):
 //!
 //! * [`DeviceTrie`] - the opaque handle: one bulk build from pairs sorted by path value, then `prove_lookup` / `prove_insert` for batches
-//!   of keys and the two verifiers for batches of proofs, all on device buffers (raw pointers, as everywhere in this crate);
+//!   of keys, `insert_chain` for a sequence of dependent insertions, and the two verifiers for batches of proofs, all on device buffers
+//!   (raw pointers, as everywhere in this crate);
 //! * [`LookupProof`] / [`InsertProof`] - shaped like the reference's (`:339-369`): a `preimage_path` of `HEIGHT` preimages of `ARITY`
 //!   elements, root level first.  [`LookupProof::from_flat`] cuts them out of a batch copied back to the host, and `flat` is what a
 //!   verifier call takes.
@@ -81,6 +82,20 @@ impl DeviceTrie {
     pub unsafe fn prove_insert_dev(&self, d_keys: *const c_void, d_new_values: *const c_void, m: usize, d_old_paths: *mut c_void, d_new_paths: *mut c_void,
                                    d_old_values: *mut c_void, d_new_roots: *mut c_void, stream: *mut c_void) -> Result<(), Error> {
         check(lurk_hip_trie_prove_insert_dev(self.handle, d_keys, d_new_values, m, d_old_paths, d_new_paths, d_old_values, d_new_roots, stream))
+    }
+    /// A chain of `m` dependent insertions: update i is applied to the trie update i - 1 left (`Trie::prove_insert` step after step).
+    /// Every output may be null when it is not wanted, but not all of them; `want_trie` asks for the trie after the last update as a
+    /// new handle (this one is not modified).  Synchronises `stream`.
+    /// # Safety
+    /// device buffers: `m` keys and values in; `m * height * 8` elements per path buffer (they must not overlap), `m` old values and
+    /// `m` roots out
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn insert_chain_dev(&self, d_keys: *const c_void, d_values: *const c_void, m: usize, d_old_paths: *mut c_void, d_new_paths: *mut c_void,
+                                   d_old_values: *mut c_void, d_roots: *mut c_void, want_trie: bool, stream: *mut c_void) -> Result<Option<DeviceTrie>, Error> {
+        let mut handle = core::ptr::null_mut();
+        let out = if want_trie { &mut handle as *mut *mut lurk_hip_trie } else { core::ptr::null_mut() };
+        check(lurk_hip_trie_insert_chain_dev(self.handle, d_keys, d_values, m, d_old_paths, d_new_paths, d_old_values, d_roots, out, stream))?;
+        Ok(if want_trie { Some(DeviceTrie { handle }) } else { None })
     }
 }
 impl Drop for DeviceTrie {
