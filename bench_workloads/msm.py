@@ -217,7 +217,7 @@ def valu_roofline(acc_ms, mixed_adds):
 
 
 def msm_window_bits(args, n):
-    """the library's own choice for a key of n points (msm.hip: set_bases_device)"""
+    """the library's own choice for a key of n points (msm.hip: MsmCtx::set_bases_device)"""
     if args.window_bits:
         return args.window_bits
     if not args.precompute:

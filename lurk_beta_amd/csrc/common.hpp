@@ -156,15 +156,12 @@ class Profiler {
 
 // scopes may be open on several host threads / devices at once (the multi-device MSM): the opening event travels
 // with the scope
-// set while the calling thread records launches into a hipGraph (msm.hip): timing events do not belong in the recording
-inline thread_local bool tl_capturing = false;
-
 struct ProfScope {
     hipStream_t s;
     const char* name;
     hipEvent_t a = nullptr;
     ProfScope(const char* nm, hipStream_t st) : s(st), name(nm) {
-        if (Profiler::get().enabled() && !tl_capturing) a = Profiler::get().begin(s);
+        if (Profiler::get().enabled()) a = Profiler::get().begin(s);
     }
     ~ProfScope() {
         if (a) Profiler::get().end(name, a, s);
@@ -193,7 +190,7 @@ class DeviceWorker {
     std::thread th_;
 };
 
-// A commitment key's device-resident points as the other translation units may read them (msm.hip): table[w * npoints + i] =
+// A commitment key's device-resident points as the other translation units may read them (msm_ctx_api.hip): table[w * npoints + i] =
 // 2^(window_bits w) P_i, 64-byte Montgomery affine records ((0, 0) = identity); windows = 1 for a plain key (and for the small-commitment
 // form, whose multiples table is not exposed: its first npoints records are the points themselves)
 struct MsmTableView {
@@ -202,11 +199,11 @@ struct MsmTableView {
     int curve = 0, window_bits = 0, windows = 1, form = 0, device = 0;
 };
 MsmTableView msm_ctx_table_view(const lurk_hip_msm_ctx* ctx);
-int msm_multi_curve(const lurk_hip_msm_multi* key);  // the curve id of a multi-device key (msm.hip)
+int msm_multi_curve(const lurk_hip_msm_multi* key);  // the curve id of a multi-device key (msm_multi.hip)
 // lurk_hip_msm_ctx_wait_pair without the normalisation: the two commitments as XYZZ points (4 x 32 B each, Montgomery limbs) - the caller
 // adds to them and normalises both with one field inversion (ipa.hip: ~17 us of host time per inversion, five per round before)
 void msm_ctx_wait_pair_xyzz(lurk_hip_msm_ctx* ctx, int slot, void* out_lo_xyzz128, void* out_hi_xyzz128);
-// the parent key's folded-key context with its points replaced by d_points (m affine records on the device): msm.hip
+// the parent key's folded-key context with its points replaced by d_points (m affine records on the device): msm_folded.hip
 struct FoldedKeyLease {
     lurk_hip_msm_ctx* ctx = nullptr;
     bool owned = false;  // a private context, destroyed with the lease

@@ -55,7 +55,7 @@ void msm_launch_accumulate_persistent(const uint32_t* sorted, const Affine<P>* t
     // LURK_MSM_PERSIST_WGS workgroups per CU (1: one wave per SIMD, the form two of which are resident at once; 2: two waves per SIMD - a
     // single accumulation at the multiplier's full rate, for LURK_MSM_MAX_ACC=1)
     static const unsigned wgs = [] { const char* e = getenv("LURK_MSM_PERSIST_WGS"); int v = e ? atoi(e) : 1; return (unsigned)(v < 1 ? 1 : v > 4 ? 4 : v); }();
-    // wgs_per_cu != 0: the caller's choice for this launch (a LURK_MSM_SUBMIT_FOLLOW commitment: msm.hip)
+    // wgs_per_cu != 0: the caller's choice for this launch (a LURK_MSM_SUBMIT_FOLLOW commitment: the PERSISTENT_SLOT_STREAM form of msm_launch_plan.hpp)
     hipLaunchKernelGGL((msm_accumulate_persistent_kernel<P>), dim3((unsigned)num_cus() * (wgs_per_cu ? wgs_per_cu : wgs)), dim3(MSM_ACC_BLOCK), 0, s, sorted, table, task_info, order,
                        group_task_base, NG, partials, cursor);
 }

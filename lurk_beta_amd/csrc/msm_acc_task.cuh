@@ -4,10 +4,9 @@
 #pragma once
 #include "msm_core.cuh"
 #include "curve29.cuh"
+#include "msm_stages.hpp"
 
 namespace lurk {
-
-constexpr int MSM_ACC_BLOCK = 256;
 
 #ifndef LURK_ACC_TASK_NOINLINE
 #define LURK_ACC_TASK_NOINLINE 0

@@ -1,4 +1,4 @@
-// msm_bucket_direct.hip - stages 3-5 of the Pippenger pipeline (msm.hip) in ONE launch for commitments with few buckets.
+// msm_bucket_direct.hip - stages 3-5 of the Pippenger pipeline (msm_core.cuh; the DIRECT form of msm_launch_plan.hpp) in ONE launch for commitments with few buckets.
 //
 // The general path plans tasks of <= S sorted entries (4 launches), accumulates them (1), and sums a bucket's partials (2): seven
 // dependent launches and a round trip of the partials through memory.  That is the right shape when the accumulation is long; under a
@@ -13,6 +13,7 @@
 #include "common.hpp"
 #include "msm_core.cuh"
 #include "curve29.cuh"
+#include "msm_stages.hpp"
 
 namespace lurk {
 
@@ -102,9 +103,7 @@ __global__ __launch_bounds__(DIRECT_BLOCK) void msm_bucket_direct_big_kernel(con
 
 // lanes per bucket: the most (<= 4) that keeps NB x L within the 131 072 lanes two waves per SIMD hold and leaves a lane >= 4 entries
 // (one key space of 16-bit windows is 32 768 buckets: 4 lanes; a pair's two key spaces: 2)
-#ifdef LURK_MSM_BN254_TU
-int msm_bucket_direct_lanes(size_t NB, size_t entries);  // (defined once, in the Pasta translation unit)
-#else
+#ifndef LURK_MSM_BN254_TU  // (defined once, in the Pasta translation unit)
 int msm_bucket_direct_lanes(size_t NB, size_t entries) {
     int L = 1;
     while (L < 4 && NB * (size_t)(2 * L) <= 131072 && entries / (NB * (size_t)(2 * L)) >= 4) L *= 2;

@@ -1,20 +1,21 @@
 // msm_core.cuh - per-thread building blocks of the Pippenger MSM (shared host/device; the kernels
-// in msm.hip call these with their thread/block indices, tests/host_harness replays the same
-// pipeline serially on the CPU).
+// of the msm_*.hip units call these with their thread/block indices, tests/host_harness replays the
+// same pipeline serially on the CPU).  msm_stages.hpp and msm_sort.hpp declare the stages' launchers;
+// MsmCtx::enqueue (msm.hip) strings them together as msm_launch_plan.hpp decides.
 //
 // Pipeline (c-bit signed windows, W = ceil(256/c) windows, B = 2^(c-1) buckets per key space):
 //   1. digits      scalar -> W signed digits d_w in [-2^(c-1), 2^(c-1)]        (msm_scalar_digits)
 //   2. sort        two-pass partitioned counting sort of (point, sign) entries by key
 //                  (key = space*B + |d|-1): 2048 coarse partitions, then the low key bits inside
 //                  each partition; LDS counters only, both passes stage their output in LDS and
-//                  write it back in runs                                        (msm.hip)
+//                  write it back in runs                                        (msm_sort.hip)
 //   3. accumulate  buckets are cut into tasks of <= S sorted entries, ordered longest first; one
 //                  lane per task runs XYZZ mixed additions over gathered bases on the radix-2^29
 //                  layer (curve29.cuh: msm_task_accumulate29; msm_task_accumulate below is the
 //                  32-bit-limb statement of the same loop, kept for A/B runs and the host harness)
 //   4. finalize    per bucket: sum of its task partials (hot buckets by a workgroup tree)
 //   5. reduce      sum_b b*B_b = S + sum_k 2^k P_k: bit-plane merge tree (c-1 levels of depth one
-//                  addition) + Horner                                           (msm.hip)
+//                  addition) + Horner                                           (msm_reduce.hip)
 //   6. combine     sum_w 2^(c*w) * W_w on the host over <= 16 points (sequential doublings: a
 //                  latency-bound tail that one host core runs ~20x faster than one GPU lane)
 // "Key space" = set of buckets entries are sorted into: one per window in the plain mode (G = W,

@@ -1,6 +1,6 @@
-// msm_finalize.hip - stage 5 of the Pippenger pipeline (msm.hip): a bucket's task partials become the bucket.
+// msm_finalize.hip - stage 5 of the Pippenger pipeline (msm_core.cuh; launched by MsmCtx::enqueue, msm.hip): a bucket's task partials become the bucket.
 //
-// One lane per bucket sums its <= MSM_SMALL partials; fuller buckets go on a list for msm_big_bucket_kernel (msm.hip).  A lane's
+// One lane per bucket sums its <= MSM_FIN_SMALL partials; fuller buckets go on a list for msm_big_bucket_kernel (msm_plan.hip).  A lane's
 // additions are DEPENDENT, so what the stage costs is nt - 1 times the latency of one general addition on a lane: round 5 moved them
 // from the 8 x 32 group law (~20 us each with one or two waves per SIMD) to the radix-2^29 layer (xyzz_sum_via29: 6.4 us).  It
 // matters where a commitment is short: the opening argument's rounds under its folded 65 536-point key (8-entry tasks, 2-5 partials
@@ -8,10 +8,9 @@
 #include "common.hpp"
 #include "msm_core.cuh"
 #include "curve29.cuh"
+#include "msm_stages.hpp"
 
 namespace lurk {
-
-constexpr int MSM_FIN_SMALL = 16;  // = MSM_SMALL of msm.hip (buckets with more partials are summed by a workgroup)
 
 #ifndef LURK_FINALIZE_WAVES  // waves per SIMD the compiler is to leave room for (4 -> 128 VGPRs, 2 -> 256): msm_finalize_bn254.hip sets 2
 #define LURK_FINALIZE_WAVES 4

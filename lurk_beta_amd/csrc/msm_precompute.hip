@@ -2,6 +2,7 @@
 #include "common.hpp"
 #include "msm_core.cuh"
 #include "msm_precompute.cuh"
+#include "msm_stages.hpp"
 
 namespace lurk {
 

@@ -1,4 +1,4 @@
-// msm_reduce.hip - the bucket reduction of the Pippenger pipeline (msm.hip, stage 6).
+// msm_reduce.hip - the bucket reduction of the Pippenger pipeline (msm_core.cuh, stage 6; launched by MsmCtx::enqueue, msm.hip).
 //
 // sum_b b * B_b with bucket b at index b - 1:  sum (idx + 1) X_idx = S + sum_k 2^k P_k,  S = sum X,  P_k = sum of the X whose idx has
 // bit k set.  The (S, P_0 .. P_{k-1}) vectors of two adjacent segments of 2^k buckets merge with k + 1 independent additions (the new
@@ -258,9 +258,7 @@ __global__ LURK_REDUCE_BOUNDS void msm_planes29_wave_kernel(const Plane29<P>* __
     }
 }
 
-#ifdef LURK_MSM_BN254_TU
-size_t msm_reduce_plane_bytes(size_t nb);  // (defined once, in the Pasta translation unit)
-#else
+#ifndef LURK_MSM_BN254_TU  // (defined once, in the Pasta translation unit)
 size_t msm_reduce_plane_bytes(size_t nb) { return nb * 160; }
 #endif
 

@@ -2,7 +2,7 @@
 //
 // Who needs it: the secondary-curve half of every folding step commits ~10^4-element vectors twice
 // (/root/reference/src/proof/nova.rs:291-293 -> arecibo NIFS::prove on the secondary circuit), and SuperNova's small
-// coprocessor circuits do the same (/root/reference/src/proof/supernova.rs:242-244).  Through the bucket pipeline of msm.hip such a
+// coprocessor circuits do the same (/root/reference/src/proof/supernova.rs:242-244).  Through the bucket pipeline (MsmCtx::enqueue, msm.hip) such a
 // commitment is ~45 dependent launches and a 2^15-bucket reduction: 0.45 ms of latency for 14 us worth of additions.
 //
 // Why not LDS-resident buckets here: a lane needs ~4.5 us for one dependent mixed addition (2 200 VALU instructions at one
@@ -30,6 +30,7 @@
 #include "common.hpp"
 #include "msm_core.cuh"
 #include "curve29.cuh"
+#include "msm_stages.hpp"
 
 namespace lurk {
 
@@ -192,10 +193,7 @@ __global__ __launch_bounds__(SMALL_BLOCK) void msm_small_kernel(const uint4* __r
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-#ifdef LURK_MSM_BN254_TU  // (the sizing functions are defined once, in the Pasta translation unit)
-unsigned msm_small_groups(size_t n, int c);
-size_t msm_small_scratch_bytes();
-#else
+#ifndef LURK_MSM_BN254_TU  // (the sizing functions are defined once, in the Pasta translation unit)
 int msm_small_window_bits(size_t n) { return n <= ((size_t)1 << 14) ? 8 : 6; }
 size_t msm_small_table_entries(size_t n, int c) { return (n * (size_t)msm_num_windows(c)) << (c - 1); }
 unsigned msm_small_groups(size_t n, int c) {

@@ -1,5 +1,5 @@
 // msm_sort.hip - the two-pass partitioned counting sort of a commitment's signed window digits (stage 2 of msm_core.cuh's
-// pipeline; the caller is arecibo's CommitmentEngine::commit through msm.hip: /root/reference/src/proof/nova.rs:287-293).
+// pipeline; the caller is arecibo's CommitmentEngine::commit through MsmCtx::enqueue, msm.hip: /root/reference/src/proof/nova.rs:287-293).
 // msm_sort.hpp describes the passes and what round 5 changed.
 #include "msm_sort.hpp"
 

@@ -1,5 +1,6 @@
 // msm_sort.hpp - stage 2 of the MSM pipeline (msm_core.cuh): the two-pass partitioned counting sort of the signed window digits.
-// The kernels live in msm_sort.hip; msm.hip sizes the workspaces from the shape and calls msm_launch_sort.
+// The kernels live in msm_sort.hip; MsmCtx (msm.hip) sizes the workspaces from the shape and calls msm_launch_sort.  The later stages'
+// interfaces are in msm_stages.hpp.
 //
 // Round 5 ("one digit extraction instead of three"): a commitment used to read its scalars three times (a
 // Montgomery -> canonical pass, then both sweeps of sort pass 1) and recode each scalar's W signed digits three times with a
@@ -44,7 +45,7 @@ struct MsmShape {
     int S;                 // sorted entries per accumulation task: MSM_S, less when that would leave lanes idle (small commitments)
     int sel;               // >= 0: TWO key spaces chosen by bit `sel` of the scalar's index (a pair of commitments with disjoint supports
                            // in one pass: the two halves of an inner-product-argument round); -1: off
-    int low_prio;          // 1: the sort's kernels run at the lowest wave priority (a LURK_MSM_SUBMIT_FOLLOW commitment, msm.hip); 0: raised
+    int low_prio;          // 1: the sort's kernels run at the lowest wave priority (a LURK_MSM_SUBMIT_FOLLOW commitment: msm_launch_plan.hpp); 0: raised
 };
 
 inline size_t msm_scatter1_lds(int P, int W, int tile) { return (size_t)(3 * P + 32) * 4 + (size_t)W * tile * 8; }

@@ -231,7 +231,7 @@ static void fold_challenge_finish(lurk_hip_fold_ctx* c, void* r32_mont) {
 static lurk_hip_msm_ctx* fold_staged_key(lurk_hip_fold_ctx* c, int b) { return c->helper_of[b] >= 0 ? c->helpers[c->helper_of[b]]->key : c->key; }
 
 // The scheduling class of a commitment staged AHEAD of its step (the next step's commit(W2) while a step is open).  Default
-// LURK_MSM_SUBMIT_FOLLOW (round 6, msm.hip: submit_impl): its sort and plan run at once at the lowest wave priority, its accumulation -
+// LURK_MSM_SUBMIT_FOLLOW (round 6, msm.hip: submit_impl, msm_launch_plan.hpp): its sort and plan run at once at the lowest wave priority, its accumulation -
 // persistent, two waves per SIMD, lowest priority - starts when the open step's commit(T) has left the accumulate stage and fills the
 // window the step's serial chain leaves (T's bucket reduction, the transcript, the folds, the next cross term), its tail keeps the raised
 // priority (the next begin waits for it).  commit(T)'s accumulation keeps the VALU to itself.  Measured at rc = 100 with the witness

@@ -485,6 +485,23 @@ extern "C" int hh_keyfold_plan(const uint64_t* weights, size_t T, size_t m, int 
 
 
 // ---------------------------------------------------------------------------------------------
+// The MSM's launch plan (msm_launch_plan.hpp, asked by MsmCtx in msm.hip once per commitment): cls = -1 for a synchronous call, else the
+// LURK_MSM_SUBMIT_* value; the four switches as given (nothing is read from the environment).  out4 = {form (0 DIRECT, 1 PLAIN,
+// 2 PERSISTENT_ACC_STREAM, 3 PERSISTENT_SLOT_STREAM), low_prio, wgs_per_cu, uses_acc_stream}.
+#include "../../lurk_beta_amd/csrc/msm_launch_plan.hpp"
+extern "C" void hh_msm_launch_plan(int cls, size_t entries, uint32_t NB, int persistent, size_t persistent_min, int bucket_direct, int follow_wgs, int* out4) {
+    lurk::MsmTuning tn;
+    tn.persistent = persistent;
+    tn.persistent_min = persistent_min;
+    tn.bucket_direct = bucket_direct;
+    const lurk::MsmLaunchPlan pl = lurk::msm_launch_plan((lurk::MsmSubmitClass)cls, entries, NB, tn, follow_wgs);
+    out4[0] = pl.form == lurk::MsmAccForm::DIRECT ? 0 : pl.form == lurk::MsmAccForm::PLAIN ? 1 : pl.form == lurk::MsmAccForm::PERSISTENT_ACC_STREAM ? 2 : 3;
+    out4[1] = pl.low_prio ? 1 : 0;
+    out4[2] = (int)pl.wgs_per_cu;
+    out4[3] = pl.uses_acc_stream ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // The NTT's wave-resident passes (ntt.hip: ntt_device, log_n >= 12) as a plain radix-2 decimation-in-time with the kernel's value
 // sequence and pass plan, every bound of ntt29.cuh asserted: the first pass converts with in_c = 2^522 mod p, a pass runs ns lazy
 // ntt_bfly stages with the table's twiddles in canonical form (ntt_twiddle29), values leave a pass through f29_reduce + f29_pack (< 2^255.1), a later pass

@@ -464,6 +464,58 @@ def test_key_fold_plan_digits_recombine_to_the_weights(kb, Wt, log_t, m):
 
 
 
+_SYNC, _DEFAULT, _FOREGROUND, _BACKGROUND, _FOLLOW = -1, 0, 1, 2, 3  # a synchronous call, then the LURK_MSM_SUBMIT_* values of lurk_hip.h
+_DIRECT, _PLAIN, _PERSISTENT_ACC_STREAM, _PERSISTENT_SLOT_STREAM = 0, 1, 2, 3
+_M = 1 << 20
+# (class, entries = W n, keys NB, form, low_prio, waves per SIMD); the switches: persistent, persistent_min, bucket_direct, follow waves
+_LAUNCH_PLAN_ROWS = [
+    ((1, 24 * _M, 1, 2), [
+        (_SYNC, _M, 65536, _DIRECT, 0, 0),
+        (_SYNC, 2 * _M, 131072, _DIRECT, 0, 0),
+        (_SYNC, 2 * _M + 1, 131072, _PLAIN, 0, 0),
+        (_SYNC, 2 * _M, 131073, _PLAIN, 0, 0),
+        (_SYNC, 64 * _M, 1 << 19, _PLAIN, 0, 0),
+        (_DEFAULT, _M, 65536, _DIRECT, 0, 0),
+        (_DEFAULT, 24 * _M - 1, 1 << 19, _PLAIN, 0, 0),
+        (_DEFAULT, 24 * _M, 1 << 19, _PERSISTENT_ACC_STREAM, 0, 0),
+        (_FOREGROUND, _M, 65536, _DIRECT, 0, 0),
+        (_FOREGROUND, 64 * _M, 1 << 19, _PLAIN, 0, 0),
+        (_BACKGROUND, _M, 65536, _PERSISTENT_ACC_STREAM, 0, 0),
+        (_FOLLOW, _M, 65536, _DIRECT, 1, 0),
+        (_FOLLOW, 4 * _M, 1 << 19, _PERSISTENT_SLOT_STREAM, 1, 2),
+    ]),
+    ((1, 24 * _M, 1, 0), [(_FOLLOW, 4 * _M, 1 << 19, _PLAIN, 1, 0)]),
+    ((2, 24 * _M, 1, 2), [
+        (_DEFAULT, _M, 65536, _PERSISTENT_ACC_STREAM, 0, 0),
+        (_SYNC, _M, 65536, _DIRECT, 0, 0),
+        (_FOREGROUND, _M, 65536, _DIRECT, 0, 0),
+    ]),
+    ((0, 24 * _M, 1, 2), [
+        (_DEFAULT, 64 * _M, 1 << 19, _PLAIN, 0, 0),
+        (_BACKGROUND, 64 * _M, 1 << 19, _PERSISTENT_ACC_STREAM, 0, 0),
+    ]),
+    ((1, 24 * _M, 0, 2), [(_SYNC, _M, 65536, _PLAIN, 0, 0)]),
+]
+
+
+def test_msm_launch_plan_table():
+    """msm_launch_plan.hpp: which form of the bucket accumulation each class of commitment takes, as a table of literal rows - the
+    default switches (LURK_MSM_ACC_PERSISTENT=1, LURK_MSM_PERSISTENT_MIN_MENTRIES=24, LURK_MSM_BUCKET_DIRECT=1, LURK_MSM_FOLLOW_WGS=2)
+    on both sides of every threshold, then one switch changed at a time.  A commitment has an accumulate stream of its own exactly when it
+    was submitted as DEFAULT or BACKGROUND."""
+    import ctypes
+
+    lib = H.lib()
+    checked = 0
+    for (persistent, persistent_min, bucket_direct, follow_wgs), rows in _LAUNCH_PLAN_ROWS:
+        for cls, entries, nb, form, low_prio, wgs in rows:
+            out = (ctypes.c_int * 4)()
+            lib.hh_msm_launch_plan(cls, ctypes.c_size_t(entries), ctypes.c_uint32(nb), persistent, ctypes.c_size_t(persistent_min), bucket_direct, follow_wgs, out)
+            assert list(out) == [form, low_prio, wgs, 1 if cls in (_DEFAULT, _BACKGROUND) else 0], (cls, entries, nb, persistent, bucket_direct, follow_wgs)
+            checked += 1
+    assert checked == 20
+
+
 def _ntt_wave(f, a, log_n, inverse=False):
     b = np.ascontiguousarray(a, dtype=np.uint64).copy()
     H.lib().hh_ntt_wave(f, vp(b), log_n, int(inverse))
