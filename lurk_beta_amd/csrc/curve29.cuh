@@ -362,15 +362,92 @@ LURK_HD Xyzz<P> xyzz_sum_via29(const Xyzz<P>* pts, uint32_t nt) {
     return xyzz29_to_xyzz<P>(acc, acc_id);
 }
 
+// A 64-byte table record in flight: four 16-byte words exactly as the loads return them (one global_load_dwordx4 each).  The
+// pipelined task loop holds the NEXT record in this form across a whole mixed addition and turns it into an Affine<P> only when its
+// turn comes: held as an Affine<P> the persistent kernel takes 194 registers, in this form it stays inside its budget of 192.
+// (a GCC / clang vector type, so that hipcc keeps each word one load and g++ builds the same header for the host harness)
+typedef uint32_t Rec16 __attribute__((vector_size(16), may_alias));
+struct Rec64 {
+    Rec16 q[4];
+};
+template <class P>
+LURK_HD Rec64 rec64_load(const Affine<P>* table, uint32_t e) {
+    static_assert(sizeof(Affine<P>) == 64 && alignof(Affine<P>) >= 16, "a table record is four aligned 16-byte words");
+    const Rec16* p = reinterpret_cast<const Rec16*>(table + (e & 0x7fffffffu));
+    Rec64 r;
+#pragma unroll
+    for (int i = 0; i < 4; i++) r.q[i] = p[i];
+    return r;
+}
+template <class P>
+LURK_HD Affine<P> rec64_affine(const Rec64& r) {
+    Affine<P> a;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        a.x.l[i] = r.q[i >> 2][i & 3];
+        a.y.l[i] = r.q[2 + (i >> 2)][i & 3];
+    }
+    return a;
+}
+// One step of the pipelined loop, taken in front of addition j: hands out record j (loaded one trip ago) with its sign and puts
+// record j + 1 and index j + 2 in flight.  Past the end of the task the look-ahead is clamped to what was read before (index j
+// again, and on the last trip the record that index names), so nothing is read beyond sorted[last - 1] or beyond the record of a
+// real entry of this task; what the clamped loads return is never used.
+template <class P>
+LURK_HD Affine<P> msm_task_next29(const uint32_t* sorted, const Affine<P>* table, uint32_t j, uint32_t last, bool& neg_next, uint32_t& e_ahead,
+                                  Rec64& rec, bool& negate) {
+    const Affine<P> q = rec64_affine<P>(rec);
+    negate = neg_next;
+    neg_next = (e_ahead & 0x80000000u) != 0;
+    rec = rec64_load<P>(table, e_ahead);         // entry j + 1 (on the last trip: an earlier entry of the task)
+    e_ahead = sorted[j + 2 < last ? j + 2 : j];  // (clamped on the last two trips)
+    return q;
+}
+
 // One accumulation task on the radix-2^29 layer: the signed table records sorted[first .. last) summed into (acc, acc_id), which
 // leave R-bounded (msm_task_accumulate29 returns them as an ordinary XYZZ point; msm_bucket_direct.hip keeps them on this layer).
-template <class P>
+// PIPELINED (the persistent kernel only): the same additions with the same arguments in the same order, the gather of record j + 1
+// and the load of index j + 2 issued in front of addition j, so that the only exposed gather of a task is its first.
+template <class P, bool PIPELINED = false>
 LURK_HD void msm_task_accumulate29_raw(const uint32_t* sorted, uint32_t first, uint32_t last, const Affine<P>* table, Xyzz29<P>& acc, bool& acc_id) {
     acc.x = acc.y = acc.zz = acc.zzz = f29_zero<P>();
     acc_id = true;
-    // (gathering the next base ahead of the current addition was measured: no gain, the other waves of the SIMD
-    // already cover the load; so was requesting one dword of it ahead - a one-VGPR "touch" for L2 and the TLB - 3.6 against
-    // 3.5 ms, although confining every gather to a 64 MB window of the 3.25 GiB table does make the kernel 8 % faster)
+    // Every trip of the plain loop below waits for two dependent loads (sorted[j], then the 64-byte record it names: a random read
+    // from a table of up to 3.25 GiB) in front of ~2 100 VALU instructions.  In the plain launch, three waves per SIMD, the other
+    // waves cover that wait: gathering the next base ahead was measured THERE with no gain, and so was requesting one dword of it
+    // ahead - a one-VGPR "touch" for L2 and the TLB - 3.6 against 3.5 ms (although confining every gather to a 64 MB window of the
+    // 3.25 GiB table does make the kernel 8 % faster); at 162 registers the plain kernel has no room for a record in flight either
+    // (16 more and it runs two waves per SIMD).  The persistent kernel of commitments in flight runs ONE wave per SIMD, whose wait
+    // nothing covers, and has the room: up to 192 registers two of its launches still sit beside a 128-register tail wave
+    // (tests/test_cabi_exports.py::test_sort_kernels_fit_beside_a_resident_accumulation).  It takes the PIPELINED loop: one
+    // accumulation alone on the device 4.00 -> 3.53 ms at 2^22, 0.85 -> 0.97 of the plain launch's rate.
+    if (PIPELINED) {
+        if (first >= last) return;
+        const uint32_t e_first = sorted[first];
+        bool neg_next = (e_first & 0x80000000u) != 0;
+        Rec64 rec = rec64_load<P>(table, e_first);
+        uint32_t e_ahead = sorted[first + 1 < last ? first + 1 : first];
+        uint32_t j = first;
+        bool negate;
+#if LURK_ACC_AFFINE_FIRST
+        {  // first base: a copy (zz = zzz = 1)
+            const Affine<P> q = msm_task_next29<P>(sorted, table, j, last, neg_next, e_ahead, rec, negate);
+            xyzz29_madd<P>(acc, acc_id, q, negate);
+            j++;
+        }
+        if (j < last) {  // second base: affine + affine (unless the first was the identity record)
+            const Affine<P> q = msm_task_next29<P>(sorted, table, j, last, neg_next, e_ahead, rec, negate);
+            if (!acc_id) xyzz29_madd<P, true>(acc, acc_id, q, negate);
+            else xyzz29_madd<P>(acc, acc_id, q, negate);
+            j++;
+        }
+#endif
+        for (; j < last; j++) {
+            const Affine<P> q = msm_task_next29<P>(sorted, table, j, last, neg_next, e_ahead, rec, negate);
+            xyzz29_madd<P>(acc, acc_id, q, negate);
+        }
+        return;
+    }
 #if LURK_ACC_AFFINE_FIRST
     uint32_t j = first;
     if (j < last) {  // first base: a copy (zz = zzz = 1)
@@ -403,11 +480,11 @@ LURK_HD void msm_task_accumulate29_raw(const uint32_t* sorted, uint32_t first, u
     }
 #endif
 }
-template <class P>
+template <class P, bool PIPELINED = false>
 LURK_HD Xyzz<P> msm_task_accumulate29(const uint32_t* sorted, uint32_t first, uint32_t last, const Affine<P>* table) {
     Xyzz29<P> acc;
     bool acc_id;
-    msm_task_accumulate29_raw<P>(sorted, first, last, table, acc, acc_id);
+    msm_task_accumulate29_raw<P, PIPELINED>(sorted, first, last, table, acc, acc_id);
     return xyzz29_to_xyzz<P>(acc, acc_id);
 }
 

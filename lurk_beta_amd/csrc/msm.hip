@@ -411,7 +411,7 @@ struct MsmCtx : MsmCtxBase {
             break;
         }
         case MsmAccForm::PERSISTENT_SLOT_STREAM: {
-            // the registers two waves per SIMD leave (512 - 2 x 176) hold the waves of what the open step's serial chain launches
+            // the registers two waves per SIMD leave (512 - 2 x 192 = 128) hold the waves of what the open step's serial chain launches
             // meanwhile - the reduction levels of commit(T), the folds, the next cross term - where a plain launch (three waves, 504
             // registers) made every one of them queue for an accumulate wave to retire
             wk.placement_valid = true;  // (the cursor block was zeroed by msm_part_start_kernel)
@@ -558,7 +558,7 @@ struct MsmCtx : MsmCtxBase {
                 // when commit(T)'s accumulation ends); its accumulation waits for the END of the followed commitment's accumulation
                 // (the event that commitment's enqueue recorded: the caller's thread has returned from it; an event of an earlier,
                 // finished commitment - or one never recorded - orders nothing) and is the persistent form with LURK_MSM_FOLLOW_WGS waves
-                // per SIMD, lowest priority: what two waves leave of a SIMD's registers (512 - 2 x 176) holds the waves of commit(T)'s
+                // per SIMD, lowest priority: what two waves leave of a SIMD's registers (512 - 2 x 192 = 128) holds the waves of commit(T)'s
                 // reduction levels, the folds and the next cross term, where a plain launch (three waves, 504 registers) made each of
                 // them queue for an accumulate wave to retire (measured: a 60 us fold 320 us, the reduction 0.35 -> 0.70 ms).  Its
                 // TAIL keeps the raised priority: the next step's begin waits for this commitment as well as for its own commit(T).

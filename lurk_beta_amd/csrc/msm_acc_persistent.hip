@@ -1,10 +1,14 @@
 // msm_acc_persistent.hip - the persistent form of the bucket accumulation (commitments in flight; round 6: the accumulation of a
 // LURK_MSM_SUBMIT_FOLLOW commitment), in its own translation unit so that it CAN be built for another register footprint than the
-// plain launch of msm_acc.hip (Makefile: PERSIST_FLAGS / PERSIST_DEFS).  The SHIPPED build sets neither: the kernel takes ~176 VGPRs,
-// the same code as the plain launch (msm_acc_task.cuh).  What has to run beside resident accumulations is sized for THAT footprint and
-// checked on the compiler's own numbers (tests/test_cabi_exports.py::test_sort_kernels_fit_beside_a_resident_accumulation): four waves
-// of a 1024-thread sort workgroup beside ONE 176-register wave, a 128-register tail wave beside TWO.  (A 144-register build - machine
-// LICM off - lets the 56-register sort passes sit beside two; measured in round 4, +1.7 % in flight, -4 % for the folding step: not shipped.)
+// plain launch of msm_acc.hip (Makefile: PERSIST_FLAGS / PERSIST_DEFS).  The SHIPPED build sets neither.  The kernel runs the same
+// additions as the plain launch (msm_acc_task.cuh); launched with one wave per SIMD it runs them through the PIPELINED task loop of
+// curve29.cuh, which keeps the next table record (16 registers) and the index after it in flight under the current addition: 192 VGPRs
+// where the plain loop takes 176.  192 is the
+// budget, not an accident: what has to run beside resident accumulations is sized for it and checked on the compiler's own numbers
+// (tests/test_cabi_exports.py::test_sort_kernels_fit_beside_a_resident_accumulation, tests/test_acc_pipeline_resources.py): four waves
+// of a 1024-thread sort workgroup beside ONE 192-register wave (4 x 72 + 192 <= 512), a 128-register tail wave beside TWO
+// (128 + 2 x 192 = 512).  One granule more and the second launch waits for the tail kernels.  (A 144-register build of the plain loop -
+// machine LICM off - lets the 56-register sort passes sit beside two; measured in round 4, +1.7 % in flight, -4 % for the folding step: not shipped.)
 #ifndef LURK_ACC_RADIX29
 #define LURK_ACC_RADIX29 1
 #endif
@@ -27,11 +31,22 @@ __device__ __forceinline__ uint32_t msm_cu_index() {
 // 64 tasks of the longest-first order from a global cursor.  The kernel then never holds more than its share of every
 // SIMD's registers and wave slots, so the latency / HBM-bound kernels of the NEXT commitment (sort, plan, bucket
 // reduction: other stream, higher priority) find room on every CU while this one keeps the integer VALU busy.
-template <class P>
+// PIPELINED: the task loop that gathers the next table record under the current addition (curve29.cuh) - the launch with ONE wave per
+// SIMD, whose loads nothing else covers.  A launch with two or more waves per SIMD (a LURK_MSM_SUBMIT_FOLLOW commitment,
+// LURK_MSM_PERSIST_WGS) keeps the plain loop at 176 registers: its waves cover each other, and what a folding step runs beside a
+// two-wave accumulation needs the 160 registers that 2 x 176 leave, not the 128 of 2 x 192 (measured: the rc = 100 step 2.95-2.99 ->
+// 3.12-3.19 ms with the pipelined loop in the FOLLOW class; profiles/r13_acc_pipeline_bench.json).
+template <class P, bool PIPELINED>
 #ifndef LURK_PERSIST_MIN_BLOCKS
 #define LURK_PERSIST_MIN_BLOCKS 1  // (HIP: minimum WAVES per SIMD) 4: the compiler holds the kernel to 128 registers (and spills the rest)
 #endif
-__global__ __launch_bounds__(MSM_ACC_BLOCK, LURK_PERSIST_MIN_BLOCKS) void msm_accumulate_persistent_kernel(const uint32_t* __restrict__ sorted, const Affine<P>* __restrict__ table,
+// The register budget is handed to the compiler as well (it binds only the pipelined instantiations).  Left alone it parks ~23 constants of the task epilogue (xyzz29_to_xyzz) in
+// VGPRs across the whole task loop and the BN254 instantiations come out at 194; told the limit it rematerialises two of them after
+// the loop instead (190, no scratch; the Pasta kernels are at 192 either way).  amdgpu_num_vgpr counts registers of the UNIFIED file
+// of gfx90a and later in halves (the backend doubles the number: AMDGPUSubtarget::getMaxNumVGPRs), so 96 here is a limit of 192;
+// tests/test_acc_pipeline_resources.py fails if a compiler ever reads it another way (the kernel would spill).
+#define LURK_PERSIST_VGPR_BUDGET 192
+__global__ __launch_bounds__(MSM_ACC_BLOCK, LURK_PERSIST_MIN_BLOCKS) __attribute__((amdgpu_num_vgpr(LURK_PERSIST_VGPR_BUDGET / 2))) void msm_accumulate_persistent_kernel(const uint32_t* __restrict__ sorted, const Affine<P>* __restrict__ table,
                                                                                     const uint2* __restrict__ task_info,
                                                                                     const uint32_t* __restrict__ order,
                                                                                     const uint32_t* __restrict__ group_task_base, int NG,
@@ -44,7 +59,7 @@ __global__ __launch_bounds__(MSM_ACC_BLOCK, LURK_PERSIST_MIN_BLOCKS) void msm_ac
         if (lane == 0) base = atomicAdd(cursor, 64u);
         base = __builtin_amdgcn_readfirstlane(base);  // wave-uniform: the loop control stays scalar
         if (base >= ntasks) break;
-        if (base + lane < ntasks) msm_accumulate_task<P>(base + lane, sorted, table, task_info, order, partials);
+        if (base + lane < ntasks) msm_accumulate_task<P, PIPELINED>(base + lane, sorted, table, task_info, order, partials);
     }
 }
 
@@ -56,8 +71,13 @@ void msm_launch_accumulate_persistent(const uint32_t* sorted, const Affine<P>* t
     // single accumulation at the multiplier's full rate, for LURK_MSM_MAX_ACC=1)
     static const unsigned wgs = [] { const char* e = getenv("LURK_MSM_PERSIST_WGS"); int v = e ? atoi(e) : 1; return (unsigned)(v < 1 ? 1 : v > 4 ? 4 : v); }();
     // wgs_per_cu != 0: the caller's choice for this launch (a LURK_MSM_SUBMIT_FOLLOW commitment: the PERSISTENT_SLOT_STREAM form of msm_launch_plan.hpp)
-    hipLaunchKernelGGL((msm_accumulate_persistent_kernel<P>), dim3((unsigned)num_cus() * (wgs_per_cu ? wgs_per_cu : wgs)), dim3(MSM_ACC_BLOCK), 0, s, sorted, table, task_info, order,
-                       group_task_base, NG, partials, cursor);
+    const unsigned waves = wgs_per_cu ? wgs_per_cu : wgs;  // per SIMD
+    if (waves == 1)
+        hipLaunchKernelGGL((msm_accumulate_persistent_kernel<P, true>), dim3((unsigned)num_cus()), dim3(MSM_ACC_BLOCK), 0, s, sorted, table, task_info, order,
+                           group_task_base, NG, partials, cursor);
+    else
+        hipLaunchKernelGGL((msm_accumulate_persistent_kernel<P, false>), dim3((unsigned)num_cus() * waves), dim3(MSM_ACC_BLOCK), 0, s, sorted, table, task_info, order,
+                           group_task_base, NG, partials, cursor);
 }
 #define LURK_ACC_PERSISTENT_INSTANTIATE(P)                                                                                                    \
     template void msm_launch_accumulate_persistent<P>(const uint32_t*, const Affine<P>*, const uint2*, const uint32_t*, const uint32_t*, int, \

@@ -266,7 +266,11 @@ class DeviceTrie:
         self.close()
 
     def __del__(self):
-        # a handle that was never closed gives its device memory back when it is collected; nothing can be raised from here
+        # a handle that was never closed gives its device memory back when it is collected; nothing can be raised from here.  A closed
+        # one has nothing left to give back, whenever the collector gets to it (a closed trie kept alive by a traceback is collected
+        # at some later collection, not when its last name goes)
+        if getattr(self, "_h", None) is None:
+            return
         try:
             self.close()
         except Exception:
