@@ -442,6 +442,73 @@ typedef struct {
 int lurk_hip_store_hydrate(int field_id, const lurk_hip_store_node* nodes, size_t n, const void* values32, size_t n_values,
                            void* digests32, size_t* levels);
 
+/* ---- the store, resident on the device -----------------------------------------------------------------------------------
+ * lurk_hip_store_hydrate is one shot: the whole DAG up, every node hashed, every digest down.  StoreCore is append-only and keeps its
+ * digest memo (z_cache) for its whole life (/root/reference/src/lem/store_core.rs:199-248); hydrate_z_cache (:256-269) hashes what has
+ * been interned since the last hydration, and Prover::prove hydrates before every proof (/root/reference/src/proof/mod.rs:180-198).
+ * A lurk_hip_store is that memo in HBM; fields LURK_FIELD_PALLAS_FP, _PALLAS_FQ and _BN254_FR (another id: "unknown field id").
+ *   node ids   assigned in append order, the first node ever appended is 0; a store holds fewer than 2^31 nodes
+ *   device     per node id the canonical digest (32 B; an atom's digest is its value) and the tag (4 B): 36 B per node of capacity
+ *   host       per node its level, its tag, and a copy of the digest of the nodes the host hashed or once fetched (below)
+ *   threads    appends to one store are serialised by the library; the two _dev readers may run on any stream once an append has
+ *              returned.  An append concurrent with readers of the same store is the caller's error (growth moves the arrays).
+ * Nodes are not interned or deduplicated: the host's Store interns, and ids are the caller's.  Every call must be made with the store's
+ * device current (lurk_hip_store_info's *device). */
+typedef struct lurk_hip_store lurk_hip_store;
+/* reserve_nodes: the initial capacity, 0 = the library's default (2^16).  Capacity grows geometrically on demand (at least doubling), the
+ * resident arrays moved by ONE device-to-device copy; the digest array never crosses PCIe, at any growth. */
+int lurk_hip_store_create(lurk_hip_store** s, int field_id, size_t reserve_nodes);
+int lurk_hip_store_destroy(lurk_hip_store* s);
+/* any output may be NULL.  *levels: the depth of the DAG held (an atom is level 0); *hashes_done: the Poseidon hashes performed since
+ * creation, on the host and on the device - after any sequence of appends it equals the number of non-atom nodes, each hashed once. */
+int lurk_hip_store_info(const lurk_hip_store* s, int* field_id, size_t* n_nodes, size_t* levels, size_t* hashes_done, size_t* capacity, int* device);
+/* n_new further nodes, which receive the ids *first_id .. *first_id + n_new - 1 (first_id may be NULL).  The records are those of
+ * lurk_hip_store_hydrate with
+ *   child[k]   a GLOBAL node id, smaller than the id the node itself receives: from an earlier append or from earlier in this batch
+ *              (any prefix of a topologically ordered DAG is a valid batch)
+ *   value      (an atom's value, a commitment's secret) an index into THIS call's values32 (n_values x 32 B canonical, reduced); no
+ *              value array stays resident
+ * Only the new nodes are hashed, grouped by (level, arity) as the one-shot call groups them: a group of more than 6 nodes is one gather
+ * of its preimages from the resident arrays and one batch of the Poseidon kernel, a narrower one goes to the library's host Poseidon.
+ * Within the append, digests change sides as in the one-shot call (one copy when a group changes sides), so appending a whole DAG in
+ * one call costs about what lurk_hip_store_hydrate costs.  Digests of children from EARLIER appends that a narrow group needs and the
+ * host holds no copy of come down once per append (one indexed gather, one copy).  Host-hashed digests are in the device array before
+ * the call returns.  new_digests32_or_null: NULL, or n_new x 32 B for the digests of the new nodes - with NULL no digest crosses PCIe but
+ * those narrow groups need.  The call synchronises (the null stream).
+ *   refusals   every argument is checked on the host before anything is allocated, launched or changed; a refused append leaves the
+ *              store exactly as it was.  LURK_HIP_ERR_INVALID_ARG, the message opening with "record <i>: " for the first offending
+ *              record i of this call: "unknown node kind"; "nodes must be in topological order (children first)" (a child id that is
+ *              not smaller than the node's own, within or beyond the store); "atom value index out of range" / "commitment secret
+ *              index out of range"; "value <v> is not reduced modulo the field order".  "too many nodes" at 2^31.
+ *   growth     an allocation failure, of the grown arrays or of the call's scratch, is LURK_HIP_ERR_OOM with the store unchanged
+ * n_new == 0 is legal and does nothing. */
+int lurk_hip_store_append(lurk_hip_store* s, const lurk_hip_store_node* nodes, size_t n_new, const void* values32, size_t n_values, size_t* first_id,
+                          void* new_digests32_or_null);
+/* d_out32[j] = the digest of node d_ids[j] (device arrays, m < 2^31).  Stream-ordered, does not synchronise.  The ids are not read on the
+ * host: an id >= n_nodes reads nothing and its row is ZERO. */
+int lurk_hip_store_digests_dev(const lurk_hip_store* s, const uint32_t* d_ids, size_t m, void* d_out32, void* stream);
+/* the same with host arrays; an id >= n_nodes is refused ("id <j> is out of range").  Synchronises. */
+int lurk_hip_store_digests(const lurk_hip_store* s, const uint32_t* ids, size_t m, void* out32);
+/* The preimages of a MultiFrame's hash slots straight from the resident digests: element j of d_out is the element d_elems[j]
+ * describes, canonical or - as_mont - Montgomery (one product per element).  allocate_slot (/root/reference/src/lem/circuit.rs:249-315)
+ * builds a slot's preimage from its SlotData, value by value (:265-292):
+ *   Val::Pointer(ptr)    ->  TAG(id), DIGEST(id)      (store.hash_ptr(ptr): its tag, then its hash, :270-277)
+ *   Val::Num(ptr_val)    ->  DIGEST(id)               (store.hash_ptr_val(ptr_val).0: id names the node of that value, :278-284)
+ *   Val::Boolean(b)      ->  CONST(b)                 (ONE or ZERO, :285-291)
+ *   an absent slot       ->  ZERO x arity             (the dummy preimage, :300-308)
+ * With the descriptors of num_frames x count slots of one type in frame-major order, d_out (n_elems x 32 B) is what
+ * lurk_hip_frames_witness_dev and lurk_hip_slot_witness_dev read as their d_preimages: n x arity x 32 B.  A TAG or DIGEST whose id is
+ * >= n_nodes reads nothing and gives ZERO, and so does an unknown kind.  n_elems < 2^31.  Stream-ordered, does not synchronise. */
+#define LURK_SLOT_ELEM_ZERO 0
+#define LURK_SLOT_ELEM_TAG 1    /* arg = node id: that node's tag */
+#define LURK_SLOT_ELEM_DIGEST 2 /* arg = node id: that node's digest */
+#define LURK_SLOT_ELEM_CONST 3  /* arg itself: booleans, literal tags */
+typedef struct {
+    uint32_t kind; /* LURK_SLOT_ELEM_* */
+    uint32_t arg;
+} lurk_hip_slot_elem;
+int lurk_hip_store_slot_preimages_dev(const lurk_hip_store* s, const lurk_hip_slot_elem* d_elems, size_t n_elems, int as_mont, void* d_out, void* stream);
+
 /* ---- slot witnesses: the Poseidon / bit-decomposition part of the witness vector, produced on the device ------------
  * Replaces generate_slots_witnesses (/root/reference/src/lem/multiframe.rs:520-592), which runs allocate_slot
  * (/root/reference/src/lem/circuit.rs:242-315) on a WitnessCS per slot: neptune's circuit2::poseidon_hash_allocated for

@@ -42,6 +42,11 @@ class CkParamsStruct(ctypes.Structure):
                 ("suite", ctypes.c_char * 32)]
 
 
+class SlotElemStruct(ctypes.Structure):
+    """lurk_hip_slot_elem: one element of a slot preimage by description (kind = LURK_SLOT_ELEM_*, arg = a node id or the constant)"""
+    _fields_ = [("kind", ctypes.c_uint32), ("arg", ctypes.c_uint32)]
+
+
 # every symbol include/lurk_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "lurk_hip_device_count": (c_int, []),
@@ -121,6 +126,13 @@ SIGNATURES = {
     "lurk_hip_trie_verify_insert_dev": (c_int, [c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
                                                 ctypes.POINTER(c_u64), c_void_p]),
     "lurk_hip_store_hydrate": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_size_t)]),
+    "lurk_hip_store_create": (c_int, [ctypes.POINTER(c_void_p), c_int, c_size_t]),
+    "lurk_hip_store_destroy": (c_int, [c_void_p]),
+    "lurk_hip_store_info": (c_int, [c_void_p, ctypes.POINTER(c_int)] + [ctypes.POINTER(c_size_t)] * 4 + [ctypes.POINTER(c_int)]),
+    "lurk_hip_store_append": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_void_p]),
+    "lurk_hip_store_digests_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lurk_hip_store_digests": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "lurk_hip_store_slot_preimages_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]),
     "lurk_hip_slot_witness_size": (c_int, [c_int, c_int, ctypes.POINTER(c_size_t)]),
     "lurk_hip_slot_witness_dev": (c_int, [c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     "lurk_hip_slot_witness": (c_int, [c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),

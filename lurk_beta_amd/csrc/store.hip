@@ -26,6 +26,7 @@
 #include "dispatch.hpp"
 #include "field.cuh"
 #include "host_poseidon.hpp"
+#include "store_layout.hpp"  // STORE_HOST_MAX, kind_arity, kind_children
 
 namespace lurk {
 
@@ -71,9 +72,6 @@ __global__ __launch_bounds__(256) void store_gather_kernel(const NodeDev* __rest
     pre[2 * (size_t)t + 1] = hi;
 }
 
-// groups of at most this many nodes are hashed on the host: device level time / host hash time = 0.138 ms / ~20 us
-constexpr uint32_t STORE_HOST_MAX = 6;
-
 // host twin of store_gather_kernel + one hash: node k of the (level, arity)-ordered list from the host copy of the digest array
 static void store_hash_node_host(int field_id, const NodeDev& nd, const uint64_t* dig, uint64_t* out4) {
     uint64_t pre[8 * 4] = {0};
@@ -101,27 +99,6 @@ static void store_hash_node_host(int field_id, const NodeDev& nd, const uint64_t
             break;
     }
     with_field(field_id, [&](auto F) { poseidon_hash_host<decltype(F)>(poseidon_host<decltype(F)>((int)nd.arity), pre, out4); });
-}
-
-static int kind_arity(uint32_t kind) {
-    switch (kind) {
-        case LURK_NODE_TUPLE2: return 4;
-        case LURK_NODE_TUPLE3: return 6;
-        case LURK_NODE_TUPLE4: return 8;
-        case LURK_NODE_COMPACT: return 4;
-        case LURK_NODE_COMM: return 3;
-        default: return 0;
-    }
-}
-static int kind_children(uint32_t kind) {
-    switch (kind) {
-        case LURK_NODE_TUPLE2: return 2;
-        case LURK_NODE_TUPLE3: return 3;
-        case LURK_NODE_TUPLE4: return 4;
-        case LURK_NODE_COMPACT: return 3;
-        case LURK_NODE_COMM: return 1;
-        default: return 0;
-    }
 }
 
 }  // namespace lurk
