@@ -71,7 +71,8 @@ const char* lurk_hip_version(void);
 /* The ABI revision this header describes; lurk_hip_abi_version() is what the loaded library was built from (a binding compares the
  * two at start-up).  A revision that only adds entry points raises the number too: a binding built against revision n runs on any library
  * that reports >= n until a revision says otherwise.  4: the verifiers - lurk_hip_r1cs_sparse_mle_dev, lurk_hip_ipa_s_vector_dev,
- * lurk_hip_sumcheck_verify, lurk_hip_ipa_verify_dev, lurk_hip_spartan_verify_dev, lurk_hip_spartan_verify_batch_dev (additions only).
+ * lurk_hip_sumcheck_verify, lurk_hip_ipa_verify_dev, lurk_hip_spartan_verify_dev, lurk_hip_spartan_verify_batch_dev (additions only);
+ * later additions under the same number (a binding probes for them by symbol): lurk_hip_r1cs_transpose_dev, lurk_hip_r1cs_read.
  * 3: lurk_hip_slot_constraints_size / lurk_hip_slot_constraints,
  * lurk_hip_frames_r1cs_create, lurk_hip_r1cs_is_sat_dev (additions only).  2 (round 6): lurk_hip_msm_ctx_info's *precomputed is a boolean (the key's form comes from lurk_hip_msm_ctx_form),
  * LURK_MSM_SLOTS is 6, LURK_MSM_SUBMIT_FOLLOW, the parameter blocks lurk_hip_ro_params / lurk_hip_ck_params, lurk_hip_scratch_trim.
@@ -599,6 +600,31 @@ int lurk_hip_r1cs_dims(const lurk_hip_r1cs* shape, int* field_id, size_t* num_co
 int lurk_hip_r1cs_info(const lurk_hip_r1cs* shape, size_t* nnz_a, size_t* nnz_b, size_t* nnz_c,
                        size_t* distinct_coefficients);
 int lurk_hip_r1cs_device(const lurk_hip_r1cs* shape, int* device); /* the device the shape is resident on */
+/* The transpose of a resident shape, made on the device it is resident on: what lurk_hip_spartan_prove_dev / _prove_batch_dev and
+ * lurk_hip_spartan_kzg_prove_dev / _prove_batch_dev take as shape_t (rows_t = 2 * num_vars), without a host CSR - so a shape the
+ * library built itself (lurk_hip_frames_r1cs_create) can be compressed.  With ncols = num_vars + 1 + num_io of the source, *out is an
+ * ordinary lurk_hip_r1cs over the same field with num_cons' = rows_t (0 means ncols), num_vars' = num_cons - 1, num_io' = 0 - its z
+ * has exactly num_cons entries - and, for each of A, B, C, M'[j][i] = M[i][j]: row j lists its entries by ascending i, entries of
+ * equal (i, j) in their input order, rows j >= ncols are empty.  Read back (lurk_hip_r1cs_read) it is bit for bit what a stable sort of
+ * the host CSR by column followed by lurk_hip_r1cs_create gives, on every run: nothing depends on the order in which atomics land.
+ * The coefficient dictionary is the source's (one device-to-device copy), so lurk_hip_r1cs_info reports the source's nnz per matrix
+ * and distinct_coefficients; the rows the wave-per-row kernels take (more than 32 entries in A, B or C) are found again.  multiply_vec,
+ * is_sat, sparse_mle, the provers and lurk_hip_r1cs_destroy take the result as any shape.
+ * The work is ordered after `stream`, which the call synchronises ONCE, at its end (the host keeps the number of long rows): the
+ * result is complete when the call returns.  The source is only read: calls on one source from several threads are independent.
+ * Temporary memory comes from the stream's scratch arena (lurk_hip_scratch_trim releases it): 16 B per non-zero of the largest of the
+ * three matrices - twice that matrix's resident entry array - plus the sort's own storage (histograms and look-back state, a few per
+ * cent of the entry array) and 8 B per 256 rows of the result.
+ * Refused with LURK_HIP_ERR_INVALID_ARG before anything is allocated or launched, *out = NULL: a NULL shape or out, num_cons = 0,
+ * rows_t non-zero and below ncols, rows_t >= 2^32, a source that is not resident on the calling thread's current device.  An
+ * allocation that fails returns LURK_HIP_ERR_OOM and leaves nothing behind. */
+int lurk_hip_r1cs_transpose_dev(const lurk_hip_r1cs* shape, size_t rows_t, lurk_hip_r1cs** out, void* stream);
+/* Matrix `which` (0 = A, 1 = B, 2 = C) of a resident shape as the CSR lurk_hip_r1cs_create takes: indptr num_cons + 1 entries, indices
+ * and data32_mont nnz entries (sizes from lurk_hip_r1cs_dims / lurk_hip_r1cs_info), data 32 B Montgomery.  data32_mont may be NULL to
+ * read the structure only; indices and data32_mont may both be NULL when nnz = 0.  A host call: it synchronises the device.  The shape
+ * must be resident on the calling thread's current device; an unknown `which` is refused by name.  For cross-checking a host's own
+ * shape against one the library built (lurk_hip_frames_r1cs_create) or transposed. */
+int lurk_hip_r1cs_read(const lurk_hip_r1cs* shape, int which, uint64_t* indptr, uint64_t* indices, void* data32_mont);
 /* R1CSShape::multiply_vec: (A z, B z, C z); d_z has num_vars + 1 + num_io elements, outputs num_cons */
 int lurk_hip_r1cs_multiply_vec_dev(const lurk_hip_r1cs* shape, const void* d_z, void* d_az, void* d_bz,
                                    void* d_cz, void* stream);

@@ -148,6 +148,8 @@ SIGNATURES = {
     "lurk_hip_r1cs_dims": (c_int, [c_void_p, ctypes.POINTER(c_int)] + [ctypes.POINTER(c_size_t)] * 3),
     "lurk_hip_r1cs_info": (c_int, [c_void_p] + [ctypes.POINTER(c_size_t)] * 4),
     "lurk_hip_r1cs_device": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "lurk_hip_r1cs_transpose_dev": (c_int, [c_void_p, c_size_t, ctypes.POINTER(c_void_p), c_void_p]),
+    "lurk_hip_r1cs_read": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "lurk_hip_r1cs_multiply_vec_dev": (c_int, [c_void_p] * 6),
     "lurk_hip_r1cs_cross_term_dev": (c_int, [c_void_p] * 5),
     "lurk_hip_r1cs_cross_term_cached_dev": (c_int, [c_void_p] * 15),

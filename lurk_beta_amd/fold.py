@@ -100,6 +100,28 @@ class R1CSShape:
         _lib.check(_lib.load().lurk_hip_r1cs_info(self._h, *[ctypes.byref(x) for x in v]))
         return {"nnz": (v[0].value, v[1].value, v[2].value), "distinct_coefficients": v[3].value}
 
+    def read(self, which: int):
+        """Matrix ``which`` (0 = A, 1 = B, 2 = C) back on the host as the CSR the constructor takes: (indptr, indices, data[(nnz, 4) u64
+        Montgomery]) - ``lurk_hip_r1cs_read``.  Synchronises the device."""
+        which = int(which)
+        nnz = self.info()["nnz"][which] if 0 <= which <= 2 else 0
+        indptr = np.zeros(self.num_cons + 1, dtype=np.uint64)
+        indices = np.zeros(nnz, dtype=np.uint64)
+        data = np.zeros((nnz, 4), dtype=np.uint64)
+        _lib.check(_lib.load().lurk_hip_r1cs_read(self._h, which, _lib.ptr(indptr), _lib.ptr(indices) if nnz else None, _lib.ptr(data) if nnz else None))
+        return indptr, indices, data
+
+    def transposed(self, rows: int = 0, stream=None) -> "R1CSShape":
+        """The transpose as a resident shape of ``rows`` rows (0: num_vars + 1 + num_io) over num_cons columns, made on the device from
+        this shape's resident matrices and sharing their coefficients - ``lurk_hip_r1cs_transpose_dev``.  The compressing provers take
+        ``transposed(2 * num_vars)`` as their shape_t.  Synchronises the stream once."""
+        import torch
+
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().lurk_hip_r1cs_transpose_dev(self._h, int(rows), ctypes.byref(h), _lib.ptr(s)))
+        return R1CSShape._wrap(h)
+
     def multiply_vec(self, d_z, stream=None):
         """(A z, B z, C z) - R1CSShape::multiply_vec."""
         import torch

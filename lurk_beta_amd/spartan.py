@@ -98,6 +98,22 @@ class SpartanProver:
         self.R = (1 << 256) % order
         self.Rinv = pow(self.R, order - 2, order)
 
+    @classmethod
+    def from_shape(cls, curve: int, order: int, shape: R1CSShape, num_cons: int, num_vars: int, num_io: int) -> "SpartanProver":
+        """The prover of a shape that is resident already (one the library built, ``R1CSShape.for_frames``, or any other): its transpose
+        is made on the device (``R1CSShape.transposed``), no host CSR is needed.  The prover owns ``shape`` from here on (``close``)."""
+        require_pasta_curve(curve, "the compressing SNARK")
+        self = cls.__new__(cls)
+        self.curve, self.q, self.num_cons, self.num_vars, self.num_io = curve, order, num_cons, num_vars, num_io
+        self.sf = 1 if curve == 0 else 0
+        assert num_cons & (num_cons - 1) == 0 and num_vars & (num_vars - 1) == 0 and 1 + num_io <= num_vars
+        assert (shape.field_id, shape.num_cons, shape.num_vars, shape.num_io) == (self.sf, num_cons, num_vars, num_io)
+        self.shape = shape
+        self.shape_t = shape.transposed(2 * num_vars)
+        self.R = (1 << 256) % order
+        self.Rinv = pow(self.R, order - 2, order)
+        return self
+
     def _mont(self, vals) -> np.ndarray:
         return sumcheck._limbs([int(v) * self.R % self.q for v in vals])
 

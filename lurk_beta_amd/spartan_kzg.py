@@ -84,6 +84,21 @@ class SpartanKzgProver:
         self.shape = R1CSShape(field_id, num_cons, num_vars, num_io, *mats)
         self.shape_t = R1CSShape(field_id, 2 * num_vars, num_cons - 1, 0, *[transpose_csr(*m, 2 * num_vars) for m in mats])
 
+    @classmethod
+    def from_shape(cls, curve: int, order: int, shape: R1CSShape, num_cons: int, num_vars: int, num_io: int) -> "SpartanKzgProver":
+        """The prover of a shape that is resident already: its transpose is made on the device (``R1CSShape.transposed``), no host CSR
+        is needed.  Same arguments as ``SpartanProver.from_shape``; curve and order are BN254's.  The prover owns ``shape`` from here on
+        (``close``)."""
+        if (curve, order) != (CURVE_BN254, BN254_R):
+            raise ValueError("the HyperKZG-opened prover runs on BN254 G1 only")
+        self = cls.__new__(cls)
+        self.curve, self.q, self.sf = CURVE_BN254, BN254_R, shape.field_id
+        self.num_cons, self.num_vars, self.num_io = num_cons, num_vars, num_io
+        assert (shape.num_cons, shape.num_vars, shape.num_io) == (num_cons, num_vars, num_io)
+        self.shape = shape
+        self.shape_t = shape.transposed(2 * num_vars)
+        return self
+
     def prove(self, X, u: int, d_W, d_E, comm_W_jac, comm_E_jac, key, label: bytes = LABEL, stream=None) -> dict:
         """d_W (num_vars, 4), d_E (num_cons, 4): Montgomery device tensors (not modified); the commitments as 96-byte Jacobians; key: the
         resident BN254 ``CommitmentKey`` (powers of tau) that committed W and E, >= max(num_cons, num_vars) points."""

@@ -232,11 +232,39 @@ impl R1csShape {
         check(lurk_hip_r1cs_is_sat_dev(self.0, d_z, d_e, &mut n, &mut first, stream))?;
         Ok((n, first))
     }
+    /// The transpose as a resident shape of `rows_t` rows (0: `num_vars + 1 + num_io`) over `num_cons` columns, made on the device from this
+    /// shape's resident matrices and sharing their coefficients (`lurk_hip_r1cs_transpose_dev`): the compressing provers take
+    /// `transposed(2 * num_vars, stream)` as their `shape_t`, so no host CSR of the transpose is needed.  Synchronises `stream` once.
+    /// # Safety
+    /// `stream`: a stream of the device the shape is resident on (the calling thread's current device), or null.
+    pub unsafe fn transposed(&self, rows_t: usize, stream: *mut c_void) -> Result<Self, Error> {
+        let mut p = core::ptr::null_mut();
+        check(lurk_hip_r1cs_transpose_dev(self.0, rows_t, &mut p, stream))?;
+        Ok(Self(p))
+    }
+    /// (num_cons, num_vars, num_io)
+    pub fn dims(&self) -> Result<(usize, usize, usize), Error> {
+        let (mut f, mut c, mut v, mut io) = (0, 0usize, 0usize, 0usize);
+        check(unsafe { lurk_hip_r1cs_dims(self.0, &mut f, &mut c, &mut v, &mut io) })?;
+        Ok((c, v, io))
+    }
+    /// Matrix `which` (0 = A, 1 = B, 2 = C) back on the host as the CSR `new` takes (`lurk_hip_r1cs_read`): for cross-checking a host's own
+    /// shape against one the library built (`for_frames`) or transposed.  Synchronises the device.
+    pub fn read(&self, which: c_int) -> Result<SlotMatrix, Error> {
+        let (rows, _, _) = self.dims()?;
+        let mut nnz = [0usize; 3];
+        let [na, nb, nc] = &mut nnz;
+        check(unsafe { lurk_hip_r1cs_info(self.0, na, nb, nc, core::ptr::null_mut()) })?;
+        let n = if (0..3).contains(&which) { nnz[which as usize] } else { 0 };
+        let mut m = SlotMatrix { indptr: vec![0; rows + 1], indices: vec![0; n], data: vec![0; n * 32] };
+        check(unsafe { lurk_hip_r1cs_read(self.0, which, m.indptr.as_mut_ptr(), m.indices.as_mut_ptr(), m.data.as_mut_ptr().cast()) })?;
+        Ok(m)
+    }
     pub fn as_ptr(&self) -> *mut lurk_hip_r1cs {
         self.0
     }
 }
-/// One sparse matrix of a slot's rows, owned (`lurk_hip_slot_constraints`).
+/// One sparse matrix, owned: of a slot's rows (`lurk_hip_slot_constraints`) or of a resident shape read back (`R1csShape::read`).
 pub struct SlotMatrix {
     pub indptr: Vec<u64>,
     pub indices: Vec<u64>,
