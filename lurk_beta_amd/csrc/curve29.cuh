@@ -1,7 +1,8 @@
 // curve29.cuh - XYZZ mixed addition on the radix-2^29 layer (field29.cuh): the inner loop of the MSM
 // bucket accumulation.  Same group law and same exceptional cases as curve.cuh::xyzz_madd; only the
-// representation of the accumulator differs.  Results leave through xyzz29_to_xyzz as ordinary
-// Montgomery(2^256) XYZZ points, bit-compatible with the rest of the pipeline.
+// representation of the accumulator differs.  Inside the MSM pipeline results stay on this layer (Plane29
+// records, below) until the last level of the bucket reduction; xyzz29_to_xyzz turns one into an ordinary
+// Montgomery(2^256) XYZZ point, bit-compatible with everything outside it.
 //
 // Bound discipline (checked by tests/host_harness with LURK_F29_CHECK): the accumulator coordinates are
 // "R-bounded" at every loop boundary: tight limbs (< 2^29, top limb < 2^27) and value < 2^259.
@@ -362,6 +363,94 @@ LURK_HD Xyzz<P> xyzz_sum_via29(const Xyzz<P>* pts, uint32_t nt) {
     return xyzz29_to_xyzz<P>(acc, acc_id);
 }
 
+// The record the MSM's stages hand each other (msm_core.cuh): a point on this layer with the identity as a flag, 160 bytes.  Task sums,
+// buckets and the planes of the bucket reduction all travel in this form, so nothing between the accumulation and the last reduction
+// level converts a point to the 8 x 32 form and back.
+// A STORED record is R-bounded - tight limbs (< 2^29, top limb < 2^27: value < 2^259) - which is what xyzz29_add asks of its inputs:
+// the copy of a first base, the outputs of xyzz29_madd / xyzz29_add and of the two doublings all are (see each).  plane_store asserts
+// it under LURK_F29_CHECK; the limbs of an identity record are never read.
+template <class P>
+struct Plane29 {
+    Xyzz29<P> p;
+    uint32_t id, pad[3];
+};
+template <class P>
+LURK_HD void plane_load(const Plane29<P>* __restrict__ src, Xyzz29<P>& v, bool& id) {
+    const Plane29<P> r = *src;
+    v = r.p;
+    id = r.id != 0;
+}
+template <class P>
+LURK_HD void plane_store(Plane29<P>* __restrict__ dst, const Xyzz29<P>& v, bool id) {
+    if (!id) {
+        F29_ASSERT_LIMBS(v.x, 29, "record x"); F29_ASSERT_TOP(v.x, 27, "record x");
+        F29_ASSERT_LIMBS(v.y, 29, "record y"); F29_ASSERT_TOP(v.y, 27, "record y");
+        F29_ASSERT_LIMBS(v.zz, 29, "record zz"); F29_ASSERT_TOP(v.zz, 27, "record zz");
+        F29_ASSERT_LIMBS(v.zzz, 29, "record zzz"); F29_ASSERT_TOP(v.zzz, 27, "record zzz");
+    }
+    Plane29<P> o;
+    o.p = v;
+    o.id = id;
+    o.pad[0] = o.pad[1] = o.pad[2] = 0;
+    *dst = o;
+}
+template <class P>
+LURK_HD void plane_store_identity(Plane29<P>* __restrict__ dst) {
+    Xyzz29<P> z;
+    z.x = z.y = z.zz = z.zzz = f29_zero<P>();
+    plane_store<P>(dst, z, true);
+}
+// Sum of nt >= 1 records (the task sums of one bucket: msm_finalize.hip), a chain of general additions on this layer.
+template <class P>
+LURK_HD void plane_sum(const Plane29<P>* recs, uint32_t nt, Xyzz29<P>& acc, bool& acc_id) {
+    plane_load<P>(recs, acc, acc_id);
+    for (uint32_t i = 1; i < nt; i++) {
+        Xyzz29<P> q;
+        bool q_id;
+        plane_load<P>(recs + i, q, q_id);
+        xyzz29_add<P>(acc, acc_id, q, q_id);
+    }
+}
+
+// The finalize stage's work for ONE bucket of the record array `records` (NB buckets in front, task t's sum at NB + t when its bucket is
+// two or more tasks): `nt` tasks, the first of them task `first`.  Returns true when the bucket has more than `fin_small` tasks and is
+// left to a workgroup (msm_finalize.hip); tests/host_bucket_records replays this on the CPU.
+template <class P>
+LURK_HD bool plane_finalize_bucket(Plane29<P>* records, uint32_t NB, size_t key, uint32_t nt, uint32_t first, uint32_t fin_small) {
+    if (nt == 1) return false;  // the bucket IS its task's sum, stored in place by the accumulation
+    if (nt == 0) {
+        plane_store_identity<P>(records + key);
+        return false;
+    }
+    if (nt > fin_small) return true;
+    Xyzz29<P> acc;
+    bool acc_id;
+    plane_sum<P>(records + NB + first, nt, acc, acc_id);  // (reads slots behind the buckets, writes one among them)
+    plane_store<P>(records + key, acc, acc_id);
+    return false;
+}
+
+#if defined(__HIPCC__)
+// acc <- the sum of the BLOCK accumulators of a workgroup (thread 0 holds it afterwards): a tree through LDS on 160-byte records
+// (sh: BLOCK of them).  The hot buckets of msm_finalize.hip and msm_bucket_direct.hip.
+template <class P, int BLOCK>
+__device__ __forceinline__ void block_tree_sum29(Xyzz29<P>& acc, bool& acc_id, Plane29<P>* sh) {
+    const int t = threadIdx.x;
+    plane_store<P>(sh + t, acc, acc_id);
+    __syncthreads();
+    for (int stride = BLOCK / 2; stride >= 1; stride >>= 1) {
+        if (t < stride) {
+            Xyzz29<P> q;
+            bool q_id;
+            plane_load<P>(sh + t + stride, q, q_id);
+            xyzz29_add<P>(acc, acc_id, q, q_id);
+            plane_store<P>(sh + t, acc, acc_id);
+        }
+        __syncthreads();
+    }
+}
+#endif
+
 // A 64-byte table record in flight: four 16-byte words exactly as the loads return them (one global_load_dwordx4 each).  The
 // pipelined task loop holds the NEXT record in this form across a whole mixed addition and turns it into an Affine<P> only when its
 // turn comes: held as an Affine<P> the persistent kernel takes 194 registers, in this form it stays inside its budget of 192.
@@ -405,7 +494,8 @@ LURK_HD Affine<P> msm_task_next29(const uint32_t* sorted, const Affine<P>* table
 }
 
 // One accumulation task on the radix-2^29 layer: the signed table records sorted[first .. last) summed into (acc, acc_id), which
-// leave R-bounded (msm_task_accumulate29 returns them as an ordinary XYZZ point; msm_bucket_direct.hip keeps them on this layer).
+// leave R-bounded (both accumulate kernels and msm_bucket_direct.hip store them as Plane29 records; msm_task_accumulate29 returns them
+// as an ordinary XYZZ point for the host harnesses).
 // PIPELINED (the persistent kernel only): the same additions with the same arguments in the same order, the gather of record j + 1
 // and the load of index j + 2 issued in front of addition j, so that the only exposed gather of a task is its first.
 template <class P, bool PIPELINED = false>

@@ -13,8 +13,10 @@
 //   scalars         32 B x n, read by both sweeps of sort pass 1  caller's
 //   inter           8 B x W x n  (low key bits, entry)           between the two sort passes
 //   sorted          4 B x W x n  (table index | sign)
-//   partials        128 B x (NB + W*n/S)                         XYZZ task sums
-//   buckets, planes 128 B x NB (x3)
+//   task_dest       4 B x (NB + W*n/S)                           where each task's sum goes in `records`
+//   records         160 B x (2 NB + W*n/S)                       radix-2^29 records (curve29.cuh: Plane29): the NB buckets, behind them the
+//                                                                sums of the tasks of buckets that are two or more tasks
+//   planes          160 B x NB (x2)                              the bucket reduction's levels, the same records
 // Algorithmic HBM bytes per call: 96 B per point (32 B scalar + 64 B base) - the dominant kernel is
 // bound by the integer VALU (v_mad_u64_u32 issue), not by HBM.
 #include "common.hpp"
@@ -46,7 +48,8 @@ struct MsmCtx : MsmCtxBase {
     struct Work {
         std::mutex mu;
         DevBuf inter, sorted, block_hist, part_cnt, part_start, cnt, bucket_start, task_start, group_tasks, group_task_base, task_info,
-            task_order, len_hist, partials, buckets, big_list, big_count, planes_a, planes_b, canon, small_counter;
+            task_dest,
+            task_order, len_hist, records, partials /* (the small form's group points) */, big_list, big_count, planes_a, planes_b, canon, small_counter;
         Xyzz<P>* host_pts = nullptr;  // pinned: window sums or bit planes for the host tail
         size_t ws_n = 0, ws_entries = 0, ws_nt = 0;  // what the workspaces hold room for: scalars (0 = nothing yet), sorted entries, tasks,
         uint32_t ws_NB = 0;                          // keys
@@ -79,15 +82,15 @@ struct MsmCtx : MsmCtxBase {
         const Work& wk;
         static uint32_t* u32(const DevBuf& b) { return (uint32_t*)b.p; }
         uint32_t *sorted = u32(wk.sorted), *cnt = u32(wk.cnt), *bucket_start = u32(wk.bucket_start), *task_start = u32(wk.task_start),
-                 *group_tasks = u32(wk.group_tasks), *group_task_base = u32(wk.group_task_base), *task_order = u32(wk.task_order),
+                 *group_tasks = u32(wk.group_tasks), *group_task_base = u32(wk.group_task_base), *task_dest = u32(wk.task_dest), *task_order = u32(wk.task_order),
                  *len_hist = u32(wk.len_hist), *big_list = u32(wk.big_list), *big_count = u32(wk.big_count), *cursor = u32(wk.cursor);
         uint2* task_info = (uint2*)wk.task_info.p;
-        Xyzz<P>*partials = (Xyzz<P>*)wk.partials.p, *buckets = (Xyzz<P>*)wk.buckets.p;
+        Plane29<P>* records = (Plane29<P>*)wk.records.p;  // buckets at [0, NB), task sums behind (msm_stages.hpp)
         void *planes_a = wk.planes_a.p, *planes_b = wk.planes_b.p;
         // (the small counters of the later stages are cleared by the sort's single-block launch)
         MsmSortBufs sort_bufs() const {
             return MsmSortBufs{wk.inter.p, sorted, u32(wk.block_hist), u32(wk.part_cnt), u32(wk.part_start), cnt, bucket_start, wk.canon.p,
-                               {big_count, len_hist, cursor}, {1, 2 * (MSM_S + 1), MSM_PLACEMENT_BASE + 512}};
+                               {big_count, len_hist, cursor}, {1, 2 * (MSM_S_MAX + 1), MSM_PLACEMENT_BASE + 512}};
         }
     };
     Work work[MSM_SLOTS];
@@ -338,10 +341,12 @@ struct MsmCtx : MsmCtxBase {
         wk.group_tasks.ensure(64 * 4);
         wk.group_task_base.ensure(64 * 4);
         wk.task_info.ensure(nt * sizeof(uint2));
+        wk.task_dest.ensure(nt * 4);
         wk.task_order.ensure(nt * 4);
-        wk.len_hist.ensure(2 * (MSM_S + 1) * 4);
-        wk.partials.ensure(nt * sizeof(Xyzz<P>));
-        wk.buckets.ensure((size_t)sh.NB * sizeof(Xyzz<P>));
+        wk.len_hist.ensure(2 * (MSM_S_MAX + 1) * 4);
+        // (sized by the largest NB and the largest task count seen, which may come from different shapes: the early return above
+        // compares each on its own)
+        wk.records.ensure(((size_t)(sh.NB > wk.ws_NB ? sh.NB : wk.ws_NB) + (nt > wk.ws_nt ? nt : wk.ws_nt)) * MSM_RECORD_BYTES);
         wk.big_list.ensure((size_t)sh.NB * 4);
         wk.big_count.ensure(16);
         wk.cursor.ensure(4 * (MSM_PLACEMENT_BASE + 512));
@@ -385,6 +390,9 @@ struct MsmCtx : MsmCtxBase {
         // at the raised one (see submit_impl)
         const int low = L.plan.low_prio ? 1 : 0;
         sh.low_prio = low;
+        // a commitment large enough for full tasks that takes the one-wave persistent form on the accumulate stream - the form whose tail
+        // another resident accumulation fills - cuts its buckets into tasks of MsmTuning::persist_s entries (128; msm_launch_plan.hpp)
+        if (form == MsmAccForm::PERSISTENT_ACC_STREAM && sh.S == MSM_S) sh.S = msm_tuning().persist_s;
         ensure_workspace(wk, sh);
         if (is_mont) wk.canon.ensure(n * 32);
         const WorkView v{wk};
@@ -396,8 +404,8 @@ struct MsmCtx : MsmCtxBase {
         }
         if (!direct) {
             ProfScope ps("msm_tasks", s);
-            msm_launch_plan_tasks(v.cnt, v.bucket_start, v.task_start, v.group_tasks, v.group_task_base, sh.NG, v.task_info, v.len_hist, v.task_order, nt,
-                                  (uint32_t)sh.S, low, s);
+            msm_launch_plan_tasks(v.cnt, v.bucket_start, v.task_start, v.group_tasks, v.group_task_base, sh.NG, sh.NB, v.task_info, v.task_dest, v.len_hist,
+                                  v.task_order, nt, (uint32_t)sh.S, low, s);
         }
         if (L.before_accumulate) (*L.before_accumulate)();  // the one-shot entry point uploads the bases here, behind the sort
         if (wk.planned) LURK_HIP_CHECK(hipEventRecord(wk.planned, s));  // sort and plan are enqueued: a background commitment may start behind this point
@@ -407,7 +415,7 @@ struct MsmCtx : MsmCtxBase {
         switch (form) {
         case MsmAccForm::DIRECT: {
             ProfScope ps("msm_accumulate_direct", s);
-            msm_launch_bucket_direct<P>(v.sorted, table, v.bucket_start, v.cnt, sh.NB, (size_t)sh.W * sh.n, v.buckets, v.big_list, v.big_count, s);
+            msm_launch_bucket_direct<P>(v.sorted, table, v.bucket_start, v.cnt, sh.NB, (size_t)sh.W * sh.n, v.records, v.big_list, v.big_count, s);
             break;
         }
         case MsmAccForm::PERSISTENT_SLOT_STREAM: {
@@ -417,7 +425,8 @@ struct MsmCtx : MsmCtxBase {
             wk.placement_valid = true;  // (the cursor block was zeroed by msm_part_start_kernel)
             {
                 ProfScope ps("msm_accumulate_persistent", s);
-                msm_launch_accumulate_persistent<P>(v.sorted, table, v.task_info, v.task_order, v.group_task_base, sh.NG, v.partials, v.cursor, s, L.plan.wgs_per_cu);
+                msm_launch_accumulate_persistent<P>(v.sorted, table, v.task_info, v.task_order, v.task_dest, v.group_task_base, sh.NG, v.records, v.cursor, s,
+                                                    L.plan.wgs_per_cu);
             }
             LURK_HIP_CHECK(hipEventRecord(wk.accumulated, s));
             break;
@@ -442,7 +451,8 @@ struct MsmCtx : MsmCtxBase {
             }
             {
                 ProfScope ps("msm_accumulate_persistent", L.acc_stream);  // (prefix "msm_accumulate" still matches both forms)
-                msm_launch_accumulate_persistent<P>(v.sorted, table, v.task_info, v.task_order, v.group_task_base, sh.NG, v.partials, v.cursor, L.acc_stream);
+                msm_launch_accumulate_persistent<P>(v.sorted, table, v.task_info, v.task_order, v.task_dest, v.group_task_base, sh.NG, v.records, v.cursor,
+                                                    L.acc_stream);
             }
             LURK_HIP_CHECK(hipEventRecord(wk.accumulated, L.acc_stream));
             LURK_HIP_CHECK(hipStreamWaitEvent(s, wk.accumulated, 0));
@@ -451,22 +461,22 @@ struct MsmCtx : MsmCtxBase {
         case MsmAccForm::PLAIN: {
             {
                 ProfScope ps("msm_accumulate", s);
-                msm_launch_accumulate<P>(v.sorted, table, v.task_info, v.task_order, v.group_task_base, sh.NG, v.partials, nt, s);
+                msm_launch_accumulate<P>(v.sorted, table, v.task_info, v.task_order, v.task_dest, v.group_task_base, sh.NG, v.records, nt, s);
             }
             if (wk.accumulated) LURK_HIP_CHECK(hipEventRecord(wk.accumulated, s));  // what a LURK_MSM_SUBMIT_FOLLOW commitment starts behind
             break;
         }
         }
-        if (!direct) {  // (the DIRECT launch left whole buckets)
+        if (!direct) {  // (the DIRECT launch left whole buckets; here the one-task buckets are whole already)
             ProfScope ps("msm_finalize", s);
-            msm_launch_finalize<P>(v.partials, v.cnt, v.task_start, v.group_task_base, sh.NB, v.buckets, v.big_list, v.big_count, (uint32_t)sh.S, s);
-            msm_launch_big_buckets<P>(v.partials, v.cnt, v.task_start, v.group_task_base, v.buckets, v.big_list, v.big_count, (uint32_t)sh.S, s);
+            msm_launch_finalize<P>(v.records, v.cnt, v.task_start, v.group_task_base, sh.NB, v.big_list, v.big_count, (uint32_t)sh.S, s);
+            msm_launch_big_buckets<P>(v.records, v.cnt, v.task_start, v.group_task_base, sh.NB, v.big_list, v.big_count, (uint32_t)sh.S, s);
         }
         {
             // the c - 1 levels of the bit-plane merge tree; the last one stores the G x c plane sums into the slot's pinned buffer: the
             // host's Horner over them (G c doublings and as many additions) is cheaper than a 20-deep dependent chain on one lane
             ProfScope ps("msm_reduce", s);
-            msm_launch_reduce<P>(v.buckets, v.planes_a, v.planes_b, sh.c, sh.G, sh.B, wk.host_pts, s);
+            msm_launch_reduce<P>(v.records, v.planes_a, v.planes_b, sh.c, sh.G, sh.B, wk.host_pts, s);
         }
         LURK_HIP_CHECK(hipGetLastError());
     }

@@ -2,9 +2,9 @@
 // LURK_MSM_SUBMIT_FOLLOW commitment), in its own translation unit so that it CAN be built for another register footprint than the
 // plain launch of msm_acc.hip (Makefile: PERSIST_FLAGS / PERSIST_DEFS).  The SHIPPED build sets neither.  The kernel runs the same
 // additions as the plain launch (msm_acc_task.cuh); launched with one wave per SIMD it runs them through the PIPELINED task loop of
-// curve29.cuh, which keeps the next table record (16 registers) and the index after it in flight under the current addition: 192 VGPRs
-// where the plain loop takes 176.  192 is the
-// budget, not an accident: what has to run beside resident accumulations is sized for it and checked on the compiler's own numbers
+// curve29.cuh, which keeps the next table record (16 registers) and the index after it in flight under the current addition: 173 VGPRs
+// where the plain loop takes 162 (Pasta).  192 is the
+// budget: what has to run beside resident accumulations is sized for it and checked on the compiler's own numbers
 // (tests/test_cabi_exports.py::test_sort_kernels_fit_beside_a_resident_accumulation, tests/test_acc_pipeline_resources.py): four waves
 // of a 1024-thread sort workgroup beside ONE 192-register wave (4 x 72 + 192 <= 512), a 128-register tail wave beside TWO
 // (128 + 2 x 192 = 512).  One granule more and the second launch waits for the tail kernels.  (A 144-register build of the plain loop -
@@ -40,17 +40,20 @@ template <class P, bool PIPELINED>
 #ifndef LURK_PERSIST_MIN_BLOCKS
 #define LURK_PERSIST_MIN_BLOCKS 1  // (HIP: minimum WAVES per SIMD) 4: the compiler holds the kernel to 128 registers (and spills the rest)
 #endif
-// The register budget is handed to the compiler as well (it binds only the pipelined instantiations).  Left alone it parks ~23 constants of the task epilogue (xyzz29_to_xyzz) in
-// VGPRs across the whole task loop and the BN254 instantiations come out at 194; told the limit it rematerialises two of them after
-// the loop instead (190, no scratch; the Pasta kernels are at 192 either way).  amdgpu_num_vgpr counts registers of the UNIFIED file
+// The register budget is handed to the compiler as well.  It bound the pipelined instantiations while a task ended in a conversion to
+// the 8 x 32 form (xyzz29_to_xyzz: ~23 constants parked in VGPRs across the whole task loop, 192 / 190 registers); now that a task
+// stores its sum as it stands - a Plane29 record, msm_acc_task.cuh - the kernels sit below it: 173 (Pasta) / 167 (BN254) pipelined,
+// 162 / 161 with the plain loop, scratch as before (192 bytes per lane on the Pasta fields, the frame of the out-of-line doubling; none
+// on the BN254 fields).  The limit stays as the statement of the budget.  amdgpu_num_vgpr counts registers of the UNIFIED file
 // of gfx90a and later in halves (the backend doubles the number: AMDGPUSubtarget::getMaxNumVGPRs), so 96 here is a limit of 192;
 // tests/test_acc_pipeline_resources.py fails if a compiler ever reads it another way (the kernel would spill).
 #define LURK_PERSIST_VGPR_BUDGET 192
 __global__ __launch_bounds__(MSM_ACC_BLOCK, LURK_PERSIST_MIN_BLOCKS) __attribute__((amdgpu_num_vgpr(LURK_PERSIST_VGPR_BUDGET / 2))) void msm_accumulate_persistent_kernel(const uint32_t* __restrict__ sorted, const Affine<P>* __restrict__ table,
                                                                                     const uint2* __restrict__ task_info,
                                                                                     const uint32_t* __restrict__ order,
+                                                                                    const uint32_t* __restrict__ task_dest,
                                                                                     const uint32_t* __restrict__ group_task_base, int NG,
-                                                                                    Xyzz<P>* __restrict__ partials, uint32_t* __restrict__ cursor) {
+                                                                                    Plane29<P>* __restrict__ records, uint32_t* __restrict__ cursor) {
     const uint32_t ntasks = group_task_base[NG];
     const uint32_t lane = threadIdx.x & 63u;
     if (threadIdx.x == 0) atomicAdd(&cursor[MSM_PLACEMENT_BASE + msm_cu_index()], 1u);  // diagnostic: workgroups per CU
@@ -59,14 +62,14 @@ __global__ __launch_bounds__(MSM_ACC_BLOCK, LURK_PERSIST_MIN_BLOCKS) __attribute
         if (lane == 0) base = atomicAdd(cursor, 64u);
         base = __builtin_amdgcn_readfirstlane(base);  // wave-uniform: the loop control stays scalar
         if (base >= ntasks) break;
-        if (base + lane < ntasks) msm_accumulate_task<P, PIPELINED>(base + lane, sorted, table, task_info, order, partials);
+        if (base + lane < ntasks) msm_accumulate_task<P, PIPELINED>(base + lane, sorted, table, task_info, order, task_dest, records);
     }
 }
 
 // one workgroup of 4 waves per CU (one wave per SIMD); cursor must be zero when the kernel starts
 template <class P>
-void msm_launch_accumulate_persistent(const uint32_t* sorted, const Affine<P>* table, const uint2* task_info, const uint32_t* order,
-                                      const uint32_t* group_task_base, int NG, Xyzz<P>* partials, uint32_t* cursor, hipStream_t s, unsigned wgs_per_cu) {
+void msm_launch_accumulate_persistent(const uint32_t* sorted, const Affine<P>* table, const uint2* task_info, const uint32_t* order, const uint32_t* task_dest,
+                                      const uint32_t* group_task_base, int NG, Plane29<P>* records, uint32_t* cursor, hipStream_t s, unsigned wgs_per_cu) {
     // LURK_MSM_PERSIST_WGS workgroups per CU (1: one wave per SIMD, the form two of which are resident at once; 2: two waves per SIMD - a
     // single accumulation at the multiplier's full rate, for LURK_MSM_MAX_ACC=1)
     static const unsigned wgs = [] { const char* e = getenv("LURK_MSM_PERSIST_WGS"); int v = e ? atoi(e) : 1; return (unsigned)(v < 1 ? 1 : v > 4 ? 4 : v); }();
@@ -74,14 +77,14 @@ void msm_launch_accumulate_persistent(const uint32_t* sorted, const Affine<P>* t
     const unsigned waves = wgs_per_cu ? wgs_per_cu : wgs;  // per SIMD
     if (waves == 1)
         hipLaunchKernelGGL((msm_accumulate_persistent_kernel<P, true>), dim3((unsigned)num_cus()), dim3(MSM_ACC_BLOCK), 0, s, sorted, table, task_info, order,
-                           group_task_base, NG, partials, cursor);
+                           task_dest, group_task_base, NG, records, cursor);
     else
         hipLaunchKernelGGL((msm_accumulate_persistent_kernel<P, false>), dim3((unsigned)num_cus() * waves), dim3(MSM_ACC_BLOCK), 0, s, sorted, table, task_info, order,
-                           group_task_base, NG, partials, cursor);
+                           task_dest, group_task_base, NG, records, cursor);
 }
 #define LURK_ACC_PERSISTENT_INSTANTIATE(P)                                                                                                    \
-    template void msm_launch_accumulate_persistent<P>(const uint32_t*, const Affine<P>*, const uint2*, const uint32_t*, const uint32_t*, int, \
-                                                      Xyzz<P>*, uint32_t*, hipStream_t, unsigned);
+    template void msm_launch_accumulate_persistent<P>(const uint32_t*, const Affine<P>*, const uint2*, const uint32_t*, const uint32_t*, const uint32_t*, int, \
+                                                      Plane29<P>*, uint32_t*, hipStream_t, unsigned);
 #ifdef LURK_MSM_BN254_TU  // msm_acc_persistent_bn254.hip
 LURK_ACC_PERSISTENT_INSTANTIATE(Bn254Fq)
 LURK_ACC_PERSISTENT_INSTANTIATE(Bn254Fr)

@@ -8,7 +8,7 @@
 //
 // Here L = 1, 2 or 4 adjacent lanes own one bucket: each sums a contiguous share of the bucket's sorted entries (mixed additions on
 // the radix-2^29 layer, msm_task_accumulate29_raw), the shares meet in log2 L xor-butterfly steps (xyzz29_add over __shfl_xor), lane 0
-// stores the bucket.  No task list, no partials, no order: cnt and bucket_start from the sort are all it reads.  A bucket with more
+// stores the bucket - as the Plane29 record the bucket reduction reads, like the planned-task stages (msm_stages.hpp).  No task list, no partials, no order: cnt and bucket_start from the sort are all it reads.  A bucket with more
 // than L x DIRECT_CAP entries (equal scalars: a whole window in one bucket) goes on the big list and is summed by a workgroup.
 #include "common.hpp"
 #include "msm_core.cuh"
@@ -23,7 +23,7 @@ constexpr uint32_t DIRECT_CAP = 64;  // entries per lane above which a bucket is
 template <class P, int L>
 __global__ __launch_bounds__(DIRECT_BLOCK) void msm_bucket_direct_kernel(const uint32_t* __restrict__ sorted, const Affine<P>* __restrict__ table,
                                                                            const uint32_t* __restrict__ bucket_start, const uint32_t* __restrict__ cnt,
-                                                                           uint32_t NB, Xyzz<P>* __restrict__ buckets, uint32_t* __restrict__ big_list,
+                                                                           uint32_t NB, Plane29<P>* __restrict__ buckets, uint32_t* __restrict__ big_list,
                                                                            uint32_t* __restrict__ big_count) {
     __builtin_amdgcn_s_setprio(1);
     const size_t lane = (size_t)blockIdx.x * DIRECT_BLOCK + threadIdx.x;
@@ -63,40 +63,30 @@ __global__ __launch_bounds__(DIRECT_BLOCK) void msm_bucket_direct_kernel(const u
         o_id = __shfl_xor((int)acc_id, off) != 0;
         xyzz29_add<P>(acc, acc_id, o, o_id);
     }
-    if (live && !big && sub == 0) buckets[key] = xyzz29_to_xyzz<P>(acc, acc_id);
+    if (live && !big && sub == 0) plane_store<P>(buckets + key, acc, acc_id);  // (an empty bucket: the identity record)
 }
 
-// the listed buckets, one workgroup each: lanes stride the bucket's entries, then an LDS tree
+// the listed buckets, one workgroup each: lanes stride the bucket's entries, then a tree through LDS on the same layer
 template <class P>
 __global__ __launch_bounds__(DIRECT_BLOCK) void msm_bucket_direct_big_kernel(const uint32_t* __restrict__ sorted, const Affine<P>* __restrict__ table,
                                                                                const uint32_t* __restrict__ bucket_start, const uint32_t* __restrict__ cnt,
-                                                                               Xyzz<P>* __restrict__ buckets, const uint32_t* __restrict__ big_list,
+                                                                               Plane29<P>* __restrict__ buckets, const uint32_t* __restrict__ big_list,
                                                                                const uint32_t* __restrict__ big_count) {
     __builtin_amdgcn_s_setprio(1);
     extern __shared__ uint4 lds_raw[];
-    Xyzz<P>* sh = reinterpret_cast<Xyzz<P>*>(lds_raw);
+    Plane29<P>* sh = reinterpret_cast<Plane29<P>*>(lds_raw);
     const uint32_t nbig = *big_count;
     for (uint32_t i = blockIdx.x; i < nbig; i += gridDim.x) {
         const uint32_t key = big_list[i], n = cnt[key], start = bucket_start[key];
-        Xyzz29<P> a29;
-        a29.x = a29.y = a29.zz = a29.zzz = f29_zero<P>();
-        bool a_id = true;
+        Xyzz29<P> acc;
+        acc.x = acc.y = acc.zz = acc.zzz = f29_zero<P>();
+        bool acc_id = true;
         for (uint32_t j = threadIdx.x; j < n; j += DIRECT_BLOCK) {
             const uint32_t e = sorted[start + j];
-            xyzz29_madd<P>(a29, a_id, table[e & 0x7fffffffu], (e & 0x80000000u) != 0);
+            xyzz29_madd<P>(acc, acc_id, table[e & 0x7fffffffu], (e & 0x80000000u) != 0);
         }
-        Xyzz<P> acc = xyzz29_to_xyzz<P>(a29, a_id);
-        const int t = threadIdx.x;
-        sh[t] = acc;
-        __syncthreads();
-        for (int stride = DIRECT_BLOCK / 2; stride >= 1; stride >>= 1) {
-            if (t < stride) {
-                xyzz_add<P>(acc, sh[t + stride]);
-                sh[t] = acc;
-            }
-            __syncthreads();
-        }
-        if (t == 0) buckets[key] = acc;
+        block_tree_sum29<P, DIRECT_BLOCK>(acc, acc_id, sh);
+        if (threadIdx.x == 0) plane_store<P>(buckets + key, acc, acc_id);
         __syncthreads();
     }
 }
@@ -113,17 +103,17 @@ int msm_bucket_direct_lanes(size_t NB, size_t entries) {
 
 template <class P>
 void msm_launch_bucket_direct(const uint32_t* sorted, const Affine<P>* table, const uint32_t* bucket_start, const uint32_t* cnt, uint32_t NB, size_t entries,
-                              Xyzz<P>* buckets, uint32_t* big_list, uint32_t* big_count, hipStream_t s) {
+                              Plane29<P>* buckets, uint32_t* big_list, uint32_t* big_count, hipStream_t s) {
     const int L = msm_bucket_direct_lanes(NB, entries);
     const dim3 grid((unsigned)div_up((size_t)NB * L, DIRECT_BLOCK)), block(DIRECT_BLOCK);
     if (L == 1) hipLaunchKernelGGL((msm_bucket_direct_kernel<P, 1>), grid, block, 0, s, sorted, table, bucket_start, cnt, NB, buckets, big_list, big_count);
     else if (L == 2) hipLaunchKernelGGL((msm_bucket_direct_kernel<P, 2>), grid, block, 0, s, sorted, table, bucket_start, cnt, NB, buckets, big_list, big_count);
     else hipLaunchKernelGGL((msm_bucket_direct_kernel<P, 4>), grid, block, 0, s, sorted, table, bucket_start, cnt, NB, buckets, big_list, big_count);
-    hipLaunchKernelGGL((msm_bucket_direct_big_kernel<P>), dim3(128), block, DIRECT_BLOCK * sizeof(Xyzz<P>), s, sorted, table, bucket_start, cnt, buckets, big_list,
+    hipLaunchKernelGGL((msm_bucket_direct_big_kernel<P>), dim3(128), block, DIRECT_BLOCK * sizeof(Plane29<P>), s, sorted, table, bucket_start, cnt, buckets, big_list,
                        big_count);
 }
 #define LURK_DIRECT_INSTANTIATE(P)                                                                                                                      \
-    template void msm_launch_bucket_direct<P>(const uint32_t*, const Affine<P>*, const uint32_t*, const uint32_t*, uint32_t, size_t, Xyzz<P>*, uint32_t*, \
+    template void msm_launch_bucket_direct<P>(const uint32_t*, const Affine<P>*, const uint32_t*, const uint32_t*, uint32_t, size_t, Plane29<P>*, uint32_t*, \
                                               uint32_t*, hipStream_t);
 #ifdef LURK_MSM_BN254_TU  // msm_bucket_direct_bn254.hip
 LURK_DIRECT_INSTANTIATE(Bn254Fq)

@@ -12,10 +12,14 @@
 //   3. accumulate  buckets are cut into tasks of <= S sorted entries, ordered longest first; one
 //                  lane per task runs XYZZ mixed additions over gathered bases on the radix-2^29
 //                  layer (curve29.cuh: msm_task_accumulate29; msm_task_accumulate below is the
-//                  32-bit-limb statement of the same loop, kept for A/B runs and the host harness)
-//   4. finalize    per bucket: sum of its task partials (hot buckets by a workgroup tree)
-//   5. reduce      sum_b b*B_b = S + sum_k 2^k P_k: bit-plane merge tree (c-1 levels of depth one
-//                  addition) + Horner                                           (msm_reduce.hip)
+//                  32-bit-limb statement of the same loop, kept for A/B runs and the host harness);
+//                  a task's sum is stored as a 160-byte record of that layer (Plane29), into the
+//                  bucket's own slot when the bucket is that one task
+//   4. finalize    per bucket of two or more tasks: the sum of its task records, on the same layer
+//                  (hot buckets by a workgroup tree); empty buckets get their identity record
+//   5. reduce      sum_b b*B_b = S + sum_k 2^k P_k: bit-plane merge tree over the bucket records (c-1
+//                  levels of depth one addition) + Horner; only the last level leaves the layer
+//                                                                               (msm_reduce.hip)
 //   6. combine     sum_w 2^(c*w) * W_w on the host over <= 16 points (sequential doublings: a
 //                  latency-bound tail that one host core runs ~20x faster than one GPU lane)
 // "Key space" = set of buckets entries are sorted into: one per window in the plain mode (G = W,

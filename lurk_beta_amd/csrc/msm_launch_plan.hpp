@@ -31,6 +31,7 @@ enum class MsmAccForm {
 struct MsmTuning {
     int persistent = 1, max_acc = 2, placement_log = 0, bucket_direct = 1;
     size_t persistent_min = (size_t)24 << 20;
+    int persist_s = 128;  // entries per task of a PERSISTENT_ACC_STREAM commitment whose shape has full tasks (128 = MSM_S_MAX, or 64 = MSM_S)
     static MsmTuning from_env() {
         auto geti = [](const char* k, int d) { const char* v = getenv(k); return v ? atoi(v) : d; };
         MsmTuning t;
@@ -43,6 +44,11 @@ struct MsmTuning {
         t.max_acc = geti("LURK_MSM_MAX_ACC", 2);              // persistent accumulations resident at once (0 = no limit)
         t.bucket_direct = geti("LURK_MSM_BUCKET_DIRECT", 1);  // 0: short commitments keep the planned-task stages (A/B runs, parity test)
         t.placement_log = geti("LURK_MSM_PLACEMENT_LOG", 0);  // diagnostic: persistent workgroups per CU, on stderr
+        // 128-entry tasks make a Poisson(96) bucket - 2^22 uniform scalars over 2^19 buckets - ONE task: its sum is stored in place and
+        // finalize has no addition for it, where 64-entry tasks cost a general addition per bucket.  The price is a longer tail per lane,
+        // which only the form with another resident accumulation behind it hides: the plain launch and the FOLLOW class keep MSM_S.
+        // 64 against 128 alternating on one box: 1 100-1 107 against 1 113 Mscalar-mul/s (LURK_MSM_PERSIST_S=64 for A/B runs)
+        t.persist_s = geti("LURK_MSM_PERSIST_S", 128) == 64 ? 64 : 128;
         if (t.max_acc > 2) t.max_acc = 0;
         return t;
     }

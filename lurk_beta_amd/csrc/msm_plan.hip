@@ -1,7 +1,6 @@
 // msm_plan.hip - stage 3 of the MSM pipeline (msm_core.cuh): the sorted entries of every bucket are cut into tasks of <= S entries and the
-// tasks ordered longest first for the accumulation; and the hot-bucket half of stage 5 (msm_finalize.hip lists the buckets with more
-// than MSM_FIN_SMALL task partials, a workgroup each sums them here).  Everything in this unit calls the multiplier as a function: the
-// kernels are short and bound by latency or LDS atomics.
+// tasks ordered longest first for the accumulation; each task is also told where its sum goes in the slot's record array (task_dest).
+// The kernels are short and bound by latency or LDS atomics; none of them touches a field element.
 #include "common.hpp"
 #include "msm_core.cuh"
 #include "msm_sort.hpp"
@@ -64,7 +63,8 @@ __global__ __launch_bounds__(1024) void msm_taskscan_kernel(const uint32_t* __re
 constexpr int MSM_NG_MAX = 64;
 __global__ __launch_bounds__(256) void msm_tasks_kernel(const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ bucket_start,
                                                           const uint32_t* __restrict__ task_start, const uint32_t* __restrict__ group_tasks,
-                                                          uint32_t* __restrict__ group_task_base_out, int NG, uint2* __restrict__ task_info, uint32_t S, int low) {
+                                                          uint32_t* __restrict__ group_task_base_out, int NG, uint32_t NB, uint2* __restrict__ task_info,
+                                                          uint32_t* __restrict__ task_dest, uint32_t S, int low) {
     msm_set_wave_prio(low);
     __shared__ uint32_t group_task_base[MSM_NG_MAX + 1];
     if (threadIdx.x == 0) {
@@ -90,18 +90,22 @@ __global__ __launch_bounds__(256) void msm_tasks_kernel(const uint32_t* __restri
     uint32_t first = bucket_start[key] + part * S;
     uint32_t end = bucket_start[key] + cnt[key];
     task_info[t] = make_uint2(first, first + S < end ? first + S : end);
+    // where the accumulation stores this task's sum in the slot's record array (msm_stages.hpp): a bucket that is ONE task is its
+    // task's sum - straight into the bucket's slot, and the finalize stage has nothing to do for it; otherwise the task's own slot
+    // behind the NB buckets
+    task_dest[t] = cnt[key] <= S ? (uint32_t)key : NB + t;
 }
 
-// Longest-task-first order: tasks are counting-sorted by length (1..MSM_S) in descending order, so
+// Longest-task-first order: tasks are counting-sorted by length (1..S <= MSM_S_MAX) in descending order, so
 // the 64 lanes of a wave run tasks of equal length (no lane waits for the longest task of its wave;
 // bucket sizes are ragged - Poisson around their mean - and skewed for witness-like scalars) and the
-// short tasks fill the tail of the launch.  Full tasks (length MSM_S, the bulk at large n) are
+// short tasks fill the tail of the launch.  Full tasks (length S, the bulk at large n) are
 // counted per wave with one ballot instead of one LDS atomic each.
 __global__ __launch_bounds__(1024) void msm_len_hist_kernel(const uint2* __restrict__ task_info, const uint32_t* __restrict__ group_task_base,
                                                               int NG, uint32_t* __restrict__ len_hist, uint32_t S, int low) {
     msm_set_wave_prio(low);
-    __shared__ uint32_t sh[MSM_S + 1];
-    if (threadIdx.x <= MSM_S) sh[threadIdx.x] = 0;
+    __shared__ uint32_t sh[MSM_S_MAX + 1];
+    if (threadIdx.x <= MSM_S_MAX) sh[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t ntasks = group_task_base[NG];
     for (uint32_t base = blockIdx.x * 8192u; base < ntasks; base += gridDim.x * 8192u) {
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(1024) void msm_len_hist_kernel(const uint2* __restr
         }
     }
     __syncthreads();
-    if (threadIdx.x <= MSM_S && sh[threadIdx.x]) atomicAdd(&len_hist[threadIdx.x], sh[threadIdx.x]);
+    if (threadIdx.x <= MSM_S_MAX && sh[threadIdx.x]) atomicAdd(&len_hist[threadIdx.x], sh[threadIdx.x]);
 }
 // (the start offset of each length class, longest first, is scanned from len_hist by every workgroup of the scatter below: the class
 // cursors count from zero - they are cleared with the other small counters by the sort's single-block launch)
@@ -127,7 +131,7 @@ __global__ __launch_bounds__(1024) void msm_len_scatter_kernel(const uint2* __re
                                                                  const uint32_t* __restrict__ len_hist, uint32_t* __restrict__ len_cursor,
                                                                  uint32_t* __restrict__ order, uint32_t S, int low) {
     msm_set_wave_prio(low);
-    __shared__ uint32_t sh_cnt[MSM_S + 1], sh_base[MSM_S + 1], sh_class[MSM_S + 1];
+    __shared__ uint32_t sh_cnt[MSM_S_MAX + 1], sh_base[MSM_S_MAX + 1], sh_class[MSM_S_MAX + 1];
     if (threadIdx.x == 0) {
         uint32_t run = 0;
         for (int l = (int)S; l >= 0; l--) {
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(1024) void msm_len_scatter_kernel(const uint2* __re
     __syncthreads();
     const uint32_t ntasks = group_task_base[NG];
     for (uint32_t base = blockIdx.x * 1024u; base < ntasks; base += gridDim.x * 1024u) {
-        if (threadIdx.x <= MSM_S) sh_cnt[threadIdx.x] = 0;
+        if (threadIdx.x <= MSM_S_MAX) sh_cnt[threadIdx.x] = 0;
         __syncthreads();
         uint32_t t = base + threadIdx.x;
         uint32_t len = 0, rank = 0;
@@ -157,72 +161,22 @@ __global__ __launch_bounds__(1024) void msm_len_scatter_kernel(const uint2* __re
             rank = atomicAdd(&sh_cnt[len], 1u);
         }
         __syncthreads();
-        if (threadIdx.x <= MSM_S && sh_cnt[threadIdx.x]) sh_base[threadIdx.x] = sh_class[threadIdx.x] + atomicAdd(&len_cursor[threadIdx.x], sh_cnt[threadIdx.x]);
+        if (threadIdx.x <= MSM_S_MAX && sh_cnt[threadIdx.x]) sh_base[threadIdx.x] = sh_class[threadIdx.x] + atomicAdd(&len_cursor[threadIdx.x], sh_cnt[threadIdx.x]);
         __syncthreads();
         if (len != 0) order[sh_base[len] + rank] = t;
         __syncthreads();
     }
 }
 
-// the four launches of the plan; len_hist holds the length histogram and, MSM_S + 1 words on, the class cursors
+// the four launches of the plan; len_hist holds the length histogram and, MSM_S_MAX + 1 words on, the class cursors
 void msm_launch_plan_tasks(const uint32_t* cnt, const uint32_t* bucket_start, uint32_t* task_start, uint32_t* group_tasks, uint32_t* group_task_base,
-                           int NG, uint2* task_info, uint32_t* len_hist, uint32_t* order, size_t nt, uint32_t S, int low, hipStream_t s) {
+                           int NG, uint32_t NB, uint2* task_info, uint32_t* task_dest, uint32_t* len_hist, uint32_t* order, size_t nt, uint32_t S, int low,
+                           hipStream_t s) {
     hipLaunchKernelGGL(msm_taskscan_kernel, dim3(NG), dim3(1024), 0, s, cnt, task_start, group_tasks, S, low);
-    hipLaunchKernelGGL(msm_tasks_kernel, dim3(div_up(nt, 256)), dim3(256), 0, s, cnt, bucket_start, task_start, group_tasks, group_task_base, NG, task_info, S,
-                       low);
+    hipLaunchKernelGGL(msm_tasks_kernel, dim3(div_up(nt, 256)), dim3(256), 0, s, cnt, bucket_start, task_start, group_tasks, group_task_base, NG, NB, task_info,
+                       task_dest, S, low);
     hipLaunchKernelGGL(msm_len_hist_kernel, dim3(256), dim3(1024), 0, s, task_info, group_task_base, NG, len_hist, S, low);
-    hipLaunchKernelGGL(msm_len_scatter_kernel, dim3(512), dim3(1024), 0, s, task_info, group_task_base, NG, len_hist, len_hist + MSM_S + 1, order, S, low);
+    hipLaunchKernelGGL(msm_len_scatter_kernel, dim3(512), dim3(1024), 0, s, task_info, group_task_base, NG, len_hist, len_hist + MSM_S_MAX + 1, order, S, low);
 }
-
-template <class P, int BLOCK>
-__device__ void block_tree_sum(Xyzz<P>& acc, Xyzz<P>* sh) {
-    const int t = threadIdx.x;
-    sh[t] = acc;
-    __syncthreads();
-    for (int stride = BLOCK / 2; stride >= 1; stride >>= 1) {
-        if (t < stride) {
-            xyzz_add<P>(acc, sh[t + stride]);
-            sh[t] = acc;
-        }
-        __syncthreads();
-    }
-}
-
-// ---- 5. the hot buckets (more than MSM_FIN_SMALL partials): one workgroup each, lanes stride the partials
-template <class P>
-__global__ __launch_bounds__(256) void msm_big_bucket_kernel(const Xyzz<P>* __restrict__ partials, const uint32_t* __restrict__ cnt,
-                                                               const uint32_t* __restrict__ task_start,
-                                                               const uint32_t* __restrict__ group_task_base, Xyzz<P>* __restrict__ buckets,
-                                                               const uint32_t* __restrict__ big_list, const uint32_t* __restrict__ big_count, uint32_t S) {
-    msm_set_wave_prio(0);
-    extern __shared__ uint4 lds_raw[];
-    Xyzz<P>* sh = reinterpret_cast<Xyzz<P>*>(lds_raw);
-    const uint32_t nbig = *big_count;
-    for (uint32_t i = blockIdx.x; i < nbig; i += gridDim.x) {
-        uint32_t key = big_list[i];
-        uint32_t g = key / MSM_GRP, b = key % MSM_GRP;
-        uint32_t nt = (cnt[key] + S - 1) / S;
-        uint32_t first = group_task_base[g] + task_start[(size_t)g * (MSM_GRP + 1) + b];
-        Xyzz<P> acc = xyzz_identity<P>();
-        for (uint32_t j = threadIdx.x; j < nt; j += 256) xyzz_add<P>(acc, partials[first + j]);
-        block_tree_sum<P, 256>(acc, sh);
-        if (threadIdx.x == 0) buckets[key] = acc;
-        __syncthreads();
-    }
-}
-
-template <class P>
-void msm_launch_big_buckets(const Xyzz<P>* partials, const uint32_t* cnt, const uint32_t* task_start, const uint32_t* group_task_base, Xyzz<P>* buckets,
-                            const uint32_t* big_list, const uint32_t* big_count, uint32_t S, hipStream_t s) {
-    hipLaunchKernelGGL((msm_big_bucket_kernel<P>), dim3(128), dim3(256), 256 * sizeof(Xyzz<P>), s, partials, cnt, task_start, group_task_base, buckets, big_list,
-                       big_count, S);
-}
-#define LURK_BIG_BUCKETS_INSTANTIATE(P)                                                                                                                   \
-    template void msm_launch_big_buckets<P>(const Xyzz<P>*, const uint32_t*, const uint32_t*, const uint32_t*, Xyzz<P>*, const uint32_t*, const uint32_t*, \
-                                            uint32_t, hipStream_t);
-LURK_BIG_BUCKETS_INSTANTIATE(PallasFp)
-LURK_BIG_BUCKETS_INSTANTIATE(PallasFq)
-LURK_BIG_BUCKETS_INSTANTIATE(Bn254Fq)
-LURK_BIG_BUCKETS_INSTANTIATE(Bn254Fr)
 
 }  // namespace lurk

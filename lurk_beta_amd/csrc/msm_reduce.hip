@@ -7,7 +7,7 @@
 //
 // One launch per level (c - 1 = 19 at 20-bit windows).  What round 3 changed:
 //   * points travel between levels on the radix-2^29 layer (curve29.cuh: xyzz29_add, the inlined 135-mad multiplier - no call per
-//     product, no conversion between levels): 160-byte records with the identity as a flag; level 0 converts the buckets on the fly,
+//     product, no conversion between levels): 160-byte records with the identity as a flag; level 0 reads the buckets in the same form (msm_finalize.hip),
 //     the last level stores ordinary XYZZ points straight into the slot's pinned host buffer (no copy node behind it);
 //   * measured and dropped: ALL levels in one persistent launch behind grid barriers (512 workgroups, one monotonic counter, agent-
 //     scope release / relaxed poll / acquire): 1.07 ms per reduction against 0.45 for the launches - a counter barrier costs 13 us
@@ -69,23 +69,12 @@ __device__ __forceinline__ void level_add(Xyzz29<P>& r, bool& r_id, const Xyzz29
 
 constexpr int REDUCE_BLOCK = 256;
 
-template <class P>
-struct Plane29 {
-    Xyzz29<P> p;
-    uint32_t id, pad[3];
-};
+// (Plane29, the 160-byte record of every level - and of the buckets level 0 reads - is curve29.cuh's: plane_load / plane_store)
 
-template <class P>
-__device__ __forceinline__ void plane_load(const Plane29<P>* __restrict__ src, Xyzz29<P>& v, bool& id) {
-    const Plane29<P> r = *src;
-    v = r.p;
-    id = r.id != 0;
-}
-
-// level k: in[g][seg][0..k] (segments of 2^k buckets; level 0 reads the buckets themselves) -> out[g][seg / 2][0..k+1]
+// level k: in[g][seg][0..k] (segments of 2^k buckets; level 0 reads the bucket records themselves) -> out[g][seg / 2][0..k+1]
 // LAST: the G x c plane sums leave as ordinary XYZZ points (out_host, pinned host memory) instead of plane records
 template <class P, bool FIRST, bool LAST>
-__global__ LURK_REDUCE_BOUNDS void msm_planes29_kernel(const Xyzz<P>* __restrict__ buckets, const Plane29<P>* __restrict__ in,
+__global__ LURK_REDUCE_BOUNDS void msm_planes29_kernel(const Plane29<P>* __restrict__ buckets, const Plane29<P>* __restrict__ in,
                                                                       Plane29<P>* __restrict__ out, Xyzz<P>* __restrict__ out_host, int k, int G, uint32_t B) {
     __builtin_amdgcn_s_setprio(3);  // a latency-bound tail kernel: issue ahead of an accumulation sharing the SIMD
     const size_t nseg_out = (size_t)B >> (k + 1);
@@ -113,11 +102,9 @@ __global__ LURK_REDUCE_BOUNDS void msm_planes29_kernel(const Xyzz<P>* __restrict
     Xyzz29<P> r, h;
     bool r_id, h_id;
     if (FIRST) {  // segments of one bucket, one component (S)
-        const Xyzz<P> hi = buckets[g * B + 2 * seg + 1];
-        xyzz29_from_xyzz<P>(hi, h, h_id);
+        plane_load<P>(buckets + (g * B + 2 * seg + 1), h, h_id);
         if (comp == 0) {
-            const Xyzz<P> lo = buckets[g * B + 2 * seg];
-            xyzz29_from_xyzz<P>(lo, r, r_id);
+            plane_load<P>(buckets + (g * B + 2 * seg), r, r_id);
             level_add<P>(r, r_id, h, h_id);
         } else {
             r = h;
@@ -137,11 +124,7 @@ __global__ LURK_REDUCE_BOUNDS void msm_planes29_kernel(const Xyzz<P>* __restrict
     if (LAST) {
         out_host[id] = xyzz29_to_xyzz<P>(r, r_id);
     } else {
-        Plane29<P> o;
-        o.p = r;
-        o.id = r_id;
-        o.pad[0] = o.pad[1] = o.pad[2] = 0;
-        out[id] = o;
+        plane_store<P>(out + id, r, r_id);
     }
 }
 
@@ -153,7 +136,7 @@ __global__ LURK_REDUCE_BOUNDS void msm_planes29_kernel(const Xyzz<P>* __restrict
 // new plane k + 1 is S2 + S3 - what the S thread holds after its first addition, stored from there.  The three-addition threads come
 // first, the one-addition threads in waves of their own behind them.  FIRST: the inputs are the buckets themselves (k = 0).
 template <class P, bool FIRST>
-__global__ LURK_REDUCE_BOUNDS void msm_planes29_quad_kernel(const Xyzz<P>* __restrict__ buckets, const Plane29<P>* __restrict__ in,
+__global__ LURK_REDUCE_BOUNDS void msm_planes29_quad_kernel(const Plane29<P>* __restrict__ buckets, const Plane29<P>* __restrict__ in,
                                                                            Plane29<P>* __restrict__ out, int k, int G, uint32_t B) {
     __builtin_amdgcn_s_setprio(3);
     const size_t nseg_out = (size_t)B >> (k + 2);
@@ -174,18 +157,13 @@ __global__ LURK_REDUCE_BOUNDS void msm_planes29_quad_kernel(const Xyzz<P>* __res
     }
     auto load = [&](int q, Xyzz29<P>& v, bool& id) {
         if (FIRST) {
-            const Xyzz<P> b = buckets[g * B + 4 * seg + q];
-            xyzz29_from_xyzz<P>(b, v, id);
+            plane_load<P>(buckets + (g * B + 4 * seg + q), v, id);
         } else {
             plane_load<P>(in + ((g * (nseg_out * 4) + 4 * seg + q) * ci + comp), v, id);
         }
     };
     auto store = [&](size_t c_out, const Xyzz29<P>& v, bool id) {
-        Plane29<P> o;
-        o.p = v;
-        o.id = id;
-        o.pad[0] = o.pad[1] = o.pad[2] = 0;
-        out[(g * nseg_out + seg) * co + c_out] = o;
+        plane_store<P>(out + ((g * nseg_out + seg) * co + c_out), v, id);
     };
     Xyzz29<P> r, h;
     bool r_id, h_id;
@@ -250,11 +228,7 @@ __global__ LURK_REDUCE_BOUNDS void msm_planes29_wave_kernel(const Plane29<P>* __
     if (LAST) {
         out_host[id] = xyzz29_to_xyzz<P>(r, r_id);
     } else {
-        Plane29<P> o;
-        o.p = r;
-        o.id = r_id;
-        o.pad[0] = o.pad[1] = o.pad[2] = 0;
-        out[id] = o;
+        plane_store<P>(out + id, r, r_id);
     }
 }
 
@@ -274,16 +248,16 @@ static bool reduce_quad_levels() {
     return on;
 }
 
-// planes_a / planes_b: msm_reduce_plane_bytes(G * B) each; out_host: G * c XYZZ points of pinned host memory
+// buckets: the G * B bucket records (the front of the slot's record array); planes_a / planes_b: msm_reduce_plane_bytes(G * B) each; out_host: G * c XYZZ points of pinned host memory
 template <class P>
-void msm_launch_reduce(const Xyzz<P>* buckets, void* planes_a, void* planes_b, int c, int G, uint32_t B, Xyzz<P>* out_host, hipStream_t s) {
+void msm_launch_reduce(const Plane29<P>* buckets, void* planes_a, void* planes_b, int c, int G, uint32_t B, Xyzz<P>* out_host, hipStream_t s) {
     static_assert(sizeof(Plane29<P>) == 160, "plane record");
     Plane29<P>* bufs[2] = {(Plane29<P>*)planes_a, (Plane29<P>*)planes_b};
     // the last <= 12 levels as two wave butterflies, starting where the first of them is at most two waves per SIMD
     int K = c - 1;  // levels [0, K) one launch each
     if (reduce_wave_levels() && c >= 3 && B == (1u << (c - 1))) {
         K = c - 1 > 12 ? c - 1 - 12 : 0;
-        if (K < 1) K = 1;  // (level 0 converts the buckets)
+        if (K < 1) K = 1;  // (level 0 reads the bucket array, not a plane buffer)
         const size_t cap = (size_t)num_cus() * 4 * 2;
         auto waves = [&](int k) {
             const int rem = c - 1 - k, log1 = rem > 6 ? rem - rem / 2 : rem;
@@ -332,11 +306,11 @@ void msm_launch_reduce(const Xyzz<P>* buckets, void* planes_a, void* planes_b, i
     LURK_HIP_CHECK(hipGetLastError());
 }
 #ifdef LURK_MSM_BN254_TU  // msm_reduce_bn254.hip
-template void msm_launch_reduce<Bn254Fq>(const Xyzz<Bn254Fq>*, void*, void*, int, int, uint32_t, Xyzz<Bn254Fq>*, hipStream_t);
-template void msm_launch_reduce<Bn254Fr>(const Xyzz<Bn254Fr>*, void*, void*, int, int, uint32_t, Xyzz<Bn254Fr>*, hipStream_t);
+template void msm_launch_reduce<Bn254Fq>(const Plane29<Bn254Fq>*, void*, void*, int, int, uint32_t, Xyzz<Bn254Fq>*, hipStream_t);
+template void msm_launch_reduce<Bn254Fr>(const Plane29<Bn254Fr>*, void*, void*, int, int, uint32_t, Xyzz<Bn254Fr>*, hipStream_t);
 #else
-template void msm_launch_reduce<PallasFp>(const Xyzz<PallasFp>*, void*, void*, int, int, uint32_t, Xyzz<PallasFp>*, hipStream_t);
-template void msm_launch_reduce<PallasFq>(const Xyzz<PallasFq>*, void*, void*, int, int, uint32_t, Xyzz<PallasFq>*, hipStream_t);
+template void msm_launch_reduce<PallasFp>(const Plane29<PallasFp>*, void*, void*, int, int, uint32_t, Xyzz<PallasFp>*, hipStream_t);
+template void msm_launch_reduce<PallasFq>(const Plane29<PallasFq>*, void*, void*, int, int, uint32_t, Xyzz<PallasFq>*, hipStream_t);
 #endif
 
 }  // namespace lurk

@@ -30,6 +30,8 @@ constexpr int MSM_P_PER_MAX = MSM_P_MAX / MSM_SORT_BLOCK;
 constexpr int MSM_NB1 = 256 * (1024 / MSM_SORT_BLOCK);  // workgroups of pass 1 (one per CU at 1024 threads, two at 512)
 constexpr int MSM_S = 64;          // sorted entries per accumulation task (the most: MsmShape::S is what a commitment uses)
 constexpr int MSM_S_MIN = 8;
+constexpr int MSM_S_MAX = 128;     // the task length of the persistent form on the accumulate stream (msm_launch_plan.hpp: persist_s), and what
+                                   // the plan's length classes and counters have room for
 constexpr size_t MSM_TASK_TARGET = 131072;  // tasks that fill the chip: 256 CUs x 4 SIMDs x 64 lanes x 2 waves
 constexpr size_t MSM_LDS_BYTES = 160 * 1024;  // per workgroup on gfx950
 constexpr int MSM_LB_MAX = 8;      // low key bits sorted in pass 2: they travel as one byte per entry
