@@ -3,14 +3,15 @@
 instruction-rate probes measured (bench_tools/microbench.hip -> profiles/r04_microbench_instr_rates.txt) and add them up.
 
 What the probes say (cycles per wave-instruction per SIMD at 2.4 GHz, one wave64 instruction stream per SIMD saturating the VALU):
-    v_mad_u64_u32                                   4.7    (also v_fma_f64 4.8)
+    v_mad_u64_u32, v_mad_i64_i32                    4.7    (also v_fma_f64 4.8)
     any VOP3-encoded / 64-bit / SGPR-operand form   4.1    v_lshrrev_b64, v_lshl_add_u64, v_mov_b64, v_alignbit_b32, v_add3_u32, v_cndmask e64,
                                                            v_addc_co, v_mul_lo/hi_u32, v_add_u32 with an SGPR operand
     VOP2 / VOP1 e32 on VGPRs, inline constants      2.3    v_add_u32, v_sub_u32, v_and_b32, v_xor_b32, v_lshrrev_b32, v_mov_b32
     and 32-bit LITERALS (measured: 2.2)
 Only the last class runs at the "full" rate, so a multiplier's true ceiling is NOT its v_mad count alone.
 
-usage: issue_model.py <listing.s> <kernel name substring> [units per loop trip = 1] [whole]
+usage: issue_model.py <listing.s> <kernel name substring> [units per loop trip = 1] [whole | mads>=N]
+       `mads>=N`: the shortest loop with at least N 64-bit mads instead of the largest loop
        `whole`: census of the WHOLE kernel body, every instruction counted once (for straight-line kernels such as the unrolled NTT pass:
        units = elements per lane; the few instructions inside short loops are under-counted, stated in the output)
        hipcc -O3 --offload-arch=gfx950 -S --cuda-device-only lurk_beta_amd/csrc/msm_acc.hip -o acc.s   (same flags as the Makefile)
@@ -30,7 +31,7 @@ def classify(line):
     op, _, rest = line.partition(" ")
     if not op.startswith("v_"):
         return None
-    if op.startswith("v_mad_u64_u32") or op.startswith("v_fma_f64"):
+    if op.startswith(("v_mad_u64_u32", "v_mad_i64_i32", "v_fma_f64")):  # the signed mad issues at the unsigned one's rate (profiles/r15_signed_mad_rate.txt)
         return "mad64"
     base = op[:-4] if op.endswith(("_e32", "_e64")) else op
     if op.endswith("_e64") or base not in VOP2_FAST:
@@ -57,6 +58,11 @@ def main(path, needle, units=1, mode="loop"):
                 loops.append((labels[t], i))
     if mode == "whole":
         a, b = 0, len(body) - 1
+    elif mode.startswith("mads>="):
+        # the shortest loop that issues at least that many 64-bit mads (a kernel whose outer loop holds more than one copy of the work,
+        # e.g. a task loop with a specialised first trip and an epilogue, has no longest loop that is also the steady one)
+        nmad = lambda x: sum(1 for l in body[x[0]:x[1] + 1] if l.strip().startswith(("v_mad_u64_u32", "v_mad_i64_i32")))
+        a, b = min((x for x in loops if nmad(x) >= int(mode[6:])), key=lambda x: x[1] - x[0])
     else:
         # the innermost loop that holds the bulk of the work: the shortest of the loops within 5 % of the longest
         longest = max(b - a for a, b in loops)

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
+#include <string>
 #include <functional>
 #define LURK_MUL_FORCE_INLINE_OFF
 #include "../lurk_beta_amd/csrc/field.cuh"
@@ -19,6 +20,24 @@ __global__ void k_mad64(uint32_t* out, uint32_t seed) {
     uint32_t x = seed * 3 + threadIdx.x, y = seed * 7 + 1;
     for (int it = 0; it < ITERS; it++) {
         asm volatile("v_mad_u64_u32 %0, s[20:21], %8, %9, %0\n v_mad_u64_u32 %1, s[20:21], %8, %9, %1\n v_mad_u64_u32 %2, s[20:21], %8, %9, %2\n v_mad_u64_u32 %3, s[20:21], %8, %9, %3\n v_mad_u64_u32 %4, s[20:21], %8, %9, %4\n v_mad_u64_u32 %5, s[20:21], %8, %9, %5\n v_mad_u64_u32 %6, s[20:21], %8, %9, %6\n v_mad_u64_u32 %7, s[20:21], %8, %9, %7" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(x), "v"(y) : "s20", "s21");
+    }
+    out[blockIdx.x * blockDim.x + threadIdx.x] = (uint32_t)(a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7);
+}
+// the signed form of the same stream: same operands, same accumulators, same carry-out pair, so the two rates compare like for like
+__global__ void k_mad64_signed(uint32_t* out, uint32_t seed) {
+    uint64_t a0 = (uint64_t)(seed + threadIdx.x + 0); uint64_t a1 = (uint64_t)(seed + threadIdx.x + 1); uint64_t a2 = (uint64_t)(seed + threadIdx.x + 2); uint64_t a3 = (uint64_t)(seed + threadIdx.x + 3); uint64_t a4 = (uint64_t)(seed + threadIdx.x + 4); uint64_t a5 = (uint64_t)(seed + threadIdx.x + 5); uint64_t a6 = (uint64_t)(seed + threadIdx.x + 6); uint64_t a7 = (uint64_t)(seed + threadIdx.x + 7);
+    uint32_t x = seed * 3 + threadIdx.x, y = 0u - (seed * 7 + 1);
+    for (int it = 0; it < ITERS; it++) {
+        asm volatile("v_mad_i64_i32 %0, s[20:21], %8, %9, %0\n v_mad_i64_i32 %1, s[20:21], %8, %9, %1\n v_mad_i64_i32 %2, s[20:21], %8, %9, %2\n v_mad_i64_i32 %3, s[20:21], %8, %9, %3\n v_mad_i64_i32 %4, s[20:21], %8, %9, %4\n v_mad_i64_i32 %5, s[20:21], %8, %9, %5\n v_mad_i64_i32 %6, s[20:21], %8, %9, %6\n v_mad_i64_i32 %7, s[20:21], %8, %9, %7" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(x), "v"(y) : "s20", "s21");
+    }
+    out[blockIdx.x * blockDim.x + threadIdx.x] = (uint32_t)(a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7);
+}
+// the two interleaved on one accumulator set, as a signed product block mixes them (operand mads signed, reduction mads unsigned)
+__global__ void k_mad64_mixed(uint32_t* out, uint32_t seed) {
+    uint64_t a0 = (uint64_t)(seed + threadIdx.x + 0); uint64_t a1 = (uint64_t)(seed + threadIdx.x + 1); uint64_t a2 = (uint64_t)(seed + threadIdx.x + 2); uint64_t a3 = (uint64_t)(seed + threadIdx.x + 3); uint64_t a4 = (uint64_t)(seed + threadIdx.x + 4); uint64_t a5 = (uint64_t)(seed + threadIdx.x + 5); uint64_t a6 = (uint64_t)(seed + threadIdx.x + 6); uint64_t a7 = (uint64_t)(seed + threadIdx.x + 7);
+    uint32_t x = seed * 3 + threadIdx.x, y = 0u - (seed * 7 + 1);
+    for (int it = 0; it < ITERS; it++) {
+        asm volatile("v_mad_i64_i32 %0, s[20:21], %8, %9, %0\n v_mad_u64_u32 %1, s[20:21], %8, %9, %1\n v_mad_i64_i32 %2, s[20:21], %8, %9, %2\n v_mad_u64_u32 %3, s[20:21], %8, %9, %3\n v_mad_i64_i32 %4, s[20:21], %8, %9, %4\n v_mad_u64_u32 %5, s[20:21], %8, %9, %5\n v_mad_i64_i32 %6, s[20:21], %8, %9, %6\n v_mad_u64_u32 %7, s[20:21], %8, %9, %7" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(x), "v"(y) : "s20", "s21");
     }
     out[blockIdx.x * blockDim.x + threadIdx.x] = (uint32_t)(a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7);
 }
@@ -339,7 +358,7 @@ static double time_kernel(std::function<void()> f, int reps = 3) {
     return best;
 }
 
-int main() {
+int main(int argc, char** argv) {
     hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, 0));
     printf("device %s, %d CUs, clock %d MHz\n", prop.gcnArchName, prop.multiProcessorCount, prop.clockRate / 1000);
     const int blocks = prop.multiProcessorCount * 16, threads = 256;
@@ -349,6 +368,13 @@ int main() {
         double winstr = waves * ITERS * PER_ITER; printf("%-22s %8.3f ms  %8.2f G wave-instr/s  %7.2f T lane-ops/s  (%.2f cyc/wave-instr/SIMD @2.4GHz)\n", LABEL, ms, winstr / ms / 1e6, winstr * 64 / ms / 1e9, \
         2.4e9 * (ms / 1e3) * prop.multiProcessorCount * 4 / winstr); }
     RUN_PROBE(k_mad64, 8, "v_mad_u64_u32");
+    RUN_PROBE(k_mad64_signed, 8, "v_mad_i64_i32");
+    RUN_PROBE(k_mad64_mixed, 8, "v_mad i64/u64 alternating");
+    if (argc > 1 && std::string(argv[1]) == "mad") {  // only the signed-against-unsigned comparison, each stream a second time
+        RUN_PROBE(k_mad64, 8, "v_mad_u64_u32");
+        RUN_PROBE(k_mad64_signed, 8, "v_mad_i64_i32");
+        return 0;
+    }
     RUN_PROBE(k_mul_lo, 8, "v_mul_lo_u32");
     RUN_PROBE(k_mul_hi, 8, "v_mul_hi_u32");
     RUN_PROBE(k_mul_u24, 8, "v_mul_u32_u24");

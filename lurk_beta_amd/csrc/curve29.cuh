@@ -13,6 +13,12 @@
 // Y3 rows (two tight terms) through dot29_finish2: reduction columns below 2^63, which the Pasta blocks without the mads by
 // modulus limb 0 need (field29.cuh).  The exceptions are in the doublings, u * u (2^30 x 2^30) and m * (s - x) (tight x loose): they
 // call the wide f29_mul.
+//
+// On the Pasta fields the task loops (msm_task_accumulate29_raw) run the mixed addition on SIGNED limbs instead, xyzz29_madd_s below:
+// differences are limb-wise signed differences that are multiplied as they stand, the accumulator is "S-bounded" (limbs 0..7 tight,
+// a signed top limb, |value| < 2^259) between additions, and a task's sum becomes R-bounded once, after its last addition.  Stored
+// records are R-bounded under either form.  xyzz29_madd itself is still what msm_small.hip, ipa.hip, the hot-bucket share of
+// msm_bucket_direct.hip and every BN254 / Grumpkin instantiation call.
 #pragma once
 #include "curve.cuh"
 #include "field29.cuh"
@@ -258,6 +264,161 @@ LURK_HD void xyzz29_madd(Xyzz29<P>& acc, bool& acc_id, const Affine<P>& q, bool 
     }
 }
 
+// ---- the mixed addition on SIGNED limbs (Pasta fields: f29_p1_form) ---------------------------------------------------------------
+// The unsigned form above pays for every difference with the 64p bias and a carry pass, and for the growth by 64p per subtraction
+// with two f29_reduce.  Here a difference is the limb-wise signed difference of its operands ("s-diff", field29.cuh) and is
+// multiplied as it stands by the signed product blocks; only X3, a sum of three products, takes one signed carry pass.
+// Loop invariant ("S-bounded"): each accumulator coordinate is s-tight with |value| < 2^259, i.e. a top limb in [-2^27, 2^27)
+// (F29S_ASSERT_ACC).  With P' = 2^254, R' = 2^261 = 128 P' and |a b / R'| + p bounding a product, one general addition gives from
+// |X1|, |Y1|, |ZZ|, |ZZZ| < 32 P' and qx, qy < 32 P':  |U2|, |S2| < 9 P';  |p|, |r| < 41 P';  PP, R2 < 14.2 P';  |PPP| < 5.6 P';
+// |Q| < 4.6 P';  |X3| < 14.2 + 5.6 + 9.2 = 29 P';  |D| < 33.6 P';  |Y3| < (41 * 33.6 + 32 * 5.6) / 128 + 1 < 13.2 P';
+// |ZZ'| < 4.6 P', |ZZZ'| < 2.4 P': S-bounded again, and every operand of a product has |value| < 2^262 and a top limb in
+// (-2^30, 2^30).  The affine + affine form (once per task) has |p|, |r| < 64 P' and would leave |X3| up to 43 P': its X3 and Y3
+// leave through f29_norm_s, as every task sum does after its last addition, so that stored records stay R-bounded.
+#ifndef LURK_ACC_SIGNED
+#define LURK_ACC_SIGNED 1
+#endif
+#if F29_CHECKS_ACTIVE
+#define F29S_ASSERT_ACC(v, what)                                                                                                  \
+    do {                                                                                                                          \
+        F29_ASSERT_LIMBS8(v, what);                                                                                               \
+        const int32_t _t = (int32_t)(v).l[8];                                                                                     \
+        if (_t < -(1 << 27) || _t >= (1 << 27)) { printf("F29 bound violated: %s top limb = %d (|value| >= 2^259)\n", what, _t); abort(); } \
+    } while (0)
+#define F29_ASSERT_LIMBS8(v, what)                                                                                                \
+    do {                                                                                                                          \
+        for (int _i = 0; _i < 8; _i++)                                                                                            \
+            if ((v).l[_i] >> 29) { printf("F29 bound violated: %s limb %d = %u (>= 2^29)\n", what, _i, (v).l[_i]); abort(); }    \
+    } while (0)
+#else
+#define F29S_ASSERT_ACC(v, what) ((void)0)
+#define F29_ASSERT_LIMBS8(v, what) ((void)0)
+#endif
+// limb-wise a - b and -a on signed limbs (two's complement in the uint32 of F29): s-tight operands give an s-diff value
+template <class P>
+LURK_HD F29<P> f29_sub_s(const F29<P>& a, const F29<P>& b) {
+    F29<P> r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] - b.l[i];
+    return r;
+}
+template <class P>
+LURK_HD F29<P> f29_neg_s(const F29<P>& a) {
+    F29<P> r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = 0u - a.l[i];
+    return r;
+}
+// signed carry pass over signed limbs in (-2^31 + 2^3, 2^31 - 2^3): s-tight, the signed top limb keeps the rest
+template <class P>
+LURK_HD F29<P> f29_carry_s(const F29<P>& a) {
+    F29<P> r;
+    uint32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t x = a.l[i] + c;
+        r.l[i] = x & F29_MASK;
+        c = (uint32_t)((int32_t)x >> 29);  // arithmetic shift
+    }
+    r.l[8] = a.l[8] + c;
+    return r;
+}
+// S-bounded (or any signed-limb value with |value| < 2^260 and limbs 0..7 in (-2^30, 2^30)) -> the R-bounded representative of the
+// same residue: + 64p (f29_bias: > 2^260, limbs 0..7 in [2^30, 2^30 + 2^29)) makes every limb and the value positive, below 2^261;
+// one carry pass makes it tight with a top limb below 2^29, f29_reduce brings it below 2^255.1.
+template <class P>
+LURK_HD F29<P> f29_norm_s(const F29<P>& a) {
+    F29<P> t;
+#pragma unroll
+    for (int i = 0; i < 9; i++) t.l[i] = a.l[i] + f29_bias<P>(i);
+    const F29<P> u = f29_carry<P>(t);
+    F29_ASSERT(u.l[8] < (1u << 29), "f29_norm_s: |value| >= 2^260");
+    return f29_reduce<P>(u);
+}
+// v == 0 mod p ? for an s-diff value with |v| < 64p, so v = k p with -64 < k < 64 and, p being 1 mod 2^29, k = v mod 2^29 read off
+// limb 0.  The pre-filter looks at limb 0 alone (a window of 128 residues out of 2^29); the exact comparison behind it adds 64p,
+// carries and compares as the unsigned form does.
+template <class P>
+LURK_HD bool f29_maybe_multiple_of_p_s(const F29<P>& v) {
+    return ((v.l[0] + 64u) & F29_MASK) < 128u;
+}
+template <class P>
+LURK_HD bool f29_is_multiple_of_p_s(const F29<P>& v) {
+    F29<P> t;
+#pragma unroll
+    for (int i = 0; i < 9; i++) t.l[i] = v.l[i] + f29_bias<P>(i);  // v + 64p, limbs in (2^29, 2^31)
+    t = f29_carry<P>(t);
+    F29_ASSERT(t.l[8] < (1u << 29), "f29_is_multiple_of_p_s: |v| >= 64p");
+    return f29_is_multiple_of_p<P>(t);
+}
+
+// acc += (+/-) q with the accumulator S-bounded (above) before and after: the group law and the exceptional cases of xyzz29_madd.
+// The sign of the base is applied once, to qy.  8 M + 2 S with the Y3 row as one reduction, as the unsigned form.
+template <class P, bool ACC_AFFINE = false>
+LURK_HD void xyzz29_madd_s(Xyzz29<P>& acc, bool& acc_id, const Affine<P>& q, bool negate) {
+    if (affine_is_identity<P>(q)) return;
+    const F29<P> qx = f29_from_mont256<P>(q.x);  // 32 x~ < 2^259, tight
+    const F29<P> qy = f29_from_mont256<P>(q.y);
+    const F29<P> qys = negate ? f29_neg_s<P>(qy) : qy;  // s-diff
+    if (acc_id) {
+        acc.x = qx;
+        acc.y = negate ? f29_carry_s<P>(qys) : qy;  // s-tight, |value| < 2^259
+        Fe<P> one = fe_one<P>();
+        acc.zz = f29_from_mont256<P>(one);
+        acc.zzz = acc.zz;
+        acc_id = false;
+        return;
+    }
+    F29S_ASSERT_ACC(acc.x, "acc.x"); F29S_ASSERT_ACC(acc.y, "acc.y"); F29S_ASSERT_ACC(acc.zz, "acc.zz"); F29S_ASSERT_ACC(acc.zzz, "acc.zzz");
+    const F29<P> u2 = ACC_AFFINE ? qx : f29_mul_s<P>(qx, acc.zz);
+    const F29<P> s2 = ACC_AFFINE ? qys : f29_mul_s<P>(qys, acc.zzz);
+    const F29<P> p = f29_sub_s<P>(u2, acc.x);  // s-diff, |p| < 41 P' (affine form: < 64 P')
+    // (affine form: S2 is qys itself, an s-diff value, so the limbs of S2 - Y1 reach (-2^30, 2^29): carried, once per task)
+    const F29<P> r = ACC_AFFINE ? f29_carry_s<P>(f29_sub_s<P>(s2, acc.y)) : f29_sub_s<P>(s2, acc.y);
+    if (f29_maybe_multiple_of_p_s<P>(p) && f29_is_multiple_of_p_s<P>(p)) {
+        if (f29_maybe_multiple_of_p_s<P>(r) && f29_is_multiple_of_p_s<P>(r)) {  // equal points: the doubling takes a normalised y
+            const F29<P> qyn = negate ? f29_reduce<P>(f29_carry<P>(f29_sub<P>(f29_zero<P>(), qy))) : qy;
+            acc = xyzz29_double_affine<P>(qx, qyn);
+            acc.zz = f29_reduce<P>(acc.zz);  // (2y)^2 / R' + (< p) may pass 2^259; the other three are R-bounded, hence S-bounded
+        } else {
+            acc_id = true;  // opposite points
+        }
+        return;
+    }
+    const F29<P> pp = f29_sqr_s<P>(p);
+    const F29<P> ppp = f29_mul_s<P>(p, pp);
+    const F29<P> qq = f29_mul_s<P>(acc.x, pp);
+    const F29<P> r2 = f29_sqr_s<P>(r);
+    // X3 = R^2 - PPP - 2Q: limbs 0..7 in (-3 * 2^29, 2^29), so one signed carry pass before it is multiplied
+    F29<P> x3;
+#pragma unroll
+    for (int i = 0; i < 9; i++) x3.l[i] = r2.l[i] - ppp.l[i] - (qq.l[i] << 1);
+    x3 = f29_carry_s<P>(x3);
+    const F29<P> d = f29_sub_s<P>(qq, x3);  // s-diff
+    // Y3 = R D - Y1 PPP as one signed row
+    F29<P> y3 = dot29_row2_s<P>(r, d, f29_neg_s<P>(acc.y), ppp);
+    if (ACC_AFFINE) {
+        acc.x = f29_norm_s<P>(x3);  // |X3| < 43 P' here (the invariant wants 32 P'): once per task
+        acc.y = f29_norm_s<P>(y3);
+        acc.zz = f29_reduce<P>(pp);  // < 33 P', and never negative (a square's output lies in [p^2 / R', p^2 / R' + p))
+        acc.zzz = f29_norm_s<P>(ppp);
+    } else {
+        acc.x = x3;
+        acc.y = y3;
+        acc.zz = f29_mul_s<P>(acc.zz, pp);
+        acc.zzz = f29_mul_s<P>(acc.zzz, ppp);
+    }
+    F29S_ASSERT_ACC(acc.x, "acc.x out"); F29S_ASSERT_ACC(acc.y, "acc.y out"); F29S_ASSERT_ACC(acc.zz, "acc.zz out"); F29S_ASSERT_ACC(acc.zzz, "acc.zzz out");
+}
+// a task's sum after its last addition: the R-bounded record plane_store asks for
+template <class P>
+LURK_HD void xyzz29_norm_s(Xyzz29<P>& acc) {
+    acc.x = f29_norm_s<P>(acc.x);
+    acc.y = f29_norm_s<P>(acc.y);
+    acc.zz = f29_norm_s<P>(acc.zz);
+    acc.zzz = f29_norm_s<P>(acc.zzz);
+}
+
 // Doubling of an R-bounded XYZZ29 point that is not the identity (dbl-2008-s-1, a = 0: 6 M + 3 S), result R-bounded: the link of
 // the doubling chains that build a window table (msm_precompute.hip).  The bounds are xyzz29_double_affine's with the two
 // products by zz / zzz of xyzz29_madd; a prime-order curve has no point with y = 0.
@@ -498,8 +659,18 @@ LURK_HD Affine<P> msm_task_next29(const uint32_t* sorted, const Affine<P>* table
 // as an ordinary XYZZ point for the host harnesses).
 // PIPELINED (the persistent kernel only): the same additions with the same arguments in the same order, the gather of record j + 1
 // and the load of index j + 2 issued in front of addition j, so that the only exposed gather of a task is its first.
+// the mixed addition of the task loops: the signed form on the Pasta fields (-DLURK_ACC_SIGNED=0: the unsigned one everywhere, A/B runs)
+template <class P>
+LURK_HD constexpr bool msm_acc_signed() {
+    return LURK_ACC_SIGNED != 0 && f29_p1_form<P>();
+}
+template <class P, bool ACC_AFFINE = false>
+LURK_HD void xyzz29_madd_task(Xyzz29<P>& acc, bool& acc_id, const Affine<P>& q, bool negate) {
+    if constexpr (msm_acc_signed<P>()) xyzz29_madd_s<P, ACC_AFFINE>(acc, acc_id, q, negate);
+    else xyzz29_madd<P, ACC_AFFINE>(acc, acc_id, q, negate);
+}
 template <class P, bool PIPELINED = false>
-LURK_HD void msm_task_accumulate29_raw(const uint32_t* sorted, uint32_t first, uint32_t last, const Affine<P>* table, Xyzz29<P>& acc, bool& acc_id) {
+LURK_HD void msm_task_accumulate29_loop(const uint32_t* sorted, uint32_t first, uint32_t last, const Affine<P>* table, Xyzz29<P>& acc, bool& acc_id) {
     acc.x = acc.y = acc.zz = acc.zzz = f29_zero<P>();
     acc_id = true;
     // Every trip of the plain loop below waits for two dependent loads (sorted[j], then the 64-byte record it names: a random read
@@ -522,19 +693,19 @@ LURK_HD void msm_task_accumulate29_raw(const uint32_t* sorted, uint32_t first, u
 #if LURK_ACC_AFFINE_FIRST
         {  // first base: a copy (zz = zzz = 1)
             const Affine<P> q = msm_task_next29<P>(sorted, table, j, last, neg_next, e_ahead, rec, negate);
-            xyzz29_madd<P>(acc, acc_id, q, negate);
+            xyzz29_madd_task<P>(acc, acc_id, q, negate);
             j++;
         }
         if (j < last) {  // second base: affine + affine (unless the first was the identity record)
             const Affine<P> q = msm_task_next29<P>(sorted, table, j, last, neg_next, e_ahead, rec, negate);
-            if (!acc_id) xyzz29_madd<P, true>(acc, acc_id, q, negate);
-            else xyzz29_madd<P>(acc, acc_id, q, negate);
+            if (!acc_id) xyzz29_madd_task<P, true>(acc, acc_id, q, negate);
+            else xyzz29_madd_task<P>(acc, acc_id, q, negate);
             j++;
         }
 #endif
         for (; j < last; j++) {
             const Affine<P> q = msm_task_next29<P>(sorted, table, j, last, neg_next, e_ahead, rec, negate);
-            xyzz29_madd<P>(acc, acc_id, q, negate);
+            xyzz29_madd_task<P>(acc, acc_id, q, negate);
         }
         return;
     }
@@ -542,21 +713,21 @@ LURK_HD void msm_task_accumulate29_raw(const uint32_t* sorted, uint32_t first, u
     uint32_t j = first;
     if (j < last) {  // first base: a copy (zz = zzz = 1)
         const uint32_t e = sorted[j++];
-        xyzz29_madd<P>(acc, acc_id, table[e & 0x7fffffffu], (e & 0x80000000u) != 0);
+        xyzz29_madd_task<P>(acc, acc_id, table[e & 0x7fffffffu], (e & 0x80000000u) != 0);
     }
     if (j < last) {  // second base: affine + affine (unless the first was the identity record)
         const uint32_t e = sorted[j++];
         const Affine<P> q = table[e & 0x7fffffffu];
 #if LURK_ACC_AFFINE_FIRST
-        if (!acc_id) xyzz29_madd<P, true>(acc, acc_id, q, (e & 0x80000000u) != 0);
+        if (!acc_id) xyzz29_madd_task<P, true>(acc, acc_id, q, (e & 0x80000000u) != 0);
         else
 #endif
-            xyzz29_madd<P>(acc, acc_id, q, (e & 0x80000000u) != 0);
+            xyzz29_madd_task<P>(acc, acc_id, q, (e & 0x80000000u) != 0);
     }
     for (; j < last; j++) {
         const uint32_t e = sorted[j];
         const Affine<P> q = table[e & 0x7fffffffu];
-        xyzz29_madd<P>(acc, acc_id, q, (e & 0x80000000u) != 0);
+        xyzz29_madd_task<P>(acc, acc_id, q, (e & 0x80000000u) != 0);
     }
 #else
     for (uint32_t j = first; j < last; j++) {
@@ -566,9 +737,17 @@ LURK_HD void msm_task_accumulate29_raw(const uint32_t* sorted, uint32_t first, u
 #else
         const Affine<P> q = table[e & 0x7fffffffu];
 #endif
-        xyzz29_madd<P>(acc, acc_id, q, (e & 0x80000000u) != 0);
+        xyzz29_madd_task<P>(acc, acc_id, q, (e & 0x80000000u) != 0);
     }
 #endif
+}
+// In the signed form the loop leaves an S-bounded sum, normalised ONCE here, after the task's last addition.
+template <class P, bool PIPELINED = false>
+LURK_HD void msm_task_accumulate29_raw(const uint32_t* sorted, uint32_t first, uint32_t last, const Affine<P>* table, Xyzz29<P>& acc, bool& acc_id) {
+    msm_task_accumulate29_loop<P, PIPELINED>(sorted, first, last, table, acc, acc_id);
+    if constexpr (msm_acc_signed<P>()) {
+        if (!acc_id) xyzz29_norm_s<P>(acc);
+    }
 }
 template <class P, bool PIPELINED = false>
 LURK_HD Xyzz<P> msm_task_accumulate29(const uint32_t* sorted, uint32_t first, uint32_t last, const Affine<P>* table) {

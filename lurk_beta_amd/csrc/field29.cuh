@@ -22,6 +22,10 @@
 // drop the nine mads by modulus limb 0: 126 mads per product, 90 per squaring, the same limbs out (gen_field29_asm.py, gen_mul).
 // f29_sqr30 (operand tight) and dot29_finish2 (rows of at most two tight terms) take the same form.  On every other modulus the
 // three are the plain functions.  -DLURK_F29_P1=0 compiles the plain form everywhere (A/B runs).
+//
+// Signed operands (same moduli): f29_mul_s, f29_sqr_s and dot29_row2_s take limbs that are signed 32-bit values.  Contract, stated in
+// full and asserted at "signed operands" below: limbs 0..7 in (-2^29, 2^29) and the top limb in (-2^30, 2^30); every column of a
+// product or a two-term row then has magnitude below 2^63; |a b| < 2^522 gives limbs 0..7 tight, a signed top limb, |t| < 2^261 + p.
 #pragma once
 #include "field.cuh"
 
@@ -234,11 +238,96 @@ LURK_HD F29<P> f29_mul30_portable(const F29<P>& a, const F29<P>& b) {
     }
 }
 
+// ---- signed operands (the moduli of f29_p1_form only): the products of xyzz29_madd_s (curve29.cuh) ------------------------------
+// A limb is an int32 held in the uint32 of F29 (two's complement).  Operand classes:
+//   "s-tight"  limbs 0..7 in [0, 2^29), the top limb signed and keeping the rest: what a signed product, a signed row or
+//              f29_carry_s gives; every unsigned tight value with a top limb below 2^30 is one
+//   "s-diff"   limbs 0..7 in (-2^29, 2^29), top limb signed: the limb-wise difference of two s-tight values, or the limb-wise
+//              negation of one - no bias is added and no carry pass follows
+// and in both the top limb lies in (-2^30, 2^30): |value| < 2^262.  F29S_ASSERT_OPERAND asserts exactly this.
+// Columns: a column of a product holds at most 7 terms below 2^58 and 2 with a top limb below 2^59 (column 16 is top x top alone,
+// below 2^60), a two-term row twice that: with the five reduction terms (m_k < 2^29 times modulus limbs 1..4 and 8) and the carry
+// from the column below, |column| < 22 * 2^58 + 5 * 2^58 + 2^36 < 2^63, which the signed shifts need.  The operand-by-operand
+// products are signed (v_mad_i64_i32), the m_k * modulus limb ones unsigned onto the same 64-bit two's complement accumulator.
+// The form is f29_mul30_portable's: H = A - 1 is carried through the reduction columns; m_k = (-A) mod 2^29 = ~H mod 2^29 and
+// (A + m_k) / 2^29 - 1 = ceil(A / 2^29) - 1 = H >> 29 hold for negative A as well when the shift is arithmetic.
+// Values: t = (a b + m p) / 2^261 with 0 <= m < 2^261, so a b / 2^261 <= t < a b / 2^261 + p; |a b| < 2^522 gives |t| < 2^261 + p
+// and a top limb in [-2^29, 2^29 + 2^22].  The output is s-tight.
+#if F29_CHECKS_ACTIVE
+#define F29S_ASSERT_OPERAND(v, what)                                                                                                   \
+    do {                                                                                                                               \
+        for (int _i = 0; _i < 9; _i++) {                                                                                               \
+            const int64_t _l = (int32_t)(v).l[_i], _b = (int64_t)1 << (_i < 8 ? 29 : 30);                                             \
+            if (_l <= -_b || _l >= _b) { printf("F29 bound violated: %s limb %d = %lld (signed operand class)\n", what, _i, (long long)_l); abort(); } \
+        }                                                                                                                              \
+    } while (0)
+#else
+#define F29S_ASSERT_OPERAND(v, what) ((void)0)
+#endif
+template <class P>
+LURK_HD F29<P> f29_mul_s_portable(const F29<P>& a, const F29<P>& b) {
+    static_assert(f29_p1_form<P>(), "the signed products exist for the moduli that are 1 mod 2^29 only");
+    F29S_ASSERT_OPERAND(a, "f29_mul_s a");
+    F29S_ASSERT_OPERAND(b, "f29_mul_s b");
+    uint32_t m[9];
+    F29<P> t;
+    uint64_t acc = ~(uint64_t)0;  // H = (true accumulator) - 1
+#pragma unroll
+    for (int k = 0; k < 17; k++) {
+#if F29_CHECKS_ACTIVE
+        unsigned __int128 mag = ((unsigned __int128)5 << 58) + ((unsigned __int128)1 << 36);
+        for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) {
+            const int64_t pr = (int64_t)(int32_t)a.l[i] * (int32_t)b.l[k - i];
+            mag += (unsigned __int128)(pr < 0 ? -pr : pr);
+        }
+        F29_ASSERT(mag < ((unsigned __int128)1 << 63), "f29_mul_s column overflow");
+#endif
+#pragma unroll
+        for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) acc += (uint64_t)((int64_t)(int32_t)a.l[i] * (int32_t)b.l[k - i]);
+#pragma unroll
+        for (int i = (k > 8 ? k - 8 : 0); i <= (k - 1 < 8 ? k - 1 : 8); i++) acc += (uint64_t)m[i] * f29_mod<P>(k - i);
+        if (k <= 8) {
+            m[k] = ~(uint32_t)acc & F29_MASK;
+            acc = (uint64_t)((int64_t)acc >> 29);
+            if (k == 8) acc += 1;
+        } else {
+            t.l[k - 9] = (uint32_t)acc & F29_MASK;
+            acc = (uint64_t)((int64_t)acc >> 29);
+        }
+    }
+    F29_ASSERT((int64_t)acc >= -((int64_t)1 << 29) && (int64_t)acc <= ((int64_t)1 << 29) + ((int64_t)1 << 22), "f29_mul_s: |a b| >= 2^522");
+    t.l[8] = (uint32_t)acc;
+    return t;
+}
+template <class P>
+LURK_HD F29<P> f29_sqr_s_portable(const F29<P>& a) {  // (the squaring block issues the cross products once against 2a: the same columns)
+    return f29_mul_s_portable<P>(a, a);
+}
+
 }  // namespace lurk
 #include "field29_mul_asm.cuh"
 #include "field29_mul_asm_bn254fq.cuh"
 #include "field29_mul_asm_p1.cuh"
+#include "field29_mul_asm_p1s.cuh"
 namespace lurk {
+
+// the signed products (contract above); Pasta fields only
+template <class P>
+LURK_HD F29<P> f29_mul_s(const F29<P>& a, const F29<P>& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return f29_mul_s_asm<P>(a, b);
+#else
+    return f29_mul_s_portable<P>(a, b);
+#endif
+}
+template <class P>
+LURK_HD F29<P> f29_sqr_s(const F29<P>& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return f29_sqr_s_asm<P>(a);
+#else
+    return f29_sqr_s_portable<P>(a);
+#endif
+}
 
 // one operand tight and the other loose, or both with limbs < 2^30
 template <class P>
@@ -405,6 +494,56 @@ LURK_HD F29<P> dot29_finish2(const Dot29<P>& A) {
         t.l[8] = (uint32_t)acc;
         return t;
     }
+}
+
+// The two-term row of signed operands (the Y3 row of xyzz29_madd_s): a * b + c * d with ONE reduction, the contract of
+// f29_mul_s_portable (every |column| < 2^63, asserted; |a b + c d| < 2^522 gives an s-tight t with |t| < 2^261 + p).  Compiled
+// from this text on the device too: the signed 32 x 32 + 64 products become v_mad_i64_i32, 162 + 45 mads.
+template <class P>
+LURK_HD F29<P> dot29_row2_s(const F29<P>& a, const F29<P>& b, const F29<P>& c, const F29<P>& d) {
+    static_assert(f29_p1_form<P>(), "the signed row exists for the moduli that are 1 mod 2^29 only");
+    F29S_ASSERT_OPERAND(a, "dot29_row2_s a");
+    F29S_ASSERT_OPERAND(b, "dot29_row2_s b");
+    F29S_ASSERT_OPERAND(c, "dot29_row2_s c");
+    F29S_ASSERT_OPERAND(d, "dot29_row2_s d");
+    uint64_t col[17];
+#pragma unroll
+    for (int k = 0; k < 17; k++) col[k] = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+#pragma unroll
+        for (int j = 0; j < 9; j++)
+            col[i + j] += (uint64_t)((int64_t)(int32_t)a.l[i] * (int32_t)b.l[j]) + (uint64_t)((int64_t)(int32_t)c.l[i] * (int32_t)d.l[j]);
+#if F29_CHECKS_ACTIVE
+    for (int k = 0; k < 17; k++) {
+        unsigned __int128 mag = ((unsigned __int128)5 << 58) + ((unsigned __int128)1 << 36);
+        for (int i = (k > 8 ? k - 8 : 0); i <= (k < 8 ? k : 8); i++) {
+            const int64_t p1 = (int64_t)(int32_t)a.l[i] * (int32_t)b.l[k - i], p2 = (int64_t)(int32_t)c.l[i] * (int32_t)d.l[k - i];
+            mag += (unsigned __int128)(p1 < 0 ? -p1 : p1) + (unsigned __int128)(p2 < 0 ? -p2 : p2);
+        }
+        F29_ASSERT(mag < ((unsigned __int128)1 << 63), "dot29_row2_s column overflow");
+    }
+#endif
+    uint32_t m[9];
+    F29<P> t;
+    uint64_t acc = ~(uint64_t)0;  // H = (true accumulator) - 1
+#pragma unroll
+    for (int k = 0; k < 17; k++) {
+        acc += col[k];
+#pragma unroll
+        for (int i = (k > 8 ? k - 8 : 0); i <= (k - 1 < 8 ? k - 1 : 8); i++) acc += (uint64_t)m[i] * f29_mod<P>(k - i);
+        if (k <= 8) {
+            m[k] = ~(uint32_t)acc & F29_MASK;
+            acc = (uint64_t)((int64_t)acc >> 29);
+            if (k == 8) acc += 1;
+        } else {
+            t.l[k - 9] = (uint32_t)acc & F29_MASK;
+            acc = (uint64_t)((int64_t)acc >> 29);
+        }
+    }
+    F29_ASSERT((int64_t)acc >= -((int64_t)1 << 29) && (int64_t)acc <= ((int64_t)1 << 29) + ((int64_t)1 << 22), "dot29_row2_s: |a b + c d| >= 2^522");
+    t.l[8] = (uint32_t)acc;
+    return t;
 }
 
 // 8 x 32 Montgomery(2^256) -> 9 x 29 Montgomery(2^261): value * 32, i.e. limbs of (x << 5); tight.

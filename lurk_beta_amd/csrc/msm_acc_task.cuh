@@ -1,5 +1,5 @@
 // msm_acc_task.cuh - the body both forms of the bucket accumulation run per task (msm_acc.hip: the plain launch; msm_acc_persistent.hip:
-// the persistent form).  One definition of the additions: both forms run the same sequence of xyzz29_madd calls on the same arguments and
+// the persistent form).  One definition of the additions: both forms run the same sequence of mixed additions (xyzz29_madd_task) on the same arguments and
 // give bit-identical task sums.  They differ in ONE compile-time choice, PIPELINED, which only moves loads: the persistent form
 // launched with one wave per SIMD (nothing to cover a wait) gathers the next table record under the current addition; the plain launch
 // (three waves per SIMD, no registers to spare) and the persistent form at two or more waves per SIMD do not - see
@@ -28,7 +28,7 @@ __device__ LURK_ACC_TASK_ATTR void msm_accumulate_task(uint32_t i, const uint32_
     uint2 ti = task_info[t];
     // The task's sum leaves as it stands, a record on the radix-2^29 layer (no conversion to the 8 x 32 form: finalize and the bucket
     // reduction work on records), at the slot the plan chose: the bucket's own when the bucket is this one task.  What is stored is
-    // R-bounded - tight limbs, value < 2^259, the loop invariant of msm_task_accumulate29_raw - as xyzz29_add requires of its inputs
+    // R-bounded - tight limbs, value < 2^259, what msm_task_accumulate29_raw leaves (the signed loop normalises its sum once, at the end) - as xyzz29_add requires of its inputs
     // (plane_store asserts it under LURK_F29_CHECK).
     Xyzz29<P> acc;
     bool acc_id;
