@@ -72,7 +72,8 @@ const char* lurk_hip_version(void);
  * two at start-up).  A revision that only adds entry points raises the number too: a binding built against revision n runs on any library
  * that reports >= n until a revision says otherwise.  4: the verifiers - lurk_hip_r1cs_sparse_mle_dev, lurk_hip_ipa_s_vector_dev,
  * lurk_hip_sumcheck_verify, lurk_hip_ipa_verify_dev, lurk_hip_spartan_verify_dev, lurk_hip_spartan_verify_batch_dev (additions only);
- * later additions under the same number (a binding probes for them by symbol): lurk_hip_r1cs_transpose_dev, lurk_hip_r1cs_read.
+ * later additions under the same number (a binding probes for them by symbol): lurk_hip_r1cs_transpose_dev, lurk_hip_r1cs_read,
+ * lurk_hip_grid_cus.
  * 3: lurk_hip_slot_constraints_size / lurk_hip_slot_constraints,
  * lurk_hip_frames_r1cs_create, lurk_hip_r1cs_is_sat_dev (additions only).  2 (round 6): lurk_hip_msm_ctx_info's *precomputed is a boolean (the key's form comes from lurk_hip_msm_ctx_form),
  * LURK_MSM_SLOTS is 6, LURK_MSM_SUBMIT_FOLLOW, the parameter blocks lurk_hip_ro_params / lurk_hip_ck_params, lurk_hip_scratch_trim.
@@ -91,6 +92,11 @@ int lurk_hip_abi_version(void);
 int lurk_hip_scratch_trim(size_t* released_bytes);
 /* bind the calling thread to a device (one process per GPU; the multi-GPU layer calls this) */
 int lurk_hip_set_device(int device);
+/* The CU count the capped grids of the vector kernels (sum-check, inner-product argument, HyperKZG, Poseidon batches) are computed from:
+ * the current device's, or LURK_GRID_CUS from the environment (a test switch, read once per process: a small value sends short inputs
+ * through the second pass of every grid-stride loop; results do not depend on it).  Host-side: no device is touched (256 is reported
+ * until a device call has read the device's count). */
+int lurk_hip_grid_cus(int* out);
 /* per-kernel timing with HIP events on the launch stream (bench.py's roofline leg) */
 int lurk_hip_profile_enable(int on);
 int lurk_hip_profile_reset(void);

@@ -54,6 +54,7 @@ SIGNATURES = {
     "lurk_hip_version": (ctypes.c_char_p, []),
     "lurk_hip_abi_version": (c_int, []),
     "lurk_hip_scratch_trim": (c_int, [ctypes.POINTER(c_size_t)]),
+    "lurk_hip_grid_cus": (c_int, [ctypes.POINTER(c_int)]),
     "lurk_hip_set_device": (c_int, [c_int]),
     "lurk_hip_profile_enable": (c_int, [c_int]),
     "lurk_hip_profile_reset": (c_int, []),

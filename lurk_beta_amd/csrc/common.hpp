@@ -288,6 +288,9 @@ inline void require_pasta_curve(int curve, const char* what) {
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 int num_cus();  // multiprocessor count of the current device
+// Workgroups a capped launch may start: per_cu for every CU of the current device (LURK_GRID_CUS in the environment puts another CU
+// count in its place); a buffer of workgroup partials and the launch that fills it take their size from the same call.
+unsigned grid_cap(unsigned per_cu);
 // The current device's stream-ordered memory pool keeps up to 4 GiB of freed blocks instead of handing them back to the driver at the
 // next synchronisation (the default release threshold is 0): the provers take their scratch from it (hipMallocAsync) dozens of times per
 // proof with synchronisations in between - a proof of a 2^20-row instance spent ~5 ms re-allocating.  Once per device, cheap afterwards.

@@ -251,7 +251,7 @@ __global__ __launch_bounds__(HK_BLOCK) void hk_div_fix_kernel(size_t len, HkRoot
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 static unsigned hk_grid(size_t work) {
-    unsigned blocks = work ? div_up(work, HK_BLOCK) : 1, cap = (unsigned)num_cus() * 16;
+    unsigned blocks = work ? div_up(work, HK_BLOCK) : 1, cap = grid_cap(16);
     return blocks > cap ? cap : blocks;
 }
 

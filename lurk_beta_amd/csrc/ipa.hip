@@ -162,7 +162,7 @@ static int top_bit_of(const Scalar256& a, const Scalar256& b) {
 
 template <class F>
 static void inner_product(const void* d_a, const void* d_b, size_t n, void* out32, hipStream_t s) {
-    unsigned blocks = n ? div_up(n, IPA_BLOCK) : 1, cap = (unsigned)num_cus() * 8;
+    unsigned blocks = n ? div_up(n, IPA_BLOCK) : 1, cap = grid_cap(8);
     if (blocks > cap) blocks = cap;
     ArenaBuf partial_buf((size_t)blocks * 32, s);
     Fe<F>* partial = (Fe<F>*)partial_buf.p;
@@ -190,7 +190,7 @@ static void fold_halves(void* d_v, size_t len, const void* lo32, const void* hi3
     Fe<F> a, b;
     memcpy(a.l, lo32, 32);
     memcpy(b.l, hi32, 32);
-    unsigned blocks = div_up(h, IPA_BLOCK), cap = (unsigned)num_cus() * 16;
+    unsigned blocks = div_up(h, IPA_BLOCK), cap = grid_cap(16);
     if (blocks > cap) blocks = cap;
     ProfScope ps("ipa_fold_halves", s);
     hipLaunchKernelGGL((fold_halves_kernel<F>), dim3(blocks), dim3(IPA_BLOCK), 0, s, (Fe<F>*)d_v, h, a, b);
@@ -199,7 +199,7 @@ static void fold_halves(void* d_v, size_t len, const void* lo32, const void* hi3
 
 template <class F>
 static void ipa_round_scalars(const void* d_a, size_t m, const void* d_coef, size_t n, void* d_l, void* d_r, hipStream_t s) {
-    unsigned blocks = div_up(n, IPA_BLOCK), cap = (unsigned)num_cus() * 16;
+    unsigned blocks = div_up(n, IPA_BLOCK), cap = grid_cap(16);
     if (blocks > cap) blocks = cap;
     ProfScope ps("ipa_round_scalars", s);
     hipLaunchKernelGGL((ipa_round_scalars_kernel<F>), dim3(blocks), dim3(IPA_BLOCK), 0, s, (const Fe<F>*)d_a, m, (const Fe<F>*)d_coef, n, (Fe<F>*)d_l,
@@ -211,7 +211,7 @@ static void ipa_coef_fold(void* d_coef, size_t n, size_t m, const void* lo32, co
     Fe<F> a, b;
     memcpy(a.l, lo32, 32);
     memcpy(b.l, hi32, 32);
-    unsigned blocks = div_up(n, IPA_BLOCK), cap = (unsigned)num_cus() * 16;
+    unsigned blocks = div_up(n, IPA_BLOCK), cap = grid_cap(16);
     if (blocks > cap) blocks = cap;
     ProfScope ps("ipa_coef_fold", s);
     hipLaunchKernelGGL((ipa_coef_fold_kernel<F>), dim3(blocks), dim3(IPA_BLOCK), 0, s, (Fe<F>*)d_coef, n, m, a, b);
@@ -385,7 +385,7 @@ static void ipa_prove_resident(lurk_hip_msm_ctx* key, int curve, int field_id, v
     stream_pool_retain();
     // stream-ordered scratch (the pool keeps it between calls: a proof opens several of these arguments)
     using Scratch = ArenaBuf;  // the stream's scratch arena (common.hpp)
-    const unsigned max_blocks = (unsigned)num_cus() * 8;
+    const unsigned max_blocks = grid_cap(8);
     Scratch coef(n0 * 32, s), dl(n0 * 32, s), dr(pairs ? 0 : n0 * 32, s), partial((size_t)2 * max_blocks * 32, s);
     {
         unsigned blocks = div_up(n0, IPA_BLOCK);

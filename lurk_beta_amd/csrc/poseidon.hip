@@ -468,7 +468,7 @@ static void launch_batch(const void* d_pre, void* d_out, size_t n, PoseidonConst
     }
     allow_dynamic_lds((const void*)kern, (int)lds_bytes);
     unsigned blocks = div_up(n, POSEIDON_BLOCK);
-    unsigned cap = (unsigned)num_cus() * 2;  // 2 workgroups (8 waves) per CU, grid-stride beyond
+    unsigned cap = grid_cap(2);  // 2 workgroups (8 waves) per CU, grid-stride beyond
     if (blocks > cap) blocks = cap;
     ProfScope ps("poseidon_batch", s);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(POSEIDON_BLOCK), lds_bytes, s, (const uint4*)d_pre, (uint4*)d_out, n, img, img_vec4,
@@ -508,7 +508,7 @@ static void launch_trace(const void* d_pre, size_t n, PoseidonConsts& pc, int fl
     } else {
         auto kern = poseidon_trace_batch_kernel<P, T>;
         allow_dynamic_lds((const void*)kern, (int)lds_bytes);
-        unsigned blocks = div_up(n, POSEIDON_BLOCK), cap = (unsigned)num_cus() * 2;
+        unsigned blocks = div_up(n, POSEIDON_BLOCK), cap = grid_cap(2);
         if (blocks > cap) blocks = cap;
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(POSEIDON_BLOCK), lds_bytes, s, (const uint4*)d_pre, n, img, img_vec4, pc.rf, pc.rp, flags, dst);
     }

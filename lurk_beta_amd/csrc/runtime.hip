@@ -1,4 +1,6 @@
 // runtime.hip - error state, device checks, profiler, misc C-ABI entry points.
+#include <cstdlib>
+
 #include "common.hpp"
 
 namespace lurk {
@@ -47,6 +49,21 @@ void require_device() {
 }
 
 int num_cus() { return g_num_cus > 0 ? g_num_cus : 256; }
+
+// LURK_GRID_CUS=<n >= 1>: the CU count the capped grids assume, instead of the device's (a test switch: with 1 the grid-stride loops,
+// the partial sums and the last-workgroup reductions behind the caps take a second pass at a few thousand elements; results must not
+// depend on it).  Read once per process, on first use; anything else in it is ignored.
+static unsigned grid_cus() {
+    static const long forced = [] {
+        const char* e = getenv("LURK_GRID_CUS");
+        if (!e || !*e) return 0L;
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        return *end == 0 && v >= 1 && v <= (1L << 20) ? v : 0L;
+    }();
+    return forced ? (unsigned)forced : (unsigned)num_cus();
+}
+unsigned grid_cap(unsigned per_cu) { return grid_cus() * per_cu; }
 
 int current_device() {
     int dev = 0;
@@ -323,6 +340,13 @@ int lurk_hip_scratch_trim(size_t* released_bytes) {
     return guarded([&] {
         const size_t n = ScratchArena::trim_all();
         if (released_bytes) *released_bytes = n;
+    });
+}
+
+int lurk_hip_grid_cus(int* out) {
+    return host_guarded([&] {
+        LURK_REQUIRE(out, "null argument");
+        *out = (int)grid_cap(1);
     });
 }
 

@@ -168,7 +168,7 @@ struct SumcheckScratch {
     hipStream_t s = nullptr;
     explicit SumcheckScratch(hipStream_t s_) : s(s_) {
         stream_pool_retain();
-        const size_t cap = (size_t)num_cus() * 8;
+        const size_t cap = grid_cap(8);
         LURK_HIP_CHECK(hipMallocAsync(&partial, cap * 3 * 32 + 256, s));
         counter = (uint32_t*)((char*)partial + cap * 3 * 32);
         LURK_HIP_CHECK(hipMemsetAsync(counter, 0, 4, s));
@@ -211,7 +211,7 @@ static void sumcheck_round(int np, void* const* d_polys, size_t len, const void*
     const bool bind = r32_mont != nullptr;
     const size_t work = bind ? len / 4 : len / 2;
     unsigned blocks = work ? div_up(work, SC_BLOCK) : 1;
-    const unsigned cap = (unsigned)num_cus() * 8;
+    const unsigned cap = grid_cap(8);
     if (blocks > cap) blocks = cap;
     const int nv = np == 4 ? 3 : 2;
     Fe<F> r = fe_zero<F>();
@@ -423,7 +423,7 @@ int lurk_hip_eq_evals_dev(int field_id, const void* r32_mont, int ell, void* d_o
         if (ell) LURK_HIP_CHECK(hipMemcpyAsync(d_r, r32_mont, (size_t)ell * 32, hipMemcpyHostToDevice, s));
         const size_t n = (size_t)1 << ell;
         const int lo = ell < EQ_LO_BITS ? ell : EQ_LO_BITS;
-        unsigned blocks = (unsigned)(n >> lo), cap = (unsigned)num_cus() * 4;  // one chunk of 2^lo outputs per workgroup and pass
+        unsigned blocks = (unsigned)(n >> lo), cap = grid_cap(4);  // one chunk of 2^lo outputs per workgroup and pass
         if (blocks > cap) blocks = cap;
         const size_t lds = ((size_t)1 << lo) * 32;
         ProfScope ps("eq_evals", s);

@@ -305,7 +305,7 @@ static void ipa_s_vector(const std::vector<Fe<F>>& r, const std::vector<Fe<F>>& 
     LURK_HIP_CHECK(hipMemcpyAsync(d_tab.p, tab.data(), (nlo + nhi) * 32, hipMemcpyHostToDevice, s));
     LURK_HIP_CHECK(hipStreamSynchronize(s));  // (pageable source: the table leaves this frame)
     ProfScope ps("ipa_s_vector", s);
-    const unsigned grid = std::max(1u, std::min(div_up(n, FOLD_BLOCK), (unsigned)num_cus() * 8u));
+    const unsigned grid = std::max(1u, std::min(div_up(n, FOLD_BLOCK), grid_cap(8)));
     hipLaunchKernelGGL((ipa_s_vector_kernel<F>), dim3(grid), dim3(FOLD_BLOCK), 0, s, (const Fe<F>*)d_tab.p, lo_bits, n, (Fe<F>*)d_out);
     LURK_HIP_CHECK(hipGetLastError());
 }

@@ -21,11 +21,39 @@ def test_every_declared_symbol_is_exported_and_bound():
     lib = _lib.load()
     declared = _declared_symbols()
     assert len(declared) >= 20
+    assert "lurk_hip_grid_cus" in declared  # the getter behind LURK_GRID_CUS (tests/test_gpu_grid_caps.py relies on it)
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/lurk_hip.h but not exported"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature"
     for name in _lib.SIGNATURES:
         assert name in declared, f"{name} bound but not declared in the header"
+
+
+def test_grid_cus_switch_is_parsed_without_a_gpu():
+    """LURK_GRID_CUS: an integer >= 1 replaces the CU count the capped grids are computed from, anything
+    else is ignored; the variable is read once per process, so every setting gets an interpreter of its own.  lurk_hip_grid_cus is a
+    host-side getter: no device is needed (before a device call has read the device's count the library assumes 256)."""
+    import subprocess
+    import sys
+
+    from lurk_beta_amd import _lib
+
+    child = ("import ctypes, sys\nlib = ctypes.CDLL(sys.argv[1])\no = ctypes.c_int(-1)\nassert lib.lurk_hip_grid_cus(ctypes.byref(o)) == 0\n"
+             "assert lib.lurk_hip_grid_cus(None) != 0\nprint(o.value)\n")
+
+    def cus(setting):
+        env = {k: v for k, v in os.environ.items() if k != "LURK_GRID_CUS"}
+        if setting is not None:
+            env["LURK_GRID_CUS"] = setting
+        r = subprocess.run([sys.executable, "-c", child, _lib.LIB_PATH], env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-800:]
+        return int(r.stdout)
+
+    default = cus(None)
+    assert default == 256
+    assert cus("1") == 1 and cus("7") == 7 and cus("304") == 304
+    for ignored in ("", "0", "-3", "abc", "12 ", "1.5", "0x10"):
+        assert cus(ignored) == default, ignored
 
 
 def test_host_side_constants_match_oracle_without_a_gpu():
