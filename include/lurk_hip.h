@@ -218,6 +218,27 @@ int lurk_hip_msm_ctx_wait(lurk_hip_msm_ctx* ctx, int slot, void* out_jacobian96)
 int lurk_hip_msm_ctx_submit_pair_dev(lurk_hip_msm_ctx* ctx, int slot, const void* d_scalars32, size_t nscalars, int is_mont, void* stream,
                                      int sel_bit);
 int lurk_hip_msm_ctx_wait_pair(lurk_hip_msm_ctx* ctx, int slot, void* out_lo_jacobian96, void* out_hi_jacobian96);
+/* A BATCH of short commitments under prefixes of the resident key in one pass (the folded polynomials of a HyperKZG opening:
+ * hyperkzg.hip):
+ *     out[k] = sum_{i < lens[k]} d_scalars32[offsets[k] + i] * bases[i],   k < count
+ * - every vector commits to the FIRST lens[k] bases, as lurk_hip_msm_ctx_run does.  `offsets` and `lens` are HOST arrays, in elements of
+ * 32 B; they are read during the call and not kept.  Vectors may overlap and come in any order; lens[k] == 0 gives the identity.
+ * Window-table keys only, as for the pair (all four curves).  A batch takes one of the LURK_MSM_SLOTS slots and is ordered after
+ * `stream`, like lurk_hip_msm_ctx_submit_dev; its workspaces are allocated on first use and grow on demand (an allocation failure
+ * returns LURK_HIP_ERR_OOM and leaves the slot free).  wait_batch blocks and writes count x 96 B to host memory: for each vector the
+ * normalised representative lurk_hip_msm_ctx_wait writes (Z = 1 in Montgomery form, or z = 0 for the identity), so a batch result is
+ * byte for byte what lurk_hip_msm_ctx_run_dev gives for that vector.
+ * Refused with LURK_HIP_ERR_INVALID_ARG before anything is allocated or launched, the message naming which: a NULL ctx, offsets, lens
+ * or output; NULL scalars when some length is non-zero; count == 0 or above LURK_MSM_BATCH_MAX_VECTORS; a length above
+ * LURK_MSM_BATCH_MAX_LEN or above the key's points; a total above LURK_MSM_BATCH_MAX_TOTAL; a key that is not in the window-table form;
+ * a slot out of range or still pending; wait_batch on a slot that holds an ordinary or pair commitment, and lurk_hip_msm_ctx_wait /
+ * _wait_pair on a slot that holds a batch (the pending commitment stays pending). */
+#define LURK_MSM_BATCH_MAX_VECTORS 64
+#define LURK_MSM_BATCH_MAX_LEN ((size_t)1 << 16)   /* scalars per vector */
+#define LURK_MSM_BATCH_MAX_TOTAL ((size_t)1 << 20) /* scalars per batch  */
+int lurk_hip_msm_ctx_submit_batch_dev(lurk_hip_msm_ctx* ctx, int slot, const void* d_scalars32, const size_t* offsets, const size_t* lens,
+                                      size_t count, int is_mont, void* stream);
+int lurk_hip_msm_ctx_wait_batch(lurk_hip_msm_ctx* ctx, int slot, void* out_jacobian96);
 int lurk_hip_msm_ctx_destroy(lurk_hip_msm_ctx* ctx);
 /* Points the context at other device-resident bases (borrowed, plain key) and keeps its workspaces: a key that changes every
  * round (the folded key of the inner-product argument) without re-allocation. */

@@ -30,6 +30,7 @@ constexpr int HK_EVAL_SEG = 4096;    // least coefficients per workgroup of the 
 constexpr int HK_EVAL_MAX_SEGS = 256;  // most workgroups per polynomial (the last workgroup adds their partial sums lane by lane)
 constexpr int HK_DIV_E = 4;          // coefficients per lane of the division's local pass
 constexpr int HK_DIV_TILE = HK_BLOCK * HK_DIV_E;  // ... and per workgroup
+constexpr int HK_BATCH_DEFAULT = 1;  // LURK_HYPERKZG_BATCH when the environment does not say: measured, DESIGN.md section 3.7.2
 
 // a^e by square-and-multiply from the top set bit (e = 0 -> 1)
 template <class F>
@@ -343,6 +344,20 @@ static void hk_div_linear(const void* d_b, size_t len, const Fe<F>* roots, int n
     LURK_HIP_CHECK(hipGetLastError());
 }
 
+// LURK_HYPERKZG_BATCH (1 / 0): the short commitments of stage 0 as one batch, or every one a submit of its own.  Read at EACH call, so
+// that one process can prove both ways.  The default is what the measurement of DESIGN.md section 3.7.2 decided.
+static bool hk_batch_enabled() {
+    const char* v = getenv("LURK_HYPERKZG_BATCH");
+    return v ? atoi(v) != 0 : HK_BATCH_DEFAULT != 0;
+}
+// LURK_HYPERKZG_BATCH_MAX_LEN: the longest polynomial that goes with the batch, at most (and by default) LURK_MSM_BATCH_MAX_LEN.  An
+// internal knob, read at each call: with it a 2^10 opening has some commitments of their own and some batched, as a 2^20 one does.
+static size_t hk_batch_max_len() {
+    const char* v = getenv("LURK_HYPERKZG_BATCH_MAX_LEN");
+    const long long x = v ? atoll(v) : 0;
+    return x > 0 && (size_t)x < LURK_MSM_BATCH_MAX_LEN ? (size_t)x : LURK_MSM_BATCH_MAX_LEN;
+}
+
 // ---- the prover ------------------------------------------------------------------------------------------------------------------------
 // Commitments stay in flight through the key's async slots: com_{i+1} is submitted behind fold i and accumulates while fold i + 1 (and
 // the ones after it) run on the caller's stream; a slot is waited for only when the loop comes round to it again.  The three W_t take
@@ -359,13 +374,31 @@ static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, 
     struct Drain {
         lurk_hip_msm_ctx* key;
         long pending[LURK_MSM_SLOTS];
+        int batch_slot;  // >= 0: a batch is pending on this slot
         ~Drain() {
             uint64_t sink[12];
             for (int k = 0; k < LURK_MSM_SLOTS; k++)
                 if (pending[k] >= 0) (void)lurk_hip_msm_ctx_wait(key, k, sink);
+            if (batch_slot >= 0) {
+                std::vector<uint64_t> many((size_t)12 * LURK_MSM_BATCH_MAX_VECTORS);
+                (void)lurk_hip_msm_ctx_wait_batch(key, batch_slot, many.data());
+            }
         }
-    } drain{key, {}};
+    } drain{key, {}, -1};
     for (int k = 0; k < LURK_MSM_SLOTS; k++) drain.pending[k] = -1;
+    // The short polynomials P_{first_short} .. P_{ell-1} (at most hk_batch_max_len() scalars each) leave as ONE batch behind the last fold
+    // (lurk_hip_msm_ctx_submit_batch_dev: msm_batch.hip) on the last slot; the longer ones keep their per-slot submits on the others.  Off
+    // (LURK_HYPERKZG_BATCH=0), under a key that is not in the window-table form, or with fewer than two short polynomials: every
+    // commitment a submit of its own, over all slots.  The proof's bytes are the same either way.
+    int first_short = ell;  // P_i, i >= first_short, are batched
+    if (hk_batch_enabled() && msm_ctx_table_view(key).form == LURK_MSM_FORM_TABLE) {
+        const size_t cap = hk_batch_max_len();
+        int i = 1;
+        while (i < ell && (n >> i) > cap) i++;
+        if (ell - i >= 2 && ell - i <= LURK_MSM_BATCH_MAX_VECTORS) first_short = i;
+    }
+    const bool batched = first_short < ell;
+    const int nslots = batched ? LURK_MSM_SLOTS - 1 : LURK_MSM_SLOTS, batch_slot = LURK_MSM_SLOTS - 1;
     // folds and commitments
     const Fe<F>* cur = (const Fe<F>*)d_poly;
     size_t len = n;
@@ -373,7 +406,9 @@ static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, 
         Fe<F>* nxt = d_rest + (n - 2 * (n >> (i + 1)));
         hk_fold_pairs<F>(cur, len, x[ell - 1 - i], nxt, s);
         len /= 2;
-        const int slot = i % LURK_MSM_SLOTS;
+        cur = nxt;
+        if (i + 1 >= first_short) continue;  // P_{i+1} goes with the batch
+        const int slot = i % nslots;
         if (drain.pending[slot] >= 0) {
             const long which = drain.pending[slot];
             drain.pending[slot] = -1;
@@ -381,7 +416,15 @@ static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, 
         }
         nested_ok(lurk_hip_msm_ctx_submit_dev(key, slot, nxt, len, 1, (void*)s));
         drain.pending[slot] = i;
-        cur = nxt;
+    }
+    if (batched) {
+        size_t off[LURK_MSM_BATCH_MAX_VECTORS], ln[LURK_MSM_BATCH_MAX_VECTORS];
+        for (int i = first_short; i < ell; i++) {
+            off[i - first_short] = n - 2 * (n >> i);
+            ln[i - first_short] = n >> i;
+        }
+        nested_ok(lurk_hip_msm_ctx_submit_batch_dev(key, batch_slot, d_rest, off, ln, (size_t)(ell - first_short), 1, (void*)s));
+        drain.batch_slot = batch_slot;
     }
     Fe<F> tail[2];
     LURK_HIP_CHECK(hipMemcpyAsync(tail, cur, 64, hipMemcpyDeviceToHost, s));
@@ -393,6 +436,10 @@ static void hyperkzg_prove(lurk_hip_msm_ctx* key, const void* d_poly, size_t n, 
         const long which = drain.pending[k];
         drain.pending[k] = -1;
         nested_ok(lurk_hip_msm_ctx_wait(key, k, out_com + 12 * which));
+    }
+    if (drain.batch_slot >= 0) {
+        drain.batch_slot = -1;
+        nested_ok(lurk_hip_msm_ctx_wait_batch(key, batch_slot, out_com + 12 * (size_t)(first_short - 1)));
     }
     // stage 0: r from the commitments
     uint64_t ch[4] = {0, 0, 0, 0};

@@ -21,6 +21,7 @@
 // bound by the integer VALU (v_mad_u64_u32 issue), not by HBM.
 #include "common.hpp"
 #include "dispatch.hpp"
+#include "msm_batch.hpp"
 #include "msm_core.cuh"
 #include "msm_ctx.hpp"
 #include "msm_launch_plan.hpp"
@@ -59,6 +60,8 @@ struct MsmCtx : MsmCtxBase {
         DevBuf cursor;                     // task cursor of the persistent accumulate kernel (+ its per-CU placement counters)
         bool placement_valid = false;
         int sel = -1;                      // the PENDING commitment is a pair split by this bit of the scalar index: set by submit_impl, cleared by wait_pair, never touched by a synchronous call
+        MsmBatchWork batch_ws;             // the buffers of the slot's batches (msm_batch.hip), made by the first one
+        bool batch = false;                // the PENDING commitment is a batch (submit_batch): wait_batch alone takes it
         bool small_ready = false;          // the small path's buffers exist and its arrival counter is zero
         hipStream_t pending_stream = nullptr;  // the stream the pending commitment ends on
         bool pending = false;
@@ -524,6 +527,7 @@ struct MsmCtx : MsmCtxBase {
         LURK_REQUIRE(slot >= 0 && slot < MSM_SLOTS, "slot out of range");
         Work& wk = work[slot];
         std::lock_guard<std::mutex> lk(wk.mu);
+        LURK_REQUIRE(!(wk.pending && wk.batch), "a batch is pending on this slot: use lurk_hip_msm_ctx_wait_batch");
         LURK_REQUIRE(wk.pending && wk.sel >= 0, "no pair was submitted on this slot");
         wk.pending = false;
         LURK_HIP_CHECK(hipStreamSynchronize(wk.pending_stream ? wk.pending_stream : wk.stream));
@@ -534,6 +538,47 @@ struct MsmCtx : MsmCtxBase {
             else put_point(outs[g], jacobian_from_affine<P>(xyzz_to_affine<P>(t)));
         }
         wk.sel = -1;
+    }
+    // a batch of short commitments in one pass (msm_batch.hip).  Every refusal comes before the first allocation or launch
+    void submit_batch(int slot, const void* d_scalars, const size_t* offsets, const size_t* lens, size_t count, int is_mont, hipStream_t after) override {
+        LURK_REQUIRE(precomputed && !small, "batch: a batch of commitments in one pass needs the window-table form of a key (precompute flag, more than 2^16 "
+                                            "points or a window-bit override)");
+        MsmBatchPlan pl;
+        // LURK_MSM_BATCH_PLANNED (0 / 1; read at each call): the DIRECT or the planned accumulation whatever the size, for A/B runs and tests
+        const char* form_env = getenv("LURK_MSM_BATCH_PLANNED");
+        if (const char* why = msm_batch_plan_make(pl, c, npoints, offsets, lens, count, form_env ? (atoi(form_env) != 0 ? 1 : 0) : -1)) LURK_REQUIRE(false, why);
+        LURK_REQUIRE(slot >= 0 && slot < MSM_SLOTS, "batch: slot out of range");
+        Work& wk = work[slot];
+        std::lock_guard<std::mutex> lk(wk.mu);
+        LURK_REQUIRE(!wk.pending, "batch: slot is busy: wait for it first");
+        ensure_streams(wk);
+        if (pl.total) {
+            LURK_HIP_CHECK(hipEventRecord(wk.ready, after));
+            LURK_HIP_CHECK(hipStreamWaitEvent(wk.stream, wk.ready, 0));
+            msm_batch_enqueue<P, SF>(wk.batch_ws, pl, d_scalars, is_mont, table, npoints, wk.stream);
+        }
+        wk.batch_ws.plan = pl;
+        wk.pending_stream = wk.stream;
+        wk.sel = -1;
+        wk.batch = true;
+        wk.pending = true;
+        wk.pending_n = pl.total;
+    }
+    void wait_batch(int slot, void* out_jac96_host) override {
+        LURK_REQUIRE(slot >= 0 && slot < MSM_SLOTS, "batch: slot out of range");
+        Work& wk = work[slot];
+        std::lock_guard<std::mutex> lk(wk.mu);
+        LURK_REQUIRE(wk.pending, "batch: nothing was submitted on this slot");
+        LURK_REQUIRE(wk.batch, "batch: the commitment pending on this slot is not a batch: use lurk_hip_msm_ctx_wait or lurk_hip_msm_ctx_wait_pair");
+        wk.pending = false;
+        wk.batch = false;
+        const MsmBatchPlan& pl = wk.batch_ws.plan;
+        if (pl.total) LURK_HIP_CHECK(hipStreamSynchronize(wk.stream));
+        for (uint32_t k = 0; k < pl.segs.count; k++) {
+            void* out = (char*)out_jac96_host + (size_t)k * sizeof(Jacobian<P>);
+            if (msm_batch_len(pl, k) == 0) put_identity(out);
+            else put_point(out, jacobian_from_affine<P>(xyzz_to_affine<P>(msm_batch_host_point<P>(wk.batch_ws, pl, k))));
+        }
     }
     void submit(int slot, const void* d_scalars, size_t n, int is_mont, hipStream_t after, int mode) override {
         submit_impl(slot, d_scalars, n, is_mont, after, mode, -1);
@@ -613,6 +658,7 @@ struct MsmCtx : MsmCtxBase {
         Work& wk = work[slot];
         std::lock_guard<std::mutex> lk(wk.mu);
         LURK_REQUIRE(wk.pending, "nothing was submitted on this slot");
+        LURK_REQUIRE(!wk.batch, "a batch is pending on this slot: use lurk_hip_msm_ctx_wait_batch");
         LURK_REQUIRE(wk.sel < 0, "a pair is pending on this slot: use lurk_hip_msm_ctx_wait_pair");
         void* out = out_jac96_host;
         wk.pending = false;

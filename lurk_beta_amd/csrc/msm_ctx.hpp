@@ -28,6 +28,9 @@ struct MsmCtxBase {
     virtual void submit_pair(int slot, const void* d_scalars, size_t n, int is_mont, hipStream_t after, int sel_bit) = 0;
     // xyzz: the two results as XYZZ points (128 B each), not normalised: no field inversion; otherwise 96-byte Jacobian points with Z = 1
     virtual void wait_pair(int slot, void* out_lo_host, void* out_hi_host, bool xyzz) = 0;
+    // a batch of short commitments under prefixes of the key in one pass (msm_batch.hip); offsets / lens: host arrays, elements of 32 B
+    virtual void submit_batch(int slot, const void* d_scalars, const size_t* offsets, const size_t* lens, size_t count, int is_mont, hipStream_t after) = 0;
+    virtual void wait_batch(int slot, void* out_jac96_host /* count x 96 B */) = 0;
     // pasta-msm's calling convention: everything in host memory, nothing resident (buffers and workspaces are kept for the next call)
     virtual void run_oneshot(const void* bases, const void* scalars, size_t n, int is_mont, void* out_jac96_host) = 0;
     virtual void rebind(const void* d_bases, size_t n) = 0;  // plain key over other (borrowed) device bases, workspaces kept

@@ -196,6 +196,26 @@ class CommitmentKey:
         getattr(self, "_keep", {}).pop(slot, None)
         return lo, hi
 
+    def submit_batch_device(self, slot: int, d_scalars, offsets, lens, is_mont: bool = False, stream=None) -> None:
+        """``len(lens)`` short commitments under prefixes of the key in one pass (``lurk_hip_msm_ctx_submit_batch_dev``): vector k is the
+        ``lens[k]`` scalars at element ``offsets[k]`` of ``d_scalars`` and commits to the first ``lens[k]`` bases.  Window-table keys only;
+        pair with ``wait_batch(slot, len(lens))``."""
+        lib = _lib.load()
+        off = (ctypes.c_size_t * max(1, len(offsets)))(*[int(o) for o in offsets])
+        ln = (ctypes.c_size_t * max(1, len(lens)))(*[int(v) for v in lens])
+        assert len(offsets) == len(lens)
+        self._keep = getattr(self, "_keep", {})
+        self._keep[slot] = d_scalars
+        _lib.check(lib.lurk_hip_msm_ctx_submit_batch_dev(self._ctx, slot, _lib.ptr(d_scalars), off, ln, len(lens), int(is_mont), _lib.ptr(stream)))
+
+    def wait_batch(self, slot: int, count: int) -> np.ndarray:
+        """count x 12 u64: the commitments of the batch submitted on ``slot``, each as ``wait`` writes one."""
+        lib = _lib.load()
+        out = np.zeros((max(1, count), 12), dtype=np.uint64)
+        _lib.check(lib.lurk_hip_msm_ctx_wait_batch(self._ctx, slot, _lib.ptr(out)))
+        getattr(self, "_keep", {}).pop(slot, None)
+        return out[:count]
+
     def close(self):
         if self._ctx:
             _lib.load().lurk_hip_msm_ctx_destroy(self._ctx)

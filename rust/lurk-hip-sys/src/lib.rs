@@ -108,6 +108,29 @@ pub mod pasta_msm {
                     check(unsafe { lurk_hip_msm_ctx_wait(self.0, slot, (&mut out as *mut $m::Point).cast()) })?;
                     Ok(out)
                 }
+                /// `lens.len()` short commitments under prefixes of the key in one pass: vector k is the `lens[k]` scalars at element
+                /// `offsets[k]` of `d_scalars` and commits to the first `lens[k]` bases.  Window-table keys only, at most
+                /// `LURK_MSM_BATCH_MAX_VECTORS` vectors; `wait_batch(slot, lens.len())` on the same slot.
+                ///
+                /// # Safety
+                /// `d_scalars` must point to 32-byte Montgomery scalars in device memory that cover every `offsets[k] + lens[k]` and stay
+                /// valid until `wait_batch`.
+                pub unsafe fn submit_batch(&self, slot: c_int, d_scalars: *const c_void, offsets: &[usize], lens: &[usize], stream: *mut c_void) -> Result<(), Error> {
+                    if offsets.len() != lens.len() {
+                        return Err(Error { code: LURK_HIP_ERR_INVALID_ARG, message: "batch: offsets and lens differ in length".into() });
+                    }
+                    check(lurk_hip_msm_ctx_submit_batch_dev(self.0, slot, d_scalars, offsets.as_ptr(), lens.as_ptr(), lens.len(), 1, stream))
+                }
+                /// The `count` commitments of the batch submitted on `slot`, each the point `wait` gives for that vector.
+                ///
+                /// # Safety
+                /// `count` must be the number of vectors submitted on `slot`: the library writes that many points.
+                pub unsafe fn wait_batch(&self, slot: c_int, count: usize) -> Result<Vec<$m::Point>, Error> {
+                    let mut out = vec![$m::Point::default(); count.max(1)];
+                    check(lurk_hip_msm_ctx_wait_batch(self.0, slot, out.as_mut_ptr().cast()))?;
+                    out.truncate(count);
+                    Ok(out)
+                }
                 /// The key folded by the weights of k inner-product rounds at once (`ck_k[p] = sum_b w_b * ck[b m + p]`, arecibo `ipa_pc`):
                 /// `weights` are Montgomery scalars (a power of two of them, at most 2^12), the `n / weights.len()` affine points land in
                 /// device memory.  Window-table keys only; `lurk_hip_ipa_prove_dev` calls this by itself.
