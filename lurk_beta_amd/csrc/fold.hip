@@ -16,9 +16,10 @@
 // it out; all field elements cross the ABI as 32-byte Montgomery(2^256) values.
 //
 // Kernels: one lane per row (the step circuit's rows hold 3-4 entries; neighbouring lanes read neighbouring
-// CSR records); the few long rows (bit decompositions: ~255 entries) go to a second launch with 16 lanes per row.  A row's inner product is accumulated in 17 unreduced 64-bit columns (poseidon29.cuh: Dot29)
-// and reduced once.  The cross-term kernel runs the six inner products of a row (A, B, C times z1, z2) from one
-// pass over the matrices and finishes T as a four-term lazy row: AZ1*BZ2 + AZ2*BZ1 + (-u1)*CZ2 + (-u2)*CZ1.
+// CSR records); the few long rows (more than FOLD_LONG entries - bit decompositions: ~255) are listed at creation and walked
+// by FOLD_GROUP lanes per row.  The row's inner product and its bounds: r1cs_shape.cuh, r1cs_row.  The cross-term kernel runs
+// the six inner products of a row (A, B, C times z1, z2) from one pass over the matrices and finishes T as a four-term lazy
+// row: AZ1*BZ2 + AZ2*BZ1 + (-u1)*CZ2 + (-u2)*CZ1.
 // Both kernels are bound by the random 32-byte gathers from z (HBM / L2), not by arithmetic.
 #include <memory>
 #include <unordered_map>
@@ -37,144 +38,51 @@ namespace lurk {
 // their loads come back (3: the class of commit(T)'s own short kernels; a followed commitment's tail runs at 2, accumulations at 0-1).
 __device__ __forceinline__ void fold_wave_prio() { __builtin_amdgcn_s_setprio(3); }
 
-constexpr uint32_t FOLD_LONG = 32;  // rows with more entries (in any of A, B, C) go to the wave-per-row kernel
-// Measured in isolation at rc = 100 (bench_tools/fold_bench.py, round 6): a batch of 4 entries keeps 180-200 registers live (two waves
-// per SIMD), a batch of 2 keeps 144 (three waves): 0.227 -> 0.200 ms for the cached-products kernel, 0.323 -> 0.312 for the six-gather
-// one - the kernels are bound by gather latency that only more resident waves hide (1.6 waves per SIMD on average in round 4's counters).
-#ifndef LURK_FOLD_BATCH
-#define LURK_FOLD_BATCH 2
-#endif
 #ifndef LURK_FOLD_MIN_WAVES
 #define LURK_FOLD_MIN_WAVES 1  // (HIP: minimum waves per SIMD the cross-term kernels are compiled for)
 #endif
-constexpr int FOLD_BATCH = LURK_FOLD_BATCH;  // entries whose loads are issued together by one lane
-
-// one lane, one (short) row of one matrix, NV vectors: entries are fetched FOLD_BATCH at a time so that the
-// dependent loads (record -> coefficient, z values) of a batch are in flight together
-template <class P, int NV>
-__device__ __forceinline__ void fold_row_lane(const CsrView& m, const uint32_t* __restrict__ dict, const uint32_t* __restrict__ one29,
-                                              uint32_t lo, uint32_t hi, const Fe<P>* const* z, F29<P>* out) {
-    RowAcc<P> acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; v++) row_init<P>(acc[v]);
-    for (uint32_t k = lo; k < hi; k += FOLD_BATCH) {
-        uint2 e[FOLD_BATCH];
-#pragma unroll
-        for (int u = 0; u < FOLD_BATCH; u++) e[u] = k + u < hi ? m.ent[k + u] : make_uint2(0u, 0u);
-        F29<P> c[FOLD_BATCH];
-        Fe<P> zz[FOLD_BATCH][NV];
-#pragma unroll
-        for (int u = 0; u < FOLD_BATCH; u++) {
-            c[u] = ld_const29<P>(dict + (size_t)e[u].y * P29_STRIDE);
-#pragma unroll
-            for (int v = 0; v < NV; v++) zz[u][v] = z[v][e[u].x];
-        }
-#pragma unroll
-        for (int u = 0; u < FOLD_BATCH; u++)
-            if (k + u < hi) {
-#pragma unroll
-                for (int v = 0; v < NV; v++) row_mac<P>(acc[v], c[u], f29_from_mont256<P>(zz[u][v]), one29);
-            }
-    }
-#pragma unroll
-    for (int v = 0; v < NV; v++) out[v] = dot29_finish<P>(acc[v].acc);
-}
-
-// FOLD_GROUP lanes, one long row of one matrix (64 / FOLD_GROUP rows per wave): lane g of the group runs a RowAcc
-// over the entries lo + g, lo + g + FOLD_GROUP, ... and reduces it; the reduced values are then summed across
-// the group - limb-wise (two butterfly steps between carry passes: 4 x 2^29 < 2^32) while the row is short enough
-// for the sum to stay below 2^261 (<= 256 entries: < 256 * 2^252 + 16 p), otherwise one by one into the group
-// leader's accumulator (times the Montgomery one).  Result valid on the group leader.
-constexpr int FOLD_GROUP = 16;
-
-template <class P, int NV>
-__device__ __forceinline__ void fold_row_wave(const CsrView& m, const uint32_t* __restrict__ dict, const uint32_t* __restrict__ one29,
-                                              uint32_t lo, uint32_t hi, const Fe<P>* const* z, F29<P>* out) {
-    static_assert(NV == 1, "one vector per pass");
-    const uint32_t gl = threadIdx.x & (FOLD_GROUP - 1);
-    RowAcc<P> acc;
-    row_init<P>(acc);
-    for (uint32_t k = lo + gl; k < hi; k += FOLD_GROUP * FOLD_BATCH) {  // FOLD_BATCH entries' loads in flight together
-        uint2 e[FOLD_BATCH];
-#pragma unroll
-        for (int u = 0; u < FOLD_BATCH; u++) e[u] = k + u * FOLD_GROUP < hi ? m.ent[k + u * FOLD_GROUP] : make_uint2(0u, 0u);
-        F29<P> c[FOLD_BATCH];
-        Fe<P> zz[FOLD_BATCH];
-#pragma unroll
-        for (int u = 0; u < FOLD_BATCH; u++) {
-            c[u] = ld_const29<P>(dict + (size_t)e[u].y * P29_STRIDE);
-            zz[u] = z[0][e[u].x];
-        }
-#pragma unroll
-        for (int u = 0; u < FOLD_BATCH; u++)
-            if (k + u * FOLD_GROUP < hi) row_mac<P>(acc, c[u], f29_from_mont256<P>(zz[u]), one29);
-    }
-    F29<P> part = dot29_finish<P>(acc.acc);  // tight, < 2^258.1
-    if (hi - lo <= 256) {
-#pragma unroll
-        for (int off = FOLD_GROUP / 2; off >= 1; off >>= 1) {
-#pragma unroll
-            for (int i = 0; i < 9; i++) part.l[i] += __shfl_down(part.l[i], off);
-            if (off == FOLD_GROUP / 4 || off == 1) part = f29_carry<P>(part);
-        }
-        out[0] = part;
-    } else {
-        RowAcc<P> tot;
-        row_init<P>(tot);
-        const int leader = (threadIdx.x & 63) & ~(FOLD_GROUP - 1);
-#pragma unroll 1
-        for (int g = 0; g < FOLD_GROUP; g++) {
-            F29<P> v;
-#pragma unroll
-            for (int i = 0; i < 9; i++) v.l[i] = __shfl(part.l[i], leader + g);
-            row_mac<P>(tot, v, ld_const29<P>(one29), one29);
-        }
-        out[0] = dot29_finish<P>(tot.acc);
-    }
-}
 
 template <class P>
 __device__ __forceinline__ void fold_store(Fe<P>* dst, const F29<P>& v) {
     *dst = f29_to_mont256<P>(v);
 }
 
-__device__ __forceinline__ bool fold_is_long(const R1csDev& s, size_t row, uint32_t* lo, uint32_t* hi) {
-    lo[0] = s.a.rowptr[row]; hi[0] = s.a.rowptr[row + 1];
-    lo[1] = s.b.rowptr[row]; hi[1] = s.b.rowptr[row + 1];
-    lo[2] = s.c.rowptr[row]; hi[2] = s.c.rowptr[row + 1];
-    return hi[0] - lo[0] > FOLD_LONG || hi[1] - lo[1] > FOLD_LONG || hi[2] - lo[2] > FOLD_LONG;
+// This lane's row in workgroup bid of the nb of its kind, and the bounds of the row's three combinations.
+//   LONG = false  one lane per row (XCD-aware); false: no row here, or a long one that is left to the other kind
+//   LONG = true   FOLD_GROUP lanes per entry of long_rows, in list order (fold_row_block is not applied to these few blocks); every
+//                 lane walks a row (r1cs_shape.cuh: row_slot), `lead` is the lane that holds and stores the row's values
+template <bool LONG>
+__device__ __forceinline__ bool fold_lane_row(const R1csDev& s, unsigned bid, unsigned nb, size_t& row, uint32_t& gl, bool& lead, uint32_t* lo, uint32_t* hi) {
+    if (!LONG) {
+        row = fold_row_block(bid, nb) * FOLD_BLOCK + threadIdx.x;
+        gl = 0;
+        lead = true;
+        return row < s.rows && !fold_is_long(s, row, lo, hi);
+    }
+    const RowSlot t = row_slot<FOLD_GROUP>(s.long_rows, s.n_long, bid, threadIdx.x);
+    row = t.row;
+    gl = t.gl;
+    lead = t.live && t.gl == 0;
+    fold_is_long(s, row, lo, hi);
+    return true;
 }
 
 // LONG = false: one lane per row, long rows skipped;  LONG = true: FOLD_GROUP lanes per entry of long_rows
 template <class P, bool LONG>
 __global__ __launch_bounds__(FOLD_BLOCK) void r1cs_multiply_vec_kernel(R1csDev s, const Fe<P>* __restrict__ z, Fe<P>* __restrict__ az,
                                                                          Fe<P>* __restrict__ bz, Fe<P>* __restrict__ cz) {
+    constexpr int G = LONG ? FOLD_GROUP : 1;
     const uint32_t* one29 = s.dict + s.dict_size * P29_STRIDE;  // the Montgomery one closes the dictionary
-    const Fe<P>* zs[1] = {z};
-    uint32_t lo[3], hi[3];
-    F29<P> r;
-    if (!LONG) {
-        size_t row = fold_row_block(blockIdx.x, gridDim.x) * FOLD_BLOCK + threadIdx.x;
-        if (row >= s.rows || fold_is_long(s, row, lo, hi)) return;
-        fold_row_lane<P, 1>(s.a, s.dict, one29, lo[0], hi[0], zs, &r);
-        fold_store<P>(az + row, r);
-        fold_row_lane<P, 1>(s.b, s.dict, one29, lo[1], hi[1], zs, &r);
-        fold_store<P>(bz + row, r);
-        fold_row_lane<P, 1>(s.c, s.dict, one29, lo[2], hi[2], zs, &r);
-        fold_store<P>(cz + row, r);
-    } else {
-        size_t w = ((size_t)blockIdx.x * FOLD_BLOCK + threadIdx.x) / FOLD_GROUP;
-        const bool live = w < s.n_long;  // a group without a row shadows the last one (the shuffles need every lane)
-        size_t row = s.long_rows[live ? w : s.n_long - 1];
-        fold_is_long(s, row, lo, hi);
-        const bool lead = live && (threadIdx.x & (FOLD_GROUP - 1)) == 0;
-        fold_row_wave<P, 1>(s.a, s.dict, one29, lo[0], hi[0], zs, &r);
-        if (lead) fold_store<P>(az + row, r);
-        fold_row_wave<P, 1>(s.b, s.dict, one29, lo[1], hi[1], zs, &r);
-        if (lead) fold_store<P>(bz + row, r);
-        fold_row_wave<P, 1>(s.c, s.dict, one29, lo[2], hi[2], zs, &r);
-        if (lead) fold_store<P>(cz + row, r);
-    }
+    uint32_t lo[3], hi[3], gl;
+    size_t row;
+    bool lead;
+    if (!fold_lane_row<LONG>(s, blockIdx.x, gridDim.x, row, gl, lead, lo, hi)) return;
+    F29<P> r = r1cs_row<P, G, LONG, false>(s.a, s.dict, one29, lo[0], hi[0], gl, z);
+    if (lead) fold_store<P>(az + row, r);
+    r = r1cs_row<P, G, LONG, false>(s.b, s.dict, one29, lo[1], hi[1], gl, z);
+    if (lead) fold_store<P>(bz + row, r);
+    r = r1cs_row<P, G, LONG, false>(s.c, s.dict, one29, lo[2], hi[2], gl, z);
+    if (lead) fold_store<P>(cz + row, r);
 }
 
 // -u1, -u2 (u_i = z_i[num_vars]) are negated and converted by every lane that finishes a row: two broadcast loads and two
@@ -183,42 +91,28 @@ __global__ __launch_bounds__(FOLD_BLOCK) void r1cs_multiply_vec_kernel(R1csDev s
 template <class P, bool LONG>
 __device__ __forceinline__ void r1cs_cross_term_body(const R1csDev& s, const Fe<P>* __restrict__ z1, const Fe<P>* __restrict__ z2, size_t u_index,
                                                      Fe<P>* __restrict__ t, unsigned bid, unsigned nb) {
+    constexpr int G = LONG ? FOLD_GROUP : 1;
     const uint32_t* one29 = s.dict + s.dict_size * P29_STRIDE;
     const Fe<P>* zs[2] = {z1, z2};
-    uint32_t lo[3], hi[3];
+    uint32_t lo[3], hi[3], gl;
     F29<P> a[2], b[2], c[2];
     size_t row;
+    bool lead;
+    if (!fold_lane_row<LONG>(s, bid, nb, row, gl, lead, lo, hi)) return;
+    // one vector at a time (a second pass re-reads the 8-byte records from L2 but halves the live accumulators:
+    // 3 waves/SIMD instead of 2 with spills); T is built up as the row values arrive
+#pragma unroll
+    for (int v = 0; v < 2; v++) {
+        a[v] = r1cs_row<P, G, LONG, false>(s.a, s.dict, one29, lo[0], hi[0], gl, zs[v]);
+        b[v] = r1cs_row<P, G, LONG, false>(s.b, s.dict, one29, lo[1], hi[1], gl, zs[v]);
+    }
     Dot29<P> acc;
     dot29_init<P>(acc);
-    if (!LONG) {
-        row = fold_row_block(bid, nb) * FOLD_BLOCK + threadIdx.x;
-        if (row >= s.rows || fold_is_long(s, row, lo, hi)) return;
-        // one vector at a time (a second pass re-reads the 8-byte records from L2 but halves the live accumulators:
-        // 3 waves/SIMD instead of 2 with spills); T is built up as the row values arrive
+    dot29_mac<P>(acc, a[0], b[1]);
+    dot29_mac<P>(acc, a[1], b[0]);
 #pragma unroll
-        for (int v = 0; v < 2; v++) {
-            fold_row_lane<P, 1>(s.a, s.dict, one29, lo[0], hi[0], zs + v, a + v);
-            fold_row_lane<P, 1>(s.b, s.dict, one29, lo[1], hi[1], zs + v, b + v);
-        }
-        dot29_mac<P>(acc, a[0], b[1]);
-        dot29_mac<P>(acc, a[1], b[0]);
-#pragma unroll
-        for (int v = 0; v < 2; v++) fold_row_lane<P, 1>(s.c, s.dict, one29, lo[2], hi[2], zs + v, c + v);
-    } else {
-        size_t w = ((size_t)bid * FOLD_BLOCK + threadIdx.x) / FOLD_GROUP;
-        const bool live = w < s.n_long;  // a group without a row shadows the last one (the shuffles need every lane)
-        row = s.long_rows[live ? w : s.n_long - 1];
-        fold_is_long(s, row, lo, hi);
-#pragma unroll
-        for (int v = 0; v < 2; v++) {
-            fold_row_wave<P, 1>(s.a, s.dict, one29, lo[0], hi[0], zs + v, a + v);
-            fold_row_wave<P, 1>(s.b, s.dict, one29, lo[1], hi[1], zs + v, b + v);
-            fold_row_wave<P, 1>(s.c, s.dict, one29, lo[2], hi[2], zs + v, c + v);
-        }
-        if (!live || (threadIdx.x & (FOLD_GROUP - 1))) return;
-        dot29_mac<P>(acc, a[0], b[1]);
-        dot29_mac<P>(acc, a[1], b[0]);
-    }
+    for (int v = 0; v < 2; v++) c[v] = r1cs_row<P, G, LONG, false>(s.c, s.dict, one29, lo[2], hi[2], gl, zs[v]);
+    if (!lead) return;
     dot29_mac<P>(acc, f29_from_mont256<P>(fe_neg<P>(z1[u_index])), c[1]);  // 32 (-u) 2^256: lazy Montgomery-2^261 form, tight, < 2^259
     dot29_mac<P>(acc, f29_from_mont256<P>(fe_neg<P>(z2[u_index])), c[0]);
     fold_store<P>(t + row, dot29_finish<P>(acc));
@@ -269,40 +163,27 @@ template <class P, bool LONG>
 __device__ __forceinline__ void r1cs_cross_term_cached_body(const R1csDev& s, const Fe<P>* __restrict__ z2, const CachedProducts<P>& cp, size_t u_index,
                                                             Fe<P>* __restrict__ t, Fe<P>* __restrict__ az2, Fe<P>* __restrict__ bz2,
                                                             Fe<P>* __restrict__ cz2, unsigned bid, unsigned nb) {
+    constexpr int G = LONG ? FOLD_GROUP : 1;
     const uint32_t* one29 = s.dict + s.dict_size * P29_STRIDE;
-    const Fe<P>* zs[1] = {z2};
-    uint32_t lo[3], hi[3];
+    uint32_t lo[3], hi[3], gl;
     size_t row;
-    bool store = true;
-    if (!LONG) {
-        row = fold_row_block(bid, nb) * FOLD_BLOCK + threadIdx.x;
-        if (row >= s.rows || fold_is_long(s, row, lo, hi)) return;
-    } else {
-        size_t w = ((size_t)bid * FOLD_BLOCK + threadIdx.x) / FOLD_GROUP;
-        const bool live = w < s.n_long;  // a group without a row shadows the last one (the shuffles need every lane)
-        row = s.long_rows[live ? w : s.n_long - 1];
-        fold_is_long(s, row, lo, hi);
-        store = live && (threadIdx.x & (FOLD_GROUP - 1)) == 0;
-    }
+    bool store;
+    if (!fold_lane_row<LONG>(s, bid, nb, row, gl, store, lo, hi)) return;
     // One product at a time, each folded into T's four-term lazy row and stored as soon as it is complete: only ONE row value is live
     // beside the accumulator (three of them at once cost the kernel its third wave per SIMD: 200 registers against 168).
     Dot29<P> acc;
     dot29_init<P>(acc);
-    F29<P> v;
-    if (!LONG) fold_row_lane<P, 1>(s.a, s.dict, one29, lo[0], hi[0], zs, &v);
-    else fold_row_wave<P, 1>(s.a, s.dict, one29, lo[0], hi[0], zs, &v);
+    F29<P> v = r1cs_row<P, G, LONG, false>(s.a, s.dict, one29, lo[0], hi[0], gl, z2);
     if (store) {
         dot29_mac<P>(acc, v, f29_from_mont256<P>(cached_row<P>(cp.b1, cp.prev_b, cp.r_prev, row)));  // A z2 o B z1
         fold_store<P>(az2 + row, v);
     }
-    if (!LONG) fold_row_lane<P, 1>(s.b, s.dict, one29, lo[1], hi[1], zs, &v);
-    else fold_row_wave<P, 1>(s.b, s.dict, one29, lo[1], hi[1], zs, &v);
+    v = r1cs_row<P, G, LONG, false>(s.b, s.dict, one29, lo[1], hi[1], gl, z2);
     if (store) {
         dot29_mac<P>(acc, f29_from_mont256<P>(cached_row<P>(cp.a1, cp.prev_a, cp.r_prev, row)), v);  // A z1 o B z2
         fold_store<P>(bz2 + row, v);
     }
-    if (!LONG) fold_row_lane<P, 1>(s.c, s.dict, one29, lo[2], hi[2], zs, &v);
-    else fold_row_wave<P, 1>(s.c, s.dict, one29, lo[2], hi[2], zs, &v);
+    v = r1cs_row<P, G, LONG, false>(s.c, s.dict, one29, lo[2], hi[2], gl, z2);
     if (!store) return;
     dot29_mac<P>(acc, f29_from_mont256<P>(fe_neg<P>(cp.u1)), v);                                                                          // - u1 C z2
     dot29_mac<P>(acc, f29_from_mont256<P>(fe_neg<P>(z2[u_index])), f29_from_mont256<P>(cached_row<P>(cp.c1, cp.prev_c, cp.r_prev, row)));  // - u2 C z1
@@ -455,11 +336,8 @@ __global__ __launch_bounds__(FOLD_BLOCK) void fold_padded_kernel(const FoldPadde
     }
 }
 
-// grid of the one-lane-per-row kernels: a multiple of FOLD_XCDS workgroups, so that fold_row_block is a bijection onto [0, grid)
-static unsigned fold_grid(size_t rows) {
-    const unsigned nb = div_up(rows, FOLD_BLOCK);
-    return (nb + FOLD_XCDS - 1) / FOLD_XCDS * FOLD_XCDS;
-}
+// workgroups of the long rows: FOLD_GROUP lanes per row, in list order (0 without a long row)
+static unsigned fold_long_blocks(const R1csShape& sh) { return div_up(sh.n_long * FOLD_GROUP, FOLD_BLOCK); }
 
 // ---- host side ---------------------------------------------------------------------------------------------
 struct Key32 {
@@ -526,9 +404,9 @@ static void multiply_vec(const R1csShape& sh, const void* d_z, void* az, void* b
     ProfScope ps("r1cs_multiply_vec", s);
     const R1csDev d = dev_view(sh);
     if (sh.n_long)  // first: its few latency-bound waves then run beside the lane-per-row launch that follows
-        hipLaunchKernelGGL((r1cs_multiply_vec_kernel<P, true>), dim3(div_up(sh.n_long * FOLD_GROUP, FOLD_BLOCK)), dim3(FOLD_BLOCK), 0, s, d,
+        hipLaunchKernelGGL((r1cs_multiply_vec_kernel<P, true>), dim3(fold_long_blocks(sh)), dim3(FOLD_BLOCK), 0, s, d,
                            (const Fe<P>*)d_z, (Fe<P>*)az, (Fe<P>*)bz, (Fe<P>*)cz);
-    hipLaunchKernelGGL((r1cs_multiply_vec_kernel<P, false>), dim3(fold_grid(sh.num_cons)), dim3(FOLD_BLOCK), 0, s, d, (const Fe<P>*)d_z,
+    hipLaunchKernelGGL((r1cs_multiply_vec_kernel<P, false>), dim3(class_blocks(sh.num_cons, 1)), dim3(FOLD_BLOCK), 0, s, d, (const Fe<P>*)d_z,
                        (Fe<P>*)az, (Fe<P>*)bz, (Fe<P>*)cz);
     LURK_HIP_CHECK(hipGetLastError());
 }
@@ -537,8 +415,8 @@ static void cross_term(const R1csShape& sh, const void* d_z1, const void* d_z2, 
     if (!sh.num_cons) return;
     ProfScope ps("r1cs_cross_term", s);
     const R1csDev d = dev_view(sh);
-    const unsigned long_blocks = sh.n_long ? div_up(sh.n_long * FOLD_GROUP, FOLD_BLOCK) : 0;
-    hipLaunchKernelGGL((r1cs_cross_term_kernel<P>), dim3(long_blocks + fold_grid(sh.num_cons)), dim3(FOLD_BLOCK), 0, s, d, (const Fe<P>*)d_z1,
+    const unsigned long_blocks = fold_long_blocks(sh);
+    hipLaunchKernelGGL((r1cs_cross_term_kernel<P>), dim3(long_blocks + class_blocks(sh.num_cons, 1)), dim3(FOLD_BLOCK), 0, s, d, (const Fe<P>*)d_z1,
                        (const Fe<P>*)d_z2, sh.num_vars, (Fe<P>*)d_t, long_blocks);
     LURK_HIP_CHECK(hipGetLastError());
 }
@@ -548,7 +426,7 @@ static void cross_term_cached(const R1csShape& sh, const void* d_z2, void* az1, 
     if (!sh.num_cons) return;
     ProfScope ps("r1cs_cross_term", s);
     const R1csDev d = dev_view(sh);
-    const unsigned long_blocks = sh.n_long ? div_up(sh.n_long * FOLD_GROUP, FOLD_BLOCK) : 0;
+    const unsigned long_blocks = fold_long_blocks(sh);
     CachedProducts<P> cp;
     cp.a1 = (Fe<P>*)az1;
     cp.b1 = (Fe<P>*)bz1;
@@ -559,7 +437,7 @@ static void cross_term_cached(const R1csShape& sh, const void* d_z2, void* az1, 
     cp.r_prev = fe_zero<P>();
     if (r_prev32) memcpy(cp.r_prev.l, r_prev32, 32);
     memcpy(cp.u1.l, u1_32, 32);
-    hipLaunchKernelGGL((r1cs_cross_term_cached_kernel<P>), dim3(long_blocks + fold_grid(sh.num_cons)), dim3(FOLD_BLOCK), 0, s, d, (const Fe<P>*)d_z2, cp,
+    hipLaunchKernelGGL((r1cs_cross_term_cached_kernel<P>), dim3(long_blocks + class_blocks(sh.num_cons, 1)), dim3(FOLD_BLOCK), 0, s, d, (const Fe<P>*)d_z2, cp,
                        sh.num_vars, (Fe<P>*)d_t, (Fe<P>*)az2, (Fe<P>*)bz2, (Fe<P>*)cz2, long_blocks);
     LURK_HIP_CHECK(hipGetLastError());
 }

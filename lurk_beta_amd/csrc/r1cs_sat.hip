@@ -9,14 +9,8 @@
 // Row classes.  The lane-per-row kernels of fold.hip are built for the step circuit's synthetic stand-in (3-4 entries per row, a few
 // 255-entry bit decompositions).  The slot gadgets' own rows (slot_circuit.hpp) are different: about a third of a Poseidon slot's rows
 // carry a linear combination of 8 to 66 entries in A and / or B (the partial rounds), and a wave of 64 neighbouring rows waits for its one
-// 60-entry lane.  Rows are therefore classed once per shape, on the first call (SatPlan), by the longest of their three combinations:
-//     lane   <= SAT_LANE_MAX entries        one lane per row
-//     mid    <= SAT_MID_MAX                 SAT_GROUP lanes per row: lane g takes entries g, g + SAT_GROUP, ... and the partial sums are
-//                                           added across the group limb-wise (two butterfly steps between carry passes)
-//     wide   the rest (bit decompositions)  16 lanes per row, the treatment fold.hip gives its long rows (any length: beyond 256 entries
-//                                           the partial sums re-enter one by one)
-// One launch covers the three classes (block ranges, each a multiple of the XCD count so that fold_row_block keeps a frame's rows on
-// one L2).  Accumulation is fold.hip's RowAcc: the bound of a row (64 terms, then re-entry) is the one argued there.
+// 60-entry lane.  Rows are therefore classed once per shape, on the first call, into lane / mid / wide rows and one launch covers the
+// three classes: r1cs_shape.cuh has the classes (RowClasses), the row product (r1cs_row) and its bounds.
 //
 // The coefficient dictionary is read through L2 as in fold.hip, or (LURK_SAT_LDS=1, an experiment kept for measurement) copied into LDS
 // by 512-thread persistent workgroups, one per CU - see DESIGN.md for what each variant measured.
@@ -34,103 +28,33 @@ namespace lurk {
 
 size_t slot_witness_size(int field_id, int slot_type);  // poseidon.hip
 
-constexpr uint32_t SAT_LANE_MAX = 8;   // defaults of the class bounds (LURK_SAT_LANE_MAX / LURK_SAT_MID_MAX override them for measurements)
-constexpr uint32_t SAT_MID_MAX = 96;
-constexpr uint32_t SAT_GROUP = 4;  // lanes per mid-length row: 4 / 8 / 16 measured 0.242 / 0.285 / 0.384 ms at rc = 100
-constexpr int SAT_WIDE_GROUP = 16;
-constexpr int SAT_BATCH = 2;  // entries whose loads one lane issues together (fold.hip: FOLD_BATCH, measured there)
 constexpr int SAT_PERSIST_BLOCK = 512;  // two waves per SIMD: 1024 threads leave 128 registers per lane and the row accumulators spill
 
 struct SatDev {
     R1csDev s;
-    const uint32_t* rows;  // [wide | mid | lane]
-    uint32_t n_wide, n_mid, n_lane;
-    unsigned wide_blocks, mid_blocks, lane_blocks;  // virtual 256-lane blocks per class, multiples of FOLD_XCDS (0 for an empty class)
+    RowClassDev c;
     size_t u_index;
     unsigned long long* rec;
 };
 
-template <class P, bool LDS>
-__device__ __forceinline__ F29<P> sat_coeff(const uint32_t* dict, uint32_t id) {
-    const uint32_t* p = dict + (size_t)id * P29_STRIDE;
-    if (!LDS) return ld_const29<P>(p);
-    F29<P> r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = p[i];
-    return r;
-}
-
-// G lanes, one row of one matrix: lane gl of the group accumulates entries lo + gl, lo + gl + G, ...; for G > 1 the reduced partial sums
-// are added across the group (valid on the group's first lane).  ANY_LEN = false: the caller guarantees at most 256 entries, so that the
-// limb-wise sum of the partial values stays below 2^261 (fold.hip: fold_row_wave).
-template <class P, int G, bool ANY_LEN, bool LDS>
-__device__ __forceinline__ F29<P> sat_row(const CsrView& m, const uint32_t* dict, const uint32_t* one29, uint32_t lo, uint32_t hi, uint32_t gl,
-                                          const Fe<P>* __restrict__ z) {
-    RowAcc<P> acc;
-    row_init<P>(acc);
-    for (uint32_t k = lo + gl; k < hi; k += G * SAT_BATCH) {
-        uint2 e[SAT_BATCH];
-#pragma unroll
-        for (int u = 0; u < SAT_BATCH; u++) e[u] = k + u * G < hi ? m.ent[k + u * G] : make_uint2(0u, 0u);
-        F29<P> c[SAT_BATCH];
-        Fe<P> zz[SAT_BATCH];
-#pragma unroll
-        for (int u = 0; u < SAT_BATCH; u++) {
-            c[u] = sat_coeff<P, LDS>(dict, e[u].y);
-            zz[u] = z[e[u].x];
-        }
-#pragma unroll
-        for (int u = 0; u < SAT_BATCH; u++)
-            if (k + u * G < hi) row_mac<P>(acc, c[u], f29_from_mont256<P>(zz[u]), one29);
-    }
-    F29<P> part = dot29_finish<P>(acc.acc);  // tight
-    if (G == 1) return part;
-    if (!ANY_LEN || hi - lo <= 256) {
-        int steps = 0;
-#pragma unroll
-        for (int off = G / 2; off >= 1; off >>= 1) {
-#pragma unroll
-            for (int i = 0; i < 9; i++) part.l[i] += __shfl_down(part.l[i], off);
-            if (++steps == 2 || off == 1) {  // 4 x 2^29 < 2^32
-                part = f29_carry<P>(part);
-                steps = 0;
-            }
-        }
-        return part;
-    }
-    RowAcc<P> tot;
-    row_init<P>(tot);
-    const int leader = (threadIdx.x & 63) & ~(G - 1);
-#pragma unroll 1
-    for (int g = 0; g < G; g++) {
-        F29<P> v;
-#pragma unroll
-        for (int i = 0; i < 9; i++) v.l[i] = __shfl(part.l[i], leader + g);
-        row_mac<P>(tot, v, sat_coeff<P, LDS>(one29, 0), one29);
-    }
-    return dot29_finish<P>(tot.acc);
-}
-
-// 256 lanes of one class: slot = the row's position in the class list
+// 256 lanes of one class
 template <class P, int G, bool ANY_LEN, bool LDS>
 __device__ __forceinline__ void sat_class(const SatDev& d, const uint32_t* dict, const uint32_t* list, uint32_t n, unsigned vb, unsigned nb, uint32_t tid,
                                           const Fe<P>* __restrict__ z, const Fe<P>* __restrict__ e) {
     const uint32_t* one29 = dict + d.s.dict_size * P29_STRIDE;  // the Montgomery one closes the dictionary
-    const size_t slot = (fold_row_block(vb, nb) * FOLD_BLOCK + tid) / G;
-    const bool live = slot < n;
-    if (G == 1 && !live) return;
-    const uint32_t row = list[live ? slot : n - 1];  // a group without a row shadows the last one (the shuffles need every lane)
-    const uint32_t gl = tid & (G - 1);
-    const F29<P> a = sat_row<P, G, ANY_LEN, LDS>(d.s.a, dict, one29, d.s.a.rowptr[row], d.s.a.rowptr[row + 1], gl, z);
-    const F29<P> b = sat_row<P, G, ANY_LEN, LDS>(d.s.b, dict, one29, d.s.b.rowptr[row], d.s.b.rowptr[row + 1], gl, z);
-    const F29<P> c = sat_row<P, G, ANY_LEN, LDS>(d.s.c, dict, one29, d.s.c.rowptr[row], d.s.c.rowptr[row + 1], gl, z);
+    const RowSlot slot = row_slot<G>(list, n, fold_row_block(vb, nb), tid);
+    if (G == 1 && !slot.live) return;
+    const uint32_t row = slot.row, gl = slot.gl;
+    const F29<P> a = r1cs_row<P, G, ANY_LEN, LDS>(d.s.a, dict, one29, d.s.a.rowptr[row], d.s.a.rowptr[row + 1], gl, z);
+    const F29<P> b = r1cs_row<P, G, ANY_LEN, LDS>(d.s.b, dict, one29, d.s.b.rowptr[row], d.s.b.rowptr[row + 1], gl, z);
+    const F29<P> c = r1cs_row<P, G, ANY_LEN, LDS>(d.s.c, dict, one29, d.s.c.rowptr[row], d.s.c.rowptr[row + 1], gl, z);
     bool fail = false;
-    if (live && gl == 0) {
+    if (slot.live && gl == 0) {
         Dot29<P> acc;
         dot29_init<P>(acc);
         dot29_mac<P>(acc, a, b);
         dot29_mac<P>(acc, f29_from_mont256<P>(fe_neg<P>(z[d.u_index])), c);  // 32 (-u) 2^256: tight, < 2^259 (fold.hip, the cross term)
-        if (e) dot29_mac<P>(acc, f29_from_mont256<P>(fe_neg<P>(e[row])), sat_coeff<P, LDS>(one29, 0));
+        if (e) dot29_mac<P>(acc, f29_from_mont256<P>(fe_neg<P>(e[row])), r1cs_coeff<P, LDS>(one29, 0));
         const Fe<P> v = f29_to_mont256<P>(dot29_finish<P>(acc));  // canonical
         uint32_t any = 0;
 #pragma unroll
@@ -149,13 +73,9 @@ __device__ __forceinline__ void sat_class(const SatDev& d, const uint32_t* dict,
 template <class P, int GM, bool LDS>
 __device__ __forceinline__ void sat_vblock(const SatDev& d, const uint32_t* dict, unsigned j, uint32_t tid, const Fe<P>* __restrict__ z,
                                            const Fe<P>* __restrict__ e) {
-    if (j < d.wide_blocks) {
-        sat_class<P, SAT_WIDE_GROUP, true, LDS>(d, dict, d.rows, d.n_wide, j, d.wide_blocks, tid, z, e);
-    } else if (j < d.wide_blocks + d.mid_blocks) {
-        sat_class<P, GM, false, LDS>(d, dict, d.rows + d.n_wide, d.n_mid, j - d.wide_blocks, d.mid_blocks, tid, z, e);
-    } else {
-        sat_class<P, 1, false, LDS>(d, dict, d.rows + d.n_wide + d.n_mid, d.n_lane, j - d.wide_blocks - d.mid_blocks, d.lane_blocks, tid, z, e);
-    }
+    row_class_vblock<GM>(d.c, j, [&](auto g, auto any_len, const uint32_t* list, uint32_t n, unsigned vb, unsigned nb) {
+        sat_class<P, decltype(g)::value, decltype(any_len)::value, LDS>(d, dict, list, n, vb, nb, tid, z, e);
+    });
 }
 
 template <class P, int GM>
@@ -171,7 +91,7 @@ __global__ __launch_bounds__(SAT_PERSIST_BLOCK) void r1cs_sat_lds_kernel(SatDev 
     const uint32_t words = (uint32_t)(d.s.dict_size + 1) * P29_STRIDE;
     for (uint32_t i = threadIdx.x; i < words / 4; i += SAT_PERSIST_BLOCK) ((uint4*)sat_dict)[i] = ((const uint4*)d.s.dict)[i];
     __syncthreads();
-    const unsigned total = d.wide_blocks + d.mid_blocks + d.lane_blocks;
+    const unsigned total = d.c.wide_blocks + d.c.mid_blocks + d.c.lane_blocks;
     for (unsigned j = (threadIdx.x >> 8) * gridDim.x + blockIdx.x; j < total; j += gridDim.x * (SAT_PERSIST_BLOCK / FOLD_BLOCK))
         sat_vblock<P, GM, true>(d, sat_dict, j, threadIdx.x & (FOLD_BLOCK - 1), z, e);
 }
@@ -182,37 +102,11 @@ static uint32_t env_u32(const char* name, uint32_t dflt) {
     return v && *v ? (uint32_t)strtoul(v, nullptr, 10) : dflt;
 }
 
-static unsigned sat_blocks(size_t n, int group) {  // 256-lane blocks for n rows of `group` lanes, rounded to the XCD count
-    if (!n) return 0;
-    const unsigned nb = div_up(n * group, FOLD_BLOCK);
-    return (nb + FOLD_XCDS - 1) / FOLD_XCDS * FOLD_XCDS;
-}
-
 // (sat_mu held)
 static SatPlan& sat_plan(const R1csShape& sh, uint32_t lane_max, uint32_t mid_max) {
-    if (sh.sat && sh.sat->lane_max == lane_max && sh.sat->mid_max == mid_max) return *sh.sat;
+    if (sh.sat && sh.sat->cls.lane_max == lane_max && sh.sat->cls.mid_max == mid_max) return *sh.sat;
     auto plan = std::make_unique<SatPlan>();
-    const size_t rows = sh.num_cons;
-    std::vector<uint32_t> rp[3];
-    for (int w = 0; w < 3; w++) {
-        rp[w].resize(rows + 1);
-        LURK_HIP_CHECK(hipMemcpy(rp[w].data(), sh.m[w].rowptr.p, (rows + 1) * 4, hipMemcpyDeviceToHost));
-    }
-    std::vector<uint32_t> cls[3];  // wide, mid, lane
-    for (size_t i = 0; i < rows; i++) {
-        uint32_t len = 0;
-        for (int w = 0; w < 3; w++) len = std::max(len, rp[w][i + 1] - rp[w][i]);
-        cls[len <= lane_max ? 2 : len <= mid_max ? 1 : 0].push_back((uint32_t)i);
-    }
-    plan->n_wide = cls[0].size();
-    plan->n_mid = cls[1].size();
-    plan->n_lane = cls[2].size();
-    plan->lane_max = lane_max;
-    plan->mid_max = mid_max;
-    cls[0].insert(cls[0].end(), cls[1].begin(), cls[1].end());
-    cls[0].insert(cls[0].end(), cls[2].begin(), cls[2].end());
-    plan->rows.alloc(rows * 4);
-    if (rows) LURK_HIP_CHECK(hipMemcpy(plan->rows.p, cls[0].data(), rows * 4, hipMemcpyHostToDevice));
+    build_row_classes(plan->cls, sh, lane_max, mid_max, false);
     plan->rec.alloc(16);
     LURK_HIP_CHECK(hipHostMalloc((void**)&plan->host, 32, hipHostMallocDefault));
     sh.sat = std::move(plan);
@@ -221,7 +115,7 @@ static SatPlan& sat_plan(const R1csShape& sh, uint32_t lane_max, uint32_t mid_ma
 
 template <class P, int GM>
 static void sat_launch(const SatDev& d, bool lds, size_t dict_size, const void* d_z, const void* d_e, hipStream_t s) {
-    const unsigned total = d.wide_blocks + d.mid_blocks + d.lane_blocks;
+    const unsigned total = d.c.wide_blocks + d.c.mid_blocks + d.c.lane_blocks;
     if (lds) {
         const int bytes = (int)((dict_size + 1) * P29_STRIDE * 4);
         allow_dynamic_lds((const void*)r1cs_sat_lds_kernel<P, GM>, bytes);
@@ -252,13 +146,7 @@ static void is_sat(const R1csShape& sh, const void* d_z, const void* d_e, uint64
     SatPlan& plan = sat_plan(sh, lane_max, mid_max);
     SatDev d;
     d.s = dev_view(sh);
-    d.rows = plan.rows.as<uint32_t>();
-    d.n_wide = (uint32_t)plan.n_wide;
-    d.n_mid = (uint32_t)plan.n_mid;
-    d.n_lane = (uint32_t)plan.n_lane;
-    d.wide_blocks = sat_blocks(plan.n_wide, SAT_WIDE_GROUP);
-    d.mid_blocks = sat_blocks(plan.n_mid, (int)group);
-    d.lane_blocks = sat_blocks(plan.n_lane, 1);
+    d.c = class_view(plan.cls, (int)group);
     d.u_index = sh.num_vars;
     d.rec = plan.rec.as<unsigned long long>();
     plan.host[0] = 0;

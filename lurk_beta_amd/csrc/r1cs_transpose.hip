@@ -31,7 +31,6 @@
 namespace lurk {
 
 constexpr int TR_BLOCK = 256;     // one entry (expand, rowptr') or one output row (long rows) per lane
-constexpr uint32_t TR_LONG = 32;  // fold.hip's FOLD_LONG: rows with more entries in A, B or C go to the wave-per-row kernels
 static_assert(TR_BLOCK == 4 * 64, "the long-row kernels sum four wave64 ballots");
 
 // the row of entry k: the largest i in [lo, hi] with rowptr[i] <= k (empty rows share their successor's pointer and are passed over)
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(TR_BLOCK) void r1cs_transpose_rowptr_kernel(const u
 }
 
 __device__ __forceinline__ bool tr_is_long(const uint32_t* __restrict__ ra, const uint32_t* __restrict__ rb, const uint32_t* __restrict__ rc, size_t j) {
-    return ra[j + 1] - ra[j] > TR_LONG || rb[j + 1] - rb[j] > TR_LONG || rc[j + 1] - rc[j] > TR_LONG;
+    return ra[j + 1] - ra[j] > FOLD_LONG || rb[j + 1] - rb[j] > FOLD_LONG || rc[j + 1] - rc[j] > FOLD_LONG;
 }
 
 // counts[b] = the long rows among rows [b TR_BLOCK, (b + 1) TR_BLOCK)
@@ -195,8 +194,8 @@ int lurk_hip_r1cs_transpose_dev(const lurk_hip_r1cs* shape, size_t rows_t, lurk_
         }
         const size_t dict_bytes = (src.dict_size + 1) * P29_STRIDE * 4;  // with the closing record, the Montgomery one
         dst.dict.alloc(dict_bytes);
-        // a long row holds at least TR_LONG + 1 entries of the three matrices together
-        const size_t long_cap = total_nnz / (TR_LONG + 1) < rows_t ? total_nnz / (TR_LONG + 1) : rows_t;
+        // a long row holds at least FOLD_LONG + 1 entries of the three matrices together
+        const size_t long_cap = total_nnz / (FOLD_LONG + 1) < rows_t ? total_nnz / (FOLD_LONG + 1) : rows_t;
         dst.long_rows.alloc(long_cap * 4);
 
         ProfScope ps("r1cs_transpose", s);

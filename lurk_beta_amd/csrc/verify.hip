@@ -10,8 +10,8 @@
 // argument (ipa_s_vector_kernel), one commitment of s under the resident key.  Everything else - the sum-check rounds, eq(tau, r_x), the
 // padding factors, eval_X, b_hat in its closed form, the 2 ell + 5 scalar multiples of the final point equation - is host arithmetic.
 //
-// sparse_mle_kernel.  M~ = sum_i eq_x[i] sum_k val[k] eq_y[col[k]] for M = A, B, C.  Rows are classed by length as r1cs_sat.hip classes
-// them (one lane, 4 lanes, 16 lanes per row; RowAcc accumulates a row lazily), rows without any entry are left out of the lists.  A
+// sparse_mle_kernel.  M~ = sum_i eq_x[i] sum_k val[k] eq_y[col[k]] for M = A, B, C.  Rows are classed by length and multiplied with
+// eq_y as r1cs_shape.cuh has it (RowClasses, r1cs_row), rows without any entry are left out of the lists.  A
 // row value (Montgomery-2^261, lazy) is multiplied by eq_x[row] taken as PLAIN limbs of its canonical Montgomery-2^256 form: the
 // product a * e / 2^261 is then the Montgomery-2^256 form of the term, below 2^255.3.  The reduction to three elements:
 //     lanes -> wave      six shuffle steps on the nine 29-bit limbs, a carry pass every second step (4 x 2^29 < 2^31); the sum of 64
@@ -28,68 +28,12 @@
 
 namespace lurk {
 
-constexpr uint32_t MLE_LANE_MAX = 8;  // the class bounds of r1cs_sat.hip (measured there)
-constexpr uint32_t MLE_MID_MAX = 96;
-constexpr int MLE_GROUP = 4;
-constexpr int MLE_WIDE_GROUP = 16;
-constexpr int MLE_BATCH = 2;
 constexpr int MLE_WAVES = FOLD_BLOCK / 64;
 
 struct MleDev {
     R1csDev s;
-    const uint32_t* rows;  // [wide | mid | lane]
-    uint32_t n_wide, n_mid, n_lane;
-    unsigned wide_blocks, mid_blocks, lane_blocks;  // 256-lane blocks per class, multiples of FOLD_XCDS (0 for an empty class)
+    RowClassDev c;
 };
-
-// G lanes, one row of one matrix against eq_y: r1cs_sat.hip's sat_row (the bounds are argued there and in fold.hip)
-template <class P, int G, bool ANY_LEN>
-__device__ __forceinline__ F29<P> mle_row(const CsrView& m, const uint32_t* dict, const uint32_t* one29, uint32_t lo, uint32_t hi, uint32_t gl,
-                                          const Fe<P>* __restrict__ y) {
-    RowAcc<P> acc;
-    row_init<P>(acc);
-    for (uint32_t k = lo + gl; k < hi; k += G * MLE_BATCH) {
-        uint2 e[MLE_BATCH];
-#pragma unroll
-        for (int u = 0; u < MLE_BATCH; u++) e[u] = k + u * G < hi ? m.ent[k + u * G] : make_uint2(0u, 0u);
-        F29<P> c[MLE_BATCH];
-        Fe<P> yy[MLE_BATCH];
-#pragma unroll
-        for (int u = 0; u < MLE_BATCH; u++) {
-            c[u] = ld_const29<P>(dict + (size_t)e[u].y * P29_STRIDE);
-            yy[u] = y[e[u].x];
-        }
-#pragma unroll
-        for (int u = 0; u < MLE_BATCH; u++)
-            if (k + u * G < hi) row_mac<P>(acc, c[u], f29_from_mont256<P>(yy[u]), one29);
-    }
-    F29<P> part = dot29_finish<P>(acc.acc);  // tight
-    if (G == 1) return part;
-    if (!ANY_LEN || hi - lo <= 256) {
-        int steps = 0;
-#pragma unroll
-        for (int off = G / 2; off >= 1; off >>= 1) {
-#pragma unroll
-            for (int i = 0; i < 9; i++) part.l[i] += __shfl_down(part.l[i], off);
-            if (++steps == 2 || off == 1) {
-                part = f29_carry<P>(part);
-                steps = 0;
-            }
-        }
-        return part;
-    }
-    RowAcc<P> tot;
-    row_init<P>(tot);
-    const int leader = (threadIdx.x & 63) & ~(G - 1);
-#pragma unroll 1
-    for (int g = 0; g < G; g++) {
-        F29<P> v;
-#pragma unroll
-        for (int i = 0; i < 9; i++) v.l[i] = __shfl(part.l[i], leader + g);
-        row_mac<P>(tot, v, ld_const29<P>(one29), one29);
-    }
-    return dot29_finish<P>(tot.acc);
-}
 
 // 256 lanes of one class -> the three terms of this lane (zero on every lane that does not lead a live row)
 template <class P, int G, bool ANY_LEN>
@@ -97,26 +41,24 @@ __device__ __forceinline__ void mle_class(const MleDev& d, const uint32_t* list,
                                           const Fe<P>* __restrict__ ey, F29<P>* v) {
     const uint32_t* dict = d.s.dict;
     const uint32_t* one29 = dict + d.s.dict_size * P29_STRIDE;
-    const size_t slot = (fold_row_block(vb, nb) * FOLD_BLOCK + tid) / G;
-    const bool live = slot < n;
+    const RowSlot slot = row_slot<G>(list, n, fold_row_block(vb, nb), tid);
 #pragma unroll
     for (int w = 0; w < 3; w++) v[w] = f29_zero<P>();
-    if (G == 1 && !live) return;
-    const uint32_t row = list[live ? slot : n - 1];  // a group without a row shadows the last one (the shuffles need every lane)
-    const uint32_t gl = tid & (G - 1);
+    if (G == 1 && !slot.live) return;
+    const uint32_t row = slot.row, gl = slot.gl;
     const Fe<P> e = ex[row];
     const F29<P> eplain = f29_from_plain<P>(e.l);  // canonical Montgomery-2^256 limbs, unshifted: the product below leaves the 2^261 domain
-    const bool lead = live && gl == 0;
+    const bool lead = slot.live && gl == 0;
     {
-        const F29<P> t = f29_mul<P>(eplain, mle_row<P, G, ANY_LEN>(d.s.a, dict, one29, d.s.a.rowptr[row], d.s.a.rowptr[row + 1], gl, ey));  // eplain tight, the row
+        const F29<P> t = f29_mul<P>(eplain, r1cs_row<P, G, ANY_LEN, false>(d.s.a, dict, one29, d.s.a.rowptr[row], d.s.a.rowptr[row + 1], gl, ey));  // eplain tight, the row
         if (lead) v[0] = t;                                                                                                              // loose at most: < 2^254.3 + p
     }
     {
-        const F29<P> t = f29_mul<P>(eplain, mle_row<P, G, ANY_LEN>(d.s.b, dict, one29, d.s.b.rowptr[row], d.s.b.rowptr[row + 1], gl, ey));
+        const F29<P> t = f29_mul<P>(eplain, r1cs_row<P, G, ANY_LEN, false>(d.s.b, dict, one29, d.s.b.rowptr[row], d.s.b.rowptr[row + 1], gl, ey));
         if (lead) v[1] = t;
     }
     {
-        const F29<P> t = f29_mul<P>(eplain, mle_row<P, G, ANY_LEN>(d.s.c, dict, one29, d.s.c.rowptr[row], d.s.c.rowptr[row + 1], gl, ey));
+        const F29<P> t = f29_mul<P>(eplain, r1cs_row<P, G, ANY_LEN, false>(d.s.c, dict, one29, d.s.c.rowptr[row], d.s.c.rowptr[row + 1], gl, ey));
         if (lead) v[2] = t;
     }
 }
@@ -128,9 +70,9 @@ __global__ __launch_bounds__(FOLD_BLOCK) void sparse_mle_kernel(MleDev d, const 
     const unsigned j = blockIdx.x;
     const uint32_t tid = threadIdx.x;
     F29<P> v[3];
-    if (j < d.wide_blocks) mle_class<P, MLE_WIDE_GROUP, true>(d, d.rows, d.n_wide, j, d.wide_blocks, tid, ex, ey, v);
-    else if (j < d.wide_blocks + d.mid_blocks) mle_class<P, MLE_GROUP, false>(d, d.rows + d.n_wide, d.n_mid, j - d.wide_blocks, d.mid_blocks, tid, ex, ey, v);
-    else mle_class<P, 1, false>(d, d.rows + d.n_wide + d.n_mid, d.n_lane, j - d.wide_blocks - d.mid_blocks, d.lane_blocks, tid, ex, ey, v);
+    row_class_vblock<(int)SAT_GROUP>(d.c, j, [&](auto g, auto any_len, const uint32_t* list, uint32_t n, unsigned vb, unsigned nb) {
+        mle_class<P, decltype(g)::value, decltype(any_len)::value>(d, list, n, vb, nb, tid, ex, ey, v);
+    });
     // lanes -> wave
     const F29<P> k = f29_from_plain<P>(k266.l);  // 2^266 mod p: x -> 32 x in one Montgomery product
 #pragma unroll
@@ -188,41 +130,17 @@ __global__ __launch_bounds__(FOLD_BLOCK) void ipa_s_vector_kernel(const Fe<F>* _
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-static unsigned mle_blocks(size_t n, int group) {
-    if (!n) return 0;
-    const unsigned nb = div_up(n * group, FOLD_BLOCK);
-    return (nb + FOLD_XCDS - 1) / FOLD_XCDS * FOLD_XCDS;
-}
-
 static const MlePlan& mle_plan(const R1csShape& sh) {
     std::lock_guard<std::mutex> lk(sh.mle_mu);
     if (sh.mle) return *sh.mle;
     auto plan = std::make_unique<MlePlan>();
-    const size_t rows = sh.num_cons;
-    std::vector<uint32_t> rp[3];
     for (int w = 0; w < 3; w++) {
-        rp[w].resize(rows + 1);
-        LURK_HIP_CHECK(hipMemcpy(rp[w].data(), sh.m[w].rowptr.p, (rows + 1) * 4, hipMemcpyDeviceToHost));
-        if (sh.m[w].nnz) {
-            std::vector<uint2> ent(sh.m[w].nnz);
-            LURK_HIP_CHECK(hipMemcpy(ent.data(), sh.m[w].ent.p, sh.m[w].nnz * sizeof(uint2), hipMemcpyDeviceToHost));
-            for (const uint2& e : ent) plan->max_col = std::max<uint64_t>(plan->max_col, e.x);
-        }
+        if (!sh.m[w].nnz) continue;
+        std::vector<uint2> ent(sh.m[w].nnz);
+        LURK_HIP_CHECK(hipMemcpy(ent.data(), sh.m[w].ent.p, sh.m[w].nnz * sizeof(uint2), hipMemcpyDeviceToHost));
+        for (const uint2& e : ent) plan->max_col = std::max<uint64_t>(plan->max_col, e.x);
     }
-    std::vector<uint32_t> cls[3];  // wide, mid, lane
-    for (size_t i = 0; i < rows; i++) {
-        uint32_t len = 0;
-        for (int w = 0; w < 3; w++) len = std::max(len, rp[w][i + 1] - rp[w][i]);
-        if (!len) continue;  // a row with no entry costs nothing
-        cls[len <= MLE_LANE_MAX ? 2 : len <= MLE_MID_MAX ? 1 : 0].push_back((uint32_t)i);
-    }
-    plan->n_wide = cls[0].size();
-    plan->n_mid = cls[1].size();
-    plan->n_lane = cls[2].size();
-    cls[0].insert(cls[0].end(), cls[1].begin(), cls[1].end());
-    cls[0].insert(cls[0].end(), cls[2].begin(), cls[2].end());
-    plan->rows.alloc(cls[0].size() * 4);
-    if (!cls[0].empty()) LURK_HIP_CHECK(hipMemcpy(plan->rows.p, cls[0].data(), cls[0].size() * 4, hipMemcpyHostToDevice));
+    build_row_classes(plan->cls, sh, SAT_LANE_MAX, SAT_MID_MAX, true);  // a row with no entry costs nothing
     sh.mle = std::move(plan);
     return *sh.mle;
 }
@@ -237,14 +155,8 @@ static void sparse_mle(const R1csShape& sh, const void* d_ex, size_t n_x, const 
     for (int w = 0; w < 3; w++) out3[w] = fe_zero<P>();
     MleDev d;
     d.s = dev_view(sh);
-    d.rows = plan.rows.as<uint32_t>();
-    d.n_wide = (uint32_t)plan.n_wide;
-    d.n_mid = (uint32_t)plan.n_mid;
-    d.n_lane = (uint32_t)plan.n_lane;
-    d.wide_blocks = mle_blocks(plan.n_wide, MLE_WIDE_GROUP);
-    d.mid_blocks = mle_blocks(plan.n_mid, MLE_GROUP);
-    d.lane_blocks = mle_blocks(plan.n_lane, 1);
-    const unsigned total = d.wide_blocks + d.mid_blocks + d.lane_blocks;
+    d.c = class_view(plan.cls, (int)SAT_GROUP);
+    const unsigned total = d.c.wide_blocks + d.c.mid_blocks + d.c.lane_blocks;
     if (!total) return;
     LURK_REQUIRE(d_ex && d_ey, "null eq table");
     ArenaBuf partial(((size_t)3 * total + 3) * 32, s);

@@ -8,34 +8,14 @@ so without new scratch: the parent's kernels had 192 bytes per lane on the Pasta
 and none on the BN254 fields.  The persistent kernel has a second instantiation with the plain loop, for launches with two or more
 waves per SIMD; it keeps the parent's footprint (176 / 178 registers: granule 184 at most).  The plain launch keeps the plain loop
 and its three waves per SIMD (<= 168 registers)."""
-import os
-import re
 import shutil
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lurk_beta_amd", "csrc")
+from tests import kernel_resources as KR
+
 UNITS = ("msm_acc_persistent.hip", "msm_acc_persistent_bn254.hip", "msm_acc.hip")
-
-
-def _usage(src, out_dir):
-    r = subprocess.run(["hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-Wno-unused-variable",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(out_dir, src + ".o")], cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-800:]
-    out, name = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("agprs", r" AGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, ln)
-            if m and name:
-                out[name][key] = int(m.group(1))
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -44,7 +24,7 @@ def usage(tmp_path_factory):
         pytest.skip("hipcc not available")
     d = str(tmp_path_factory.mktemp("acc_pipeline_resources"))
     with ThreadPoolExecutor(max_workers=len(UNITS)) as ex:
-        return dict(zip(UNITS, ex.map(lambda s: _usage(s, d), UNITS)))
+        return dict(zip(UNITS, ex.map(lambda s: KR.usage(s, d), UNITS)))
 
 
 def _granule(v):

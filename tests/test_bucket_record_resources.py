@@ -7,34 +7,14 @@ commitment, with an empty list under uniform scalars; in its 8 x 32 form it took
 waited for an accumulation to end.  The accumulate kernels store a record instead of converting their sum: their budgets are the
 parent's (192 pipelined, 184 for the persistent plain loop, three waves per SIMD for the plain launch) and their scratch may not grow
 (parent: 192 bytes per lane on the Pasta fields - the frame of the out-of-line doubling - and none on the BN254 fields)."""
-import os
-import re
 import shutil
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lurk_beta_amd", "csrc")
+from tests import kernel_resources as KR
+
 UNITS = ("msm_finalize.hip", "msm_acc_persistent.hip", "msm_acc_persistent_bn254.hip", "msm_acc.hip", "msm_acc_bn254.hip")
-
-
-def _usage(src, out_dir):
-    r = subprocess.run(["hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-Wno-unused-variable",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(out_dir, src + ".o")], cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-800:]
-    out, name = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("agprs", r" AGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, ln)
-            if m and name:
-                out[name][key] = int(m.group(1))
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -43,7 +23,7 @@ def usage(tmp_path_factory):
         pytest.skip("hipcc not available")
     d = str(tmp_path_factory.mktemp("bucket_record_resources"))
     with ThreadPoolExecutor(max_workers=len(UNITS)) as ex:
-        return dict(zip(UNITS, ex.map(lambda s: _usage(s, d), UNITS)))
+        return dict(zip(UNITS, ex.map(lambda s: KR.usage(s, d), UNITS)))
 
 
 def _granule(v):

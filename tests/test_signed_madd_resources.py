@@ -21,27 +21,10 @@ from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "lurk_beta_amd", "csrc")
-FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-Wno-unused-variable"]
+from tests import kernel_resources as KR
+
+ROOT, CSRC, FLAGS = KR.ROOT, KR.CSRC, KR.FLAGS
 PARENT_VALU, PARENT_CYCLES = 2166, 8448
-
-
-def _usage(src, out_dir):
-    r = subprocess.run(["hipcc", *FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(out_dir, src + ".o")], cwd=CSRC,
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-800:]
-    out, name = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-        for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("agprs", r" AGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pat, ln)
-            if m and name:
-                out[name][key] = int(m.group(1))
-    return out
 
 
 def _listing(src, out_dir):
@@ -57,8 +40,8 @@ def built(tmp_path_factory):
         pytest.skip("hipcc not available")
     d = str(tmp_path_factory.mktemp("signed_madd_resources"))
     with ThreadPoolExecutor(max_workers=3) as ex:
-        a = ex.submit(_usage, "msm_acc_persistent.hip", d)
-        b = ex.submit(_usage, "msm_acc.hip", d)
+        a = ex.submit(KR.usage, "msm_acc_persistent.hip", d)
+        b = ex.submit(KR.usage, "msm_acc.hip", d)
         c = ex.submit(_listing, "msm_acc_persistent.hip", d)
         return {"persistent": a.result(), "plain": b.result(), "listing": c.result()}
 
