@@ -7,7 +7,11 @@ as bench_workloads/compress.py), one resident window-table key.  Reported: the m
   (b) lurk_hip_spartan_verify_dev under the same key,
   (c) the parts of (b) through the library profiler (eq_evals, sparse_mle, ipa_s_vector, the commitment's msm_* kernels) in a run of its
       own, host tail = wall - kernels,
-  (d) oracle/spartan_fast.py: verify on the CPU (OpenMP threads as OMP_NUM_THREADS says; three calls, median).
+  (d) oracle/spartan_fast.py: verify on the CPU (OpenMP threads as OMP_NUM_THREADS says; three calls, median),
+  (e) on BN254 G1, for an instance of the same size under a powers-of-tau test key (row i < n/2: w_i * u = w_{n/2 + i}, as
+      bench_tools/spartan_kzg_bench.py): lurk_hip_spartan_kzg_verify_dev, which stops before the pairing, and
+  (f) lurk_hip_spartan_kzg_verify_pairing_dev, the pairing-complete verifier, on the same proof - accepted under [tau]H and rejected
+      with LURK_VERIFY_PAIRING under [tau + 1]H before anything is timed.
 The sparse evaluation's HBM fraction is of COMPULSORY bytes (8 B per non-zero, the row pointers, both eq tables once) over 8 TB/s: not
 gather traffic."""
 import argparse
@@ -116,3 +120,31 @@ if not args.no_oracle:
     print(f"    (d) / (b) = {t_or / t_verify:.1f}")
 key.close()
 prover.close()
+
+# (e), (f): the BN254 cycle's verifier, up to the pairing and pairing-complete
+from lurk_beta_amd import SpartanKzgProver, SpartanKzgVerifier, hyperkzg, synth  # noqa: E402
+
+R_BN = hyperkzg.BN254_R
+TAU = 0x2B0F3C4D5E6F708192A3B4C5D6E7F8091A2B3C4D5E6F708192A3B4C5D6E7F809 % R_BN
+half = n // 2
+kkey = hyperkzg.trapdoor_key(TAU, n, precompute=True)
+kkey.reserve(n, 6)
+ip = np.minimum(np.arange(n + 1, dtype=np.uint64), np.uint64(half))
+one = np.tile(np.array([[((1 << 256) % R_BN >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range(4)]], dtype=np.uint64), (half, 1))
+mats = ((ip, np.arange(half, dtype=np.uint64), one), (ip, np.full(half, n, dtype=np.uint64), one), (ip, np.arange(half, n, dtype=np.uint64), one))
+free = synth.scalars(L.FIELD_BN254_FR, 31, 0, half, mont=True)
+k_W, k_E = torch.cat([free, free]).contiguous(), torch.zeros((n, 4), dtype=torch.int64, device="cuda")
+torch.cuda.synchronize()
+kcw, kce = kkey.commit_device(k_W, n, is_mont=True), kkey.commit_device(k_E, n, is_mont=True)
+kpr = SpartanKzgProver(mats, n, n, 2)
+kver = SpartanKzgVerifier.from_shape(kpr.shape)
+kproof = kpr.prove([5, 7], 1, k_W, k_E, kcw, kce, kkey)
+vk, vk_other = hyperkzg.trapdoor_vk(TAU), hyperkzg.trapdoor_vk((TAU + 1) % R_BN)
+assert kver.verify([5, 7], 1, kcw, kce, kproof)[0]
+assert kver.verify_pairing([5, 7], 1, kcw, kce, kproof, vk) and kver.last_failed_check == 0
+assert not kver.verify_pairing([5, 7], 1, kcw, kce, kproof, vk_other) and kver.last_failed_check == 6
+t_upto = line("(e) lurk_hip_spartan_kzg_verify_dev (BN254)", wall(lambda: kver.verify([5, 7], 1, kcw, kce, kproof), args.reps, args.warmup))
+t_pair = line("(f) lurk_hip_spartan_kzg_verify_pairing_dev", wall(lambda: kver.verify_pairing([5, 7], 1, kcw, kce, kproof, vk), args.reps, args.warmup))
+print(f"    (f) - (e) = {t_pair - t_upto:.3f} ms for the pairing check and the subgroup test of [tau]H;   (f) / (b) = {t_pair / t_verify:.3f}")
+kpr.close()
+kkey.close()

@@ -1018,6 +1018,48 @@ int lurk_hip_hyperkzg_pairing_inputs(int curve, int ell, const void* c_jacobian9
                                      const void* q32_canonical, const void* d32_canonical, void* out_l_jacobian96, void* out_r_jacobian96,
                                      int* accepted, int* failed_check);
 
+/* ---- the BN254 pairing check: what lets the KZG verifiers DECIDE ------------------------------------------------------------------------
+ * Host code, no device needed, and no kernel: one check is a 65-step Miller loop and one final exponentiation over twelve-limb towers,
+ * a few milliseconds on one core, once per proof (lurk_beta_amd/csrc/bn254_pairing.hpp: the optimal ate pairing over the tower
+ * Fq2 = Fq[u]/(u^2 + 1), Fq6 = Fq2[v]/(v^3 - (9 + u)), Fq12 = Fq6[w]/(w^2 - v); tests/bn254_pairing_ref.py decides the same products by
+ * another construction).  Only the DECISION crosses the ABI, never a GT element.
+ *   G2 point: the sextic twist y^2 = x^3 + 3/(9 + u) over Fq2, affine, 128 bytes {x.c0, x.c1, y.c0, y.c1}, each 4 x u64 little-endian
+ *   Montgomery (R = 2^256); all-zero is the identity.  This is halo2curves' G2Affine as recalled [MEM], unpinned like the G1 layouts.
+ *   G1 point: the 96-byte Jacobian of every other entry point.
+ * g2_mul: out = [k] P, P = the generator H of the order-r subgroup when g2_affine128 is NULL (so g2_mul(out, NULL, tau) is the verifier
+ * key [tau]H of a trapdoor setup); k a canonical scalar.  Refused: a scalar not below r, a point off the twist (a point on the twist
+ * outside the subgroup is multiplied as it is).
+ * pairing_check: *product_is_one = (prod_{i < n} e(P_i, Q_i) == 1), one Miller accumulator for the n pairs and one final
+ * exponentiation.  A pair with an identity on either side contributes 1; n = 0 gives 1.  Refused with LURK_HIP_ERR_INVALID_ARG, the
+ * message naming the index and which: a G1 point neither the identity nor on the curve; a G2 point off the twist; a G2 point on the
+ * twist but outside the order-r subgroup (the twist's cofactor is 2p - r: the curve equation alone does not put a point in G2; the test
+ * is one 254-bit multiple per point, 1.4 ms). */
+int lurk_hip_bn254_g2_mul(void* out_g2_affine128, const void* g2_affine128, const void* k32_canonical);
+int lurk_hip_bn254_pairing_check(size_t n, const void* g1_jacobian96, const void* g2_affine128, int* product_is_one);
+/* The HyperKZG verifier that decides: lurk_hip_hyperkzg_pairing_inputs (same arguments, same checks, same codes) and then
+ * e(L, H) e(-R, tau_H) == 1 against the verifier key tau_H = [tau]H.  *accepted = 1: the proof is VALID.  *failed_check (may be NULL):
+ * every failure the call above reports keeps its code; LURK_HYPERKZG_PAIRING when only the pairing equation fails; a tau_H that is off
+ * the twist, outside the order-r subgroup or the identity gives LURK_HYPERKZG_MALFORMED whatever the proof.  tau_H is tested for
+ * subgroup membership at every call (1.4 ms of the ~5 ms the pairing adds to a verification: DESIGN.md section 3.7.2); nothing is cached. */
+#define LURK_HYPERKZG_PAIRING 3 /* lurk_hip_hyperkzg_verify only: e(L, H) e(-R, [tau]H) != 1 after every other check passed */
+int lurk_hip_hyperkzg_verify(int curve, int ell, const void* c_jacobian96, const void* x32_canonical, const void* y32_canonical,
+                             const void* com_jacobian96, const void* v32_canonical, const void* w_jacobian96, const void* r32_canonical,
+                             const void* q32_canonical, const void* d32_canonical, const void* tau_h_g2_affine128, int* accepted,
+                             int* failed_check);
+/* Is a resident key a powers-of-tau key for THIS verifier key?  key: a resident BN254 G1 key of N points in any form (plain, window
+ * table, small); Grumpkin and Pasta keys are refused by name.  *consistent = 1 iff ck[0] == (1, 2) - the G the verifiers assume - and
+ * e(R, H) == e(L, tau_H) for
+ *     rho_i = uniform(stream = seed, i), the scalars lurk_hip_synth_scalars_dev(LURK_FIELD_BN254_FR, seed, dist 0, ...) writes,
+ *     L = sum_{i < N-1} rho_i ck[i],   R = sum_{i < N-1} rho_i ck[i+1]:
+ * two commitments of ONE device buffer (0, rho_0 .. rho_{N-2}, 0) from its elements 1 and 0 through the key's ordinary commitment path -
+ * no copy of the key, no kernel of its own.  N = 1 checks ck[0] only.  A key with any ck[j+1] != [tau] ck[j] passes with probability
+ * 1/r over UNIFORM weights: the seed must be chosen AFTER the key exists (a key made knowing the seed can be made to pass), and
+ * SplitMix64 is not a cryptographic generator - a caller that needs more than a file-integrity check draws its own weights.  A tau_H
+ * that is off the twist, outside the subgroup or the identity is refused (LURK_HIP_ERR_INVALID_ARG, the message naming which).  The call
+ * uses slots 0 and 1 of the key (they must be free), (N + 1) x 32 B of the stream's scratch arena, synchronises `stream`, and leaves the
+ * key usable whatever happens. */
+int lurk_hip_kzg_key_check_dev(lurk_hip_msm_ctx* key, const void* tau_h_g2_affine128, uint64_t seed, int* consistent, void* stream);
+
 /* The single-instance compressing prover as ONE call (what CompressedSNARK::prove runs per curve: /root/reference/src/proof/nova.rs:341-356
  * -> arecibo RelaxedR1CSSNARK::prove): outer cubic sum-check, inner quadratic sum-check over the transposed shape, the two evaluation claims
  * batched to one point, one inner-product argument under the resident key - a sequence of the entry points above with the vectors resident
@@ -1094,6 +1136,7 @@ int lurk_hip_spartan_prove_batch_dev(const lurk_hip_spartan_instance* instances,
 #define LURK_VERIFY_INNER 3     /* inner sum-check: a round, or its final claim against the matrices at (r_x, r_y) and eval_w */
 #define LURK_VERIFY_BATCH 4     /* the sum-check that batches the evaluation claims to one point */
 #define LURK_VERIFY_OPENING 5   /* the inner-product argument's final point equation; the _kzg_ verifiers: HyperKZG's scalar checks */
+#define LURK_VERIFY_PAIRING (6) /* the _kzg_verify_pairing verifiers only: e(L, H) e(-R, [tau]H) != 1 after every other check passed */
 /* Building block: the sparse multilinear evaluation of a resident shape, M~ = sum_i eq_x[i] sum_{k in row i} val[k] eq_y[col[k]] for
  * M = A, B, C in ONE launch over the shape's non-empty rows (SparsePolynomial::evaluate of arecibo's Spartan verifier).  d_eq_x (n_x
  * elements), d_eq_y (n_y): Montgomery, device memory - whole eq tables or their leading parts (the batched verifier passes truncated
@@ -1200,6 +1243,17 @@ int lurk_hip_spartan_kzg_verify_dev(const lurk_hip_r1cs* shape, size_t num_cons,
 int lurk_hip_spartan_kzg_verify_batch_dev(const lurk_hip_spartan_instance* instances, size_t n_instances, const void* label, size_t label_len,
                                           const lurk_hip_spartan_kzg_batch_proof* proof, void* out_l_jacobian96, void* out_r_jacobian96,
                                           int* accepted, int* failed_check, void* stream);
+/* The same two verifiers DECIDING: the calls above unchanged, then e(L, H) e(-R, tau_H) == 1 on the host (lurk_hip_bn254_pairing_check's
+ * arithmetic) against the verifier key tau_H = [tau]H, a 128-byte G2 point, in place of the two outputs.  *accepted = 1: the proof is
+ * VALID.  Every failure the calls above report keeps its code; LURK_VERIFY_PAIRING when only the pairing equation fails; a tau_H off
+ * the twist, outside the order-r subgroup or the identity gives LURK_VERIFY_MALFORMED whatever the proof. */
+int lurk_hip_spartan_kzg_verify_pairing_dev(const lurk_hip_r1cs* shape, size_t num_cons, size_t num_vars, size_t num_io, const void* x32_canonical,
+                                            const void* u32_canonical, const void* comm_w_jacobian96, const void* comm_e_jacobian96,
+                                            const void* label, size_t label_len, const lurk_hip_spartan_kzg_proof* proof,
+                                            const void* tau_h_g2_affine128, int* accepted, int* failed_check, void* stream);
+int lurk_hip_spartan_kzg_verify_pairing_batch_dev(const lurk_hip_spartan_instance* instances, size_t n_instances, const void* label,
+                                                  size_t label_len, const lurk_hip_spartan_kzg_batch_proof* proof,
+                                                  const void* tau_h_g2_affine128, int* accepted, int* failed_check, void* stream);
 
 /* ---- synthetic inputs (bench / tests) -------------------------------------
  * SplitMix64 counter mode, seed 0x4C55524B.  dist 0 = uniform, 1 = witness-like. */

@@ -17,6 +17,7 @@ from .fold import R1CSShape, fold_padded, fold_vec, fold_vecs  # noqa: E402
 from .step import FoldingContext, NivcFoldingContext, nifs_challenge, nova_ro_squeeze, point_mul, public_io  # noqa: E402
 from . import sumcheck, ipa, spartan  # noqa: E402,F401
 from . import hyperkzg  # noqa: E402,F401
+from . import pairing  # noqa: E402,F401
 from .spartan import BatchedSpartanProver, BatchedSpartanVerifier, SpartanProver, SpartanVerifier  # noqa: E402
 from . import spartan_kzg  # noqa: E402,F401
 from .spartan_kzg import BatchedSpartanKzgProver, BatchedSpartanKzgVerifier, SpartanKzgProver, SpartanKzgVerifier  # noqa: E402

@@ -227,6 +227,10 @@ SIGNATURES = {
     "lurk_hip_poly_div_linear_dev": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_int, ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
     "lurk_hip_hyperkzg_prove_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lurk_hip_hyperkzg_pairing_inputs": (c_int, [c_int, c_int] + [c_void_p] * 11 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "lurk_hip_bn254_g2_mul": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "lurk_hip_bn254_pairing_check": (c_int, [c_size_t, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
+    "lurk_hip_hyperkzg_verify": (c_int, [c_int, c_int] + [c_void_p] * 10 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "lurk_hip_kzg_key_check_dev": (c_int, [c_void_p, c_void_p, c_u64, ctypes.POINTER(c_int), c_void_p]),
     "lurk_hip_fold_padded_dev": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_void_p, c_size_t, c_void_p, c_void_p]),
     "lurk_hip_spartan_kzg_prove_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_size_t, c_void_p, c_void_p]),
@@ -235,6 +239,10 @@ SIGNATURES = {
                                                 c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]),
     "lurk_hip_spartan_kzg_verify_batch_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int),
                                                       ctypes.POINTER(c_int), c_void_p]),
+    "lurk_hip_spartan_kzg_verify_pairing_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                                        c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]),
+    "lurk_hip_spartan_kzg_verify_pairing_batch_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, ctypes.POINTER(c_int),
+                                                              ctypes.POINTER(c_int), c_void_p]),
 }
 
 

@@ -1,7 +1,8 @@
 """Host-side mirror of the HyperKZG opening argument over BN254 G1 (include/lurk_hip.h, "HyperKZG"): EE1 of lurk-beta's default engine
 Bn256EngineKZG (/root/reference/src/proof/nova.rs:65-71).  The polynomial and the commitment key stay in HBM; the transcript is a
-callback; the pairing that finishes a verification stays with the caller (``pairing_inputs`` returns its two G1 inputs).  The protocol is
-this repository's own statement of the published scheme, not arecibo's byte for byte.  Also here: the three polynomial primitives the
+callback; ``verify`` decides a proof against a verifier key [tau]H by the library's pairing check, ``pairing_inputs`` stops before the
+pairing and returns its two G1 inputs.  The protocol is this repository's own statement of the published scheme, not arecibo's byte for
+byte.  Also here: the three polynomial primitives the
 argument is made of, and the powers-of-tau key tests and benchmarks prove under."""
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ from . import _lib
 CURVE_BN254 = 2
 FIELD_BN254_FR = 2
 BN254_R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
-ACCEPTED, MALFORMED, FOLD = 0, 1, 2  # LURK_HYPERKZG_*
+ACCEPTED, MALFORMED, FOLD, PAIRING = 0, 1, 2, 3  # LURK_HYPERKZG_*
 
 
 def _limbs(v: int) -> np.ndarray:
@@ -143,15 +144,46 @@ def pairing_inputs(ell: int, c, x, y: int, com, v, w, r: int, q: int, d: int, cu
     """lurk_hip_hyperkzg_pairing_inputs (host only): the verifier up to the pairing.  c, com (ell - 1), w (3): 96-byte Jacobians as u64
     arrays; x (ell), y, v (three rows of ell), r, q, d: canonical integers.  Returns (L, R, accepted, failed_check) with L, R as
     (12,) u64 Jacobians: the proof is valid iff accepted and e(L, H) == e(R, [tau]H)."""
+    cj, xs, ys, comj, vs, wj, rs, qs, ds = _verifier_args(ell, c, x, y, com, v, w, r, q, d)
+    L, Rr = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+    acc, failed = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.load().lurk_hip_hyperkzg_pairing_inputs(curve, ell, _lib.ptr(cj), _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(comj), _lib.ptr(vs), _lib.ptr(wj), _lib.ptr(rs),
+                                                            _lib.ptr(qs), _lib.ptr(ds), _lib.ptr(L), _lib.ptr(Rr), ctypes.byref(acc), ctypes.byref(failed)))
+    return L, Rr, bool(acc.value), failed.value
+
+
+def _verifier_args(ell: int, c, x, y: int, com, v, w, r: int, q: int, d: int):
     cj = np.ascontiguousarray(c, dtype=np.uint64).reshape(12)
     comj = np.ascontiguousarray(com, dtype=np.uint64).reshape(-1, 12) if ell > 1 else np.zeros((1, 12), dtype=np.uint64)
     wj = np.ascontiguousarray(w, dtype=np.uint64).reshape(3, 12)
     flat_v = [e for row in v for e in row]
     if len(x) != ell or len(flat_v) != 3 * ell or (ell > 1 and comj.shape[0] != ell - 1):
         raise ValueError("x, v and com must hold ell, 3 ell and ell - 1 entries")
-    xs, vs, ys, rs, qs, ds = _scalars(x), _scalars(flat_v), _scalars([y]), _scalars([r]), _scalars([q]), _scalars([d])
-    L, Rr = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
+    return cj, _scalars(x), _scalars([y]), comj, _scalars(flat_v), wj, _scalars([r]), _scalars([q]), _scalars([d])
+
+
+def verify(ell: int, c, x, y: int, com, v, w, r: int, q: int, d: int, tau_h, curve: int = CURVE_BN254):
+    """lurk_hip_hyperkzg_verify (host only): the verifier that DECIDES.  The arguments of ``pairing_inputs`` and the verifier key
+    tau_h = [tau]H, a (16,) u64 G2 point (``pairing.g2_mul`` / ``trapdoor_vk``).  Returns (accepted, failed_check): accepted means the
+    proof is valid; failed_check is PAIRING when only e(L, H) == e(R, tau_h) fails."""
+    a = _verifier_args(ell, c, x, y, com, v, w, r, q, d)
+    vk = np.ascontiguousarray(tau_h, dtype=np.uint64).reshape(16)
     acc, failed = ctypes.c_int(0), ctypes.c_int(0)
-    _lib.check(_lib.load().lurk_hip_hyperkzg_pairing_inputs(curve, ell, _lib.ptr(cj), _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(comj), _lib.ptr(vs), _lib.ptr(wj), _lib.ptr(rs),
-                                                            _lib.ptr(qs), _lib.ptr(ds), _lib.ptr(L), _lib.ptr(Rr), ctypes.byref(acc), ctypes.byref(failed)))
-    return L, Rr, bool(acc.value), failed.value
+    _lib.check(_lib.load().lurk_hip_hyperkzg_verify(curve, ell, *[_lib.ptr(e) for e in a], _lib.ptr(vk), ctypes.byref(acc), ctypes.byref(failed)))
+    return bool(acc.value), failed.value
+
+
+def trapdoor_vk(tau: int) -> np.ndarray:
+    """[tau]H: the verifier key that goes with ``trapdoor_key(tau, ...)``, a (16,) u64 G2 point."""
+    from . import pairing
+
+    return pairing.g2_mul(None, int(tau) % BN254_R)
+
+
+def key_check(key, tau_h, seed: int, stream=None) -> bool:
+    """lurk_hip_kzg_key_check_dev: is the resident BN254 ``CommitmentKey`` a powers-of-tau key for the verifier key tau_h?  Two
+    commitments under the key with weights drawn from ``seed`` (choose it after the key exists) and one pairing check."""
+    vk = np.ascontiguousarray(tau_h, dtype=np.uint64).reshape(16)
+    out = ctypes.c_int(0)
+    _lib.check(_lib.load().lurk_hip_kzg_key_check_dev(key._ctx, _lib.ptr(vk), int(seed), ctypes.byref(out), _lib.ptr(_stream(stream))))
+    return bool(out.value)

@@ -1,8 +1,8 @@
 """The compressing SNARK on BN254 G1 (lurk-beta's default cycle): the Spartan sum-checks of ``spartan.py`` opened by HyperKZG, as the
 library runs them (include/lurk_hip.h: lurk_hip_spartan_kzg_prove_dev / _prove_batch_dev / _verify_dev / _verify_batch_dev).  Library
 calls only: these classes marshal, nothing of the prover is restated in Python (tests/spartan_kzg_ref.py is the independent restatement
-the tests compare with).  A verification ends UP TO THE PAIRING: ``verify`` returns the two G1 inputs L, R of e(L, H) = e(R, [tau]H),
-which stays with the caller.
+the tests compare with).  ``verify`` ends UP TO THE PAIRING and returns the two G1 inputs L, R of e(L, H) = e(R, [tau]H);
+``verify_pairing`` takes the verifier key [tau]H and decides.
 
 A proof is a dictionary: polys_outer, claims_outer, eval_E, polys_inner, eval_W, polys_batch, evals_batch as ``SpartanProver`` returns
 them (batched: evals_E, evals_W), kzg_com (log2 N - 1 points), kzg_v (3 log2 N integers, t-major), kzg_w (3 points); points are affine
@@ -19,6 +19,7 @@ from .msm import point_to_affine
 from .spartan import VERIFY_MALFORMED, _Malformed, _scalars, transpose_csr
 
 CURVE_BN254, FIELD_BN254_FR = 2, 2
+VERIFY_PAIRING = 6  # LURK_VERIFY_PAIRING
 BN254_R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 BN254_P = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
 LABEL = b"lurk-hip spartan v2bn254"
@@ -180,32 +181,57 @@ class SpartanKzgVerifier:
         self.shape, self._owns_shape, self.last_failed_check = shape, False, None
         return self
 
+    def _marshal(self, X, u, comm_W, comm_E, proof: dict):
+        """The statement and the proof in the library's layout: (proof struct, x, u, comm_W, comm_E, the arrays the struct borrows).
+        Raises _Malformed / KeyError / TypeError for what cannot be written down at all."""
+        nc, nv = self.num_cons, self.num_vars
+        ell_x, ell_y = nc.bit_length() - 1, nv.bit_length()
+        ell = max(nc, nv).bit_length() - 1
+        if any(len(p) != 4 for p in proof["polys_outer"]) or any(len(p) != 3 for p in proof["polys_inner"]) or any(len(p) != 3 for p in proof["polys_batch"]):
+            raise _Malformed
+        bufs = dict(polys_outer=_scalars([c for p in proof["polys_outer"] for c in p], 4 * ell_x), claims_outer=_scalars(proof["claims_outer"], 3),
+                    eval_e=_scalars([proof["eval_E"]], 1), polys_inner=_scalars([c for p in proof["polys_inner"] for c in p], 3 * ell_y),
+                    eval_w=_scalars([proof["eval_W"]], 1), polys_batch=_scalars([c for p in proof["polys_batch"] for c in p], 3 * ell),
+                    evals_batch=_scalars(proof["evals_batch"], 2), **_kzg_in(proof, ell))
+        x, uu = _scalars(X, self.num_io), _scalars([u], 1)
+        cw, ce = _jacobian(comm_W), _jacobian(comm_E)
+        pf = _lib.SpartanKzgProofStruct(*[bufs[k].ctypes.data for k, _ in _lib.SpartanKzgProofStruct._fields_])
+        return pf, x, uu, cw, ce, bufs
+
     def verify(self, X, u, comm_W, comm_E, proof: dict, label: bytes = LABEL, stream=None):
         """-> (accepted, L, R): accepted SO FAR; L, R: (12,) u64 Jacobians, the identity unless accepted.  The proof is valid iff accepted
         and e(L, H) == e(R, [tau]H).  The first failed check (spartan.VERIFY_*) is left in ``last_failed_check``."""
         nc, nv = self.num_cons, self.num_vars
-        ell_x, ell_y = nc.bit_length() - 1, nv.bit_length()
-        ell = max(nc, nv).bit_length() - 1
         L, Rr = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
         self.last_failed_check = VERIFY_MALFORMED
         try:
-            if any(len(p) != 4 for p in proof["polys_outer"]) or any(len(p) != 3 for p in proof["polys_inner"]) or any(len(p) != 3 for p in proof["polys_batch"]):
-                raise _Malformed
-            bufs = dict(polys_outer=_scalars([c for p in proof["polys_outer"] for c in p], 4 * ell_x), claims_outer=_scalars(proof["claims_outer"], 3),
-                        eval_e=_scalars([proof["eval_E"]], 1), polys_inner=_scalars([c for p in proof["polys_inner"] for c in p], 3 * ell_y),
-                        eval_w=_scalars([proof["eval_W"]], 1), polys_batch=_scalars([c for p in proof["polys_batch"] for c in p], 3 * ell),
-                        evals_batch=_scalars(proof["evals_batch"], 2), **_kzg_in(proof, ell))
-            x, uu = _scalars(X, self.num_io), _scalars([u], 1)
-            cw, ce = _jacobian(comm_W), _jacobian(comm_E)
+            pf, x, uu, cw, ce, _bufs = self._marshal(X, u, comm_W, comm_E, proof)
         except (_Malformed, KeyError, TypeError):
             return False, L, Rr
-        pf = _lib.SpartanKzgProofStruct(*[bufs[k].ctypes.data for k, _ in _lib.SpartanKzgProofStruct._fields_])
         acc, failed = ctypes.c_int(0), ctypes.c_int(0)
         _lib.check(_lib.load().lurk_hip_spartan_kzg_verify_dev(self.shape._h, nc, nv, self.num_io, _lib.ptr(x), _lib.ptr(uu), _lib.ptr(cw), _lib.ptr(ce), label, len(label),
                                                                ctypes.byref(pf), _lib.ptr(L), _lib.ptr(Rr), ctypes.byref(acc), ctypes.byref(failed),
                                                                _lib.ptr(_stream(stream))))
         self.last_failed_check = failed.value
         return bool(acc.value), L, Rr
+
+    def verify_pairing(self, X, u, comm_W, comm_E, proof: dict, tau_h, label: bytes = LABEL, stream=None) -> bool:
+        """The verifier that DECIDES (lurk_hip_spartan_kzg_verify_pairing_dev): ``verify`` and then e(L, H) == e(R, tau_h) against the
+        verifier key tau_h = [tau]H, a (16,) u64 G2 point.  True: the proof is valid.  ``last_failed_check`` as for ``verify``, with
+        VERIFY_PAIRING when only the pairing equation fails."""
+        nc, nv = self.num_cons, self.num_vars
+        self.last_failed_check = VERIFY_MALFORMED
+        try:
+            pf, x, uu, cw, ce, _bufs = self._marshal(X, u, comm_W, comm_E, proof)
+        except (_Malformed, KeyError, TypeError):
+            return False
+        vk = np.ascontiguousarray(tau_h, dtype=np.uint64).reshape(16)
+        acc, failed = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().lurk_hip_spartan_kzg_verify_pairing_dev(self.shape._h, nc, nv, self.num_io, _lib.ptr(x), _lib.ptr(uu), _lib.ptr(cw), _lib.ptr(ce), label,
+                                                                       len(label), ctypes.byref(pf), _lib.ptr(vk), ctypes.byref(acc), ctypes.byref(failed),
+                                                                       _lib.ptr(_stream(stream))))
+        self.last_failed_check = failed.value
+        return bool(acc.value)
 
     def close(self):
         if self._owns_shape:
@@ -221,38 +247,59 @@ class BatchedSpartanKzgVerifier:
         self.verifiers = list(verifiers)
         self.last_failed_check = None
 
-    def verify(self, instances, proof: dict, label: bytes = LABEL_BATCHED, stream=None):
-        """instances[i] = dict(X, u, comm_W, comm_E) (further keys are ignored).  -> (accepted, L, R) as ``SpartanKzgVerifier.verify``."""
+    def _marshal(self, instances, proof: dict):
+        """The instances and the proof in the library's layout: (proof struct, instance array, the arrays they borrow)."""
         n = len(self.verifiers)
         ell_x = max(v.num_cons for v in self.verifiers).bit_length() - 1
         ell_y = max(v.num_vars for v in self.verifiers).bit_length()
         ell = max(max(v.num_cons, v.num_vars) for v in self.verifiers).bit_length() - 1
+        keep, arr = [], (_lib.SpartanInstanceStruct * n)()
+        if len(instances) != n:
+            raise _Malformed
+        if any(len(p) != 4 for p in proof["polys_outer"]) or any(len(p) != 3 for p in proof["polys_inner"]) or any(len(p) != 3 for p in proof["polys_batch"]):
+            raise _Malformed
+        if len(proof["claims_outer"]) != n or any(len(c) != 3 for c in proof["claims_outer"]):
+            raise _Malformed
+        bufs = dict(polys_outer=_scalars([c for p in proof["polys_outer"] for c in p], 4 * ell_x),
+                    claims_outer=_scalars([c for cl in proof["claims_outer"] for c in cl], 3 * n), evals_e=_scalars(proof["evals_E"], n),
+                    polys_inner=_scalars([c for p in proof["polys_inner"] for c in p], 3 * ell_y), evals_w=_scalars(proof["evals_W"], n),
+                    polys_batch=_scalars([c for p in proof["polys_batch"] for c in p], 3 * ell), evals_batch=_scalars(proof["evals_batch"], 2 * n),
+                    **_kzg_in(proof, ell))
+        for i, (v, it) in enumerate(zip(self.verifiers, instances)):
+            x, uu = _scalars(it["X"], v.num_io), _scalars([it["u"]], 1)
+            cw, ce = _jacobian(it["comm_W"]), _jacobian(it["comm_E"])
+            keep += [x, uu, cw, ce]
+            arr[i] = _lib.SpartanInstanceStruct(v.shape._h.value, None, v.num_cons, v.num_vars, v.num_io, x.ctypes.data, uu.ctypes.data, None, None, cw.ctypes.data,
+                                                ce.ctypes.data)
+        pf = _lib.SpartanKzgBatchProofStruct(*[bufs[k].ctypes.data for k, _ in _lib.SpartanKzgBatchProofStruct._fields_])
+        return pf, arr, (keep, bufs)
+
+    def verify(self, instances, proof: dict, label: bytes = LABEL_BATCHED, stream=None):
+        """instances[i] = dict(X, u, comm_W, comm_E) (further keys are ignored).  -> (accepted, L, R) as ``SpartanKzgVerifier.verify``."""
+        n = len(self.verifiers)
         L, Rr = np.zeros(12, dtype=np.uint64), np.zeros(12, dtype=np.uint64)
         self.last_failed_check = VERIFY_MALFORMED
-        keep, arr = [], (_lib.SpartanInstanceStruct * n)()
         try:
-            if len(instances) != n:
-                raise _Malformed
-            if any(len(p) != 4 for p in proof["polys_outer"]) or any(len(p) != 3 for p in proof["polys_inner"]) or any(len(p) != 3 for p in proof["polys_batch"]):
-                raise _Malformed
-            if len(proof["claims_outer"]) != n or any(len(c) != 3 for c in proof["claims_outer"]):
-                raise _Malformed
-            bufs = dict(polys_outer=_scalars([c for p in proof["polys_outer"] for c in p], 4 * ell_x),
-                        claims_outer=_scalars([c for cl in proof["claims_outer"] for c in cl], 3 * n), evals_e=_scalars(proof["evals_E"], n),
-                        polys_inner=_scalars([c for p in proof["polys_inner"] for c in p], 3 * ell_y), evals_w=_scalars(proof["evals_W"], n),
-                        polys_batch=_scalars([c for p in proof["polys_batch"] for c in p], 3 * ell), evals_batch=_scalars(proof["evals_batch"], 2 * n),
-                        **_kzg_in(proof, ell))
-            for i, (v, it) in enumerate(zip(self.verifiers, instances)):
-                x, uu = _scalars(it["X"], v.num_io), _scalars([it["u"]], 1)
-                cw, ce = _jacobian(it["comm_W"]), _jacobian(it["comm_E"])
-                keep += [x, uu, cw, ce]
-                arr[i] = _lib.SpartanInstanceStruct(v.shape._h.value, None, v.num_cons, v.num_vars, v.num_io, x.ctypes.data, uu.ctypes.data, None, None, cw.ctypes.data,
-                                                    ce.ctypes.data)
+            pf, arr, _keep = self._marshal(instances, proof)
         except (_Malformed, KeyError, TypeError):
             return False, L, Rr
-        pf = _lib.SpartanKzgBatchProofStruct(*[bufs[k].ctypes.data for k, _ in _lib.SpartanKzgBatchProofStruct._fields_])
         acc, failed = ctypes.c_int(0), ctypes.c_int(0)
         _lib.check(_lib.load().lurk_hip_spartan_kzg_verify_batch_dev(ctypes.cast(arr, ctypes.c_void_p), n, label, len(label), ctypes.byref(pf), _lib.ptr(L), _lib.ptr(Rr),
                                                                      ctypes.byref(acc), ctypes.byref(failed), _lib.ptr(_stream(stream))))
         self.last_failed_check = failed.value
         return bool(acc.value), L, Rr
+
+    def verify_pairing(self, instances, proof: dict, tau_h, label: bytes = LABEL_BATCHED, stream=None) -> bool:
+        """The verifier that DECIDES (lurk_hip_spartan_kzg_verify_pairing_batch_dev): as ``SpartanKzgVerifier.verify_pairing``."""
+        n = len(self.verifiers)
+        self.last_failed_check = VERIFY_MALFORMED
+        try:
+            pf, arr, _keep = self._marshal(instances, proof)
+        except (_Malformed, KeyError, TypeError):
+            return False
+        vk = np.ascontiguousarray(tau_h, dtype=np.uint64).reshape(16)
+        acc, failed = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().lurk_hip_spartan_kzg_verify_pairing_batch_dev(ctypes.cast(arr, ctypes.c_void_p), n, label, len(label), ctypes.byref(pf), _lib.ptr(vk),
+                                                                             ctypes.byref(acc), ctypes.byref(failed), _lib.ptr(_stream(stream))))
+        self.last_failed_check = failed.value
+        return bool(acc.value)

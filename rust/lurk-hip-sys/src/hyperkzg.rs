@@ -1,7 +1,8 @@
 //! The HyperKZG opening argument of the BN254 cycle (`EE1` of lurk-beta's default `Bn256EngineKZG`,
 //! `/root/reference/src/proof/nova.rs:65-71`) over the library: the prover with the polynomial and the key resident in HBM, and the
-//! verifier up to the pairing.  The pairing itself - `e(L, H) == e(R, [tau]H)` - stays with the caller (halo2curves).  The protocol is
-//! the library's own statement of the scheme (include/lurk_hip.h), not arecibo's bytes: the transcript is the caller's closure.
+//! verifier - [`verify`] decides `e(L, H) == e(R, [tau]H)` against a [`VerifierKey`] by the library's pairing check, [`pairing_inputs`]
+//! stops before it for a caller with a pairing of its own (halo2curves).  The protocol is the library's own statement of the scheme
+//! (include/lurk_hip.h), not arecibo's bytes: the transcript is the caller's closure.
 use core::ffi::{c_int, c_void};
 
 use crate::ffi::*;
@@ -63,6 +64,47 @@ pub fn pairing_inputs(c: &[u8; 96], x: &[[u8; 32]], proof: &Proof, r: &[u8; 32],
                                          rr.as_mut_ptr().cast(), &mut accepted, &mut failed)
     })?;
     Ok((l, rr, accepted != 0, failed))
+}
+
+/// The verifier's half of a KZG setup: `tau_h = [tau]H`, a G2 point in the library's 128-byte form ({x.c0, x.c1, y.c0, y.c1}, each four
+/// little-endian u64 Montgomery limbs - halo2curves' `G2Affine` as recalled, unpinned).
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct VerifierKey {
+    pub tau_h: [u8; 128],
+}
+
+impl VerifierKey {
+    /// `[tau]H` from a canonical `tau` below the group order: a TRAPDOOR setup for tests and benchmarks only.
+    pub fn trapdoor(tau: &[u8; 32]) -> Result<Self, Error> {
+        let mut tau_h = [0u8; 128];
+        // SAFETY: out is 128 bytes, the scalar 32; a null point means the generator
+        check(unsafe { lurk_hip_bn254_g2_mul(tau_h.as_mut_ptr().cast(), core::ptr::null(), tau.as_ptr().cast()) })?;
+        Ok(VerifierKey { tau_h })
+    }
+
+    /// Is the resident BN254 G1 key a powers-of-tau key for this verifier key?  Two commitments under the key with weights drawn from
+    /// `seed` (choose it after the key exists) and one pairing check.
+    ///
+    /// # Safety
+    /// `key` must be a live context with slots 0 and 1 free.
+    pub unsafe fn key_check(&self, key: *mut lurk_hip_msm_ctx, seed: u64, stream: *mut c_void) -> Result<bool, Error> {
+        let mut consistent: c_int = 0;
+        check(lurk_hip_kzg_key_check_dev(key, self.tau_h.as_ptr().cast(), seed, &mut consistent, stream))?;
+        Ok(consistent != 0)
+    }
+}
+
+/// The verifier that DECIDES (host only): [`pairing_inputs`] and then `e(L, H) e(-R, tau_h) == 1` in the library.  `Ok(true)`: the proof
+/// is valid.
+pub fn verify(c: &[u8; 96], x: &[[u8; 32]], proof: &Proof, r: &[u8; 32], q: &[u8; 32], d: &[u8; 32], vk: &VerifierKey) -> Result<bool, Error> {
+    let (mut accepted, mut failed): (c_int, c_int) = (0, 0);
+    let ell = x.len() as c_int;
+    // SAFETY: every pointer is a live host buffer of the size the header states for `ell`
+    check(unsafe {
+        lurk_hip_hyperkzg_verify(LURK_CURVE_BN254, ell, c.as_ptr().cast(), x.as_ptr().cast(), proof.y.as_ptr().cast(), proof.com.as_ptr().cast(), proof.v.as_ptr().cast(),
+                                 proof.w.as_ptr().cast(), r.as_ptr().cast(), q.as_ptr().cast(), d.as_ptr().cast(), vk.tau_h.as_ptr().cast(), &mut accepted, &mut failed)
+    })?;
+    Ok(accepted != 0)
 }
 
 /// `[tau^(first + i)]G` for i < n into device memory (64-byte affine records): a TRAPDOOR setup for tests and benchmarks only.

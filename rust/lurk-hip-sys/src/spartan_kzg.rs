@@ -1,6 +1,7 @@
 //! The compressing SNARK on BN254 G1 (lurk-beta's default cycle): the Spartan sum-checks of [`crate::spartan_prove`] opened by the
-//! HyperKZG argument of [`crate::hyperkzg`], each as one library call with the Keccak transcript inside.  A verification ends UP TO THE
-//! PAIRING: the verifier returns `(verdict, L, R)` and the proof is valid iff `verdict.accepted` and
+//! HyperKZG argument of [`crate::hyperkzg`], each as one library call with the Keccak transcript inside.  [`verify_pairing`] /
+//! [`verify_pairing_batch`] DECIDE against a [`VerifierKey`] by the library's own pairing check.  [`verify`] / [`verify_batch`] end UP TO
+//! THE PAIRING for a caller that has its own: they return `(verdict, L, R)` and the proof is valid iff `verdict.accepted` and
 //!
 //! ```ignore
 //! use halo2curves::bn256::{pairing, G1Affine, G2Affine};
@@ -8,11 +9,12 @@
 //! pairing(&l, &h) == pairing(&r, &tau_h)
 //! ```
 //!
-//! which stays on the Rust side (G2 never reaches the library).  The protocol is the library's own (include/lurk_hip.h, DESIGN.md section
+//! on the Rust side.  The protocol is the library's own (include/lurk_hip.h, DESIGN.md section
 //! 3.7.3), not arecibo's byte for byte.
 use core::ffi::{c_int, c_void};
 
 use crate::ffi::*;
+use crate::hyperkzg::VerifierKey;
 use crate::{check, Error, R1csShape, Verdict};
 
 /// The proof of [`prove`]: the seven sum-check fields of [`crate::SpartanProof`], then HyperKZG's.
@@ -49,6 +51,43 @@ fn batch_ells(instances: &[lurk_hip_spartan_instance]) -> (usize, usize, usize) 
     let max_nc = instances.iter().map(|i| i.num_cons).max().unwrap_or(2);
     let max_nv = instances.iter().map(|i| i.num_vars).max().unwrap_or(2);
     (log2(max_nc), log2(max_nv) + 1, log2(max_nc.max(max_nv)))
+}
+
+impl Proof {
+    /// Every field has the length the header states for this shape.
+    fn well_sized(&self, num_cons: usize, num_vars: usize) -> bool {
+        let (ell_x, ell_y, ell) = (log2(num_cons), log2(num_vars) + 1, log2(num_cons.max(num_vars)));
+        self.polys_outer.len() == ell_x * 128 && self.polys_inner.len() == ell_y * 96 && self.polys_batch.len() >= ell * 96
+            && self.kzg_com.len() == ell.saturating_sub(1) * 96 && self.kzg_v.len() == 3 * ell * 32
+    }
+    /// The proof as the verifiers take it (the library only reads through these pointers).
+    fn as_ffi(&self) -> lurk_hip_spartan_kzg_proof {
+        lurk_hip_spartan_kzg_proof {
+            polys_outer: self.polys_outer.as_ptr() as *mut c_void, claims_outer: self.claims_outer.as_ptr() as *mut c_void, eval_e: self.eval_e.as_ptr() as *mut c_void,
+            polys_inner: self.polys_inner.as_ptr() as *mut c_void, eval_w: self.eval_w.as_ptr() as *mut c_void, polys_batch: self.polys_batch.as_ptr() as *mut c_void,
+            evals_batch: self.evals_batch.as_ptr() as *mut c_void,
+            kzg_com: if self.kzg_com.is_empty() { core::ptr::null_mut() } else { self.kzg_com.as_ptr() as *mut c_void }, kzg_v: self.kzg_v.as_ptr() as *mut c_void,
+            kzg_w: self.kzg_w.as_ptr() as *mut c_void,
+        }
+    }
+}
+impl BatchProof {
+    fn well_sized(&self, instances: &[lurk_hip_spartan_instance]) -> bool {
+        let n = instances.len();
+        let (ell_x, ell_y, ell) = batch_ells(instances);
+        self.polys_outer.len() == ell_x * 128 && self.claims_outer.len() == n * 96 && self.evals_e.len() == n * 32 && self.polys_inner.len() == ell_y * 96
+            && self.evals_w.len() == n * 32 && self.polys_batch.len() >= ell * 96 && self.evals_batch.len() == 2 * n * 32
+            && self.kzg_com.len() == ell.saturating_sub(1) * 96 && self.kzg_v.len() == 3 * ell * 32
+    }
+    fn as_ffi(&self) -> lurk_hip_spartan_kzg_batch_proof {
+        lurk_hip_spartan_kzg_batch_proof {
+            polys_outer: self.polys_outer.as_ptr() as *mut c_void, claims_outer: self.claims_outer.as_ptr() as *mut c_void, evals_e: self.evals_e.as_ptr() as *mut c_void,
+            polys_inner: self.polys_inner.as_ptr() as *mut c_void, evals_w: self.evals_w.as_ptr() as *mut c_void, polys_batch: self.polys_batch.as_ptr() as *mut c_void,
+            evals_batch: self.evals_batch.as_ptr() as *mut c_void,
+            kzg_com: if self.kzg_com.is_empty() { core::ptr::null_mut() } else { self.kzg_com.as_ptr() as *mut c_void }, kzg_v: self.kzg_v.as_ptr() as *mut c_void,
+            kzg_w: self.kzg_w.as_ptr() as *mut c_void,
+        }
+    }
 }
 
 /// `lurk_hip_spartan_kzg_prove_dev`.  `key`: the resident BN254 G1 powers-of-tau key that committed W and E.
@@ -103,20 +142,11 @@ pub unsafe fn prove_batch(instances: &[lurk_hip_spartan_instance], key: *mut lur
 #[allow(clippy::too_many_arguments)]
 pub unsafe fn verify(shape: &R1csShape, num_cons: usize, num_vars: usize, x: &[u8], u: &[u8; 32], comm_w: &[u8; 96], comm_e: &[u8; 96], label: &[u8], proof: &Proof,
                      stream: *mut c_void) -> Result<(Verdict, [u8; 96], [u8; 96]), Error> {
-    let (ell_x, ell_y, ell) = (log2(num_cons), log2(num_vars) + 1, log2(num_cons.max(num_vars)));
     let (mut l, mut r) = ([0u8; 96], [0u8; 96]);
-    if proof.polys_outer.len() != ell_x * 128 || proof.polys_inner.len() != ell_y * 96 || proof.polys_batch.len() < ell * 96
-        || proof.kzg_com.len() != ell.saturating_sub(1) * 96 || proof.kzg_v.len() != 3 * ell * 32 || x.len() % 32 != 0 {
+    if !proof.well_sized(num_cons, num_vars) || x.len() % 32 != 0 {
         return Ok((Verdict { accepted: false, failed_check: LURK_VERIFY_MALFORMED }, l, r));
     }
-    // (the library only reads through these pointers)
-    let pf = lurk_hip_spartan_kzg_proof {
-        polys_outer: proof.polys_outer.as_ptr() as *mut c_void, claims_outer: proof.claims_outer.as_ptr() as *mut c_void, eval_e: proof.eval_e.as_ptr() as *mut c_void,
-        polys_inner: proof.polys_inner.as_ptr() as *mut c_void, eval_w: proof.eval_w.as_ptr() as *mut c_void, polys_batch: proof.polys_batch.as_ptr() as *mut c_void,
-        evals_batch: proof.evals_batch.as_ptr() as *mut c_void,
-        kzg_com: if proof.kzg_com.is_empty() { core::ptr::null_mut() } else { proof.kzg_com.as_ptr() as *mut c_void }, kzg_v: proof.kzg_v.as_ptr() as *mut c_void,
-        kzg_w: proof.kzg_w.as_ptr() as *mut c_void,
-    };
+    let pf = proof.as_ffi();
     let (mut accepted, mut failed): (c_int, c_int) = (0, 0);
     check(lurk_hip_spartan_kzg_verify_dev(shape.as_ptr(), num_cons, num_vars, x.len() / 32, x.as_ptr().cast(), u.as_ptr().cast(), comm_w.as_ptr().cast(),
                                           comm_e.as_ptr().cast(), label.as_ptr().cast(), label.len(), &pf, l.as_mut_ptr().cast(), r.as_mut_ptr().cast(), &mut accepted,
@@ -130,24 +160,48 @@ pub unsafe fn verify(shape: &R1csShape, num_cons: usize, num_vars: usize, x: &[u
 pub unsafe fn verify_batch(instances: &[lurk_hip_spartan_instance], label: &[u8], proof: &BatchProof, stream: *mut c_void)
                            -> Result<(Verdict, [u8; 96], [u8; 96]), Error> {
     let n = instances.len();
-    let (ell_x, ell_y, ell) = batch_ells(instances);
     let (mut l, mut r) = ([0u8; 96], [0u8; 96]);
-    if proof.polys_outer.len() != ell_x * 128 || proof.claims_outer.len() != n * 96 || proof.evals_e.len() != n * 32 || proof.polys_inner.len() != ell_y * 96
-        || proof.evals_w.len() != n * 32 || proof.polys_batch.len() < ell * 96 || proof.evals_batch.len() != 2 * n * 32
-        || proof.kzg_com.len() != ell.saturating_sub(1) * 96 || proof.kzg_v.len() != 3 * ell * 32 {
+    if !proof.well_sized(instances) {
         return Ok((Verdict { accepted: false, failed_check: LURK_VERIFY_MALFORMED }, l, r));
     }
-    let pf = lurk_hip_spartan_kzg_batch_proof {
-        polys_outer: proof.polys_outer.as_ptr() as *mut c_void, claims_outer: proof.claims_outer.as_ptr() as *mut c_void, evals_e: proof.evals_e.as_ptr() as *mut c_void,
-        polys_inner: proof.polys_inner.as_ptr() as *mut c_void, evals_w: proof.evals_w.as_ptr() as *mut c_void, polys_batch: proof.polys_batch.as_ptr() as *mut c_void,
-        evals_batch: proof.evals_batch.as_ptr() as *mut c_void,
-        kzg_com: if proof.kzg_com.is_empty() { core::ptr::null_mut() } else { proof.kzg_com.as_ptr() as *mut c_void }, kzg_v: proof.kzg_v.as_ptr() as *mut c_void,
-        kzg_w: proof.kzg_w.as_ptr() as *mut c_void,
-    };
+    let pf = proof.as_ffi();
     let (mut accepted, mut failed): (c_int, c_int) = (0, 0);
     check(lurk_hip_spartan_kzg_verify_batch_dev(instances.as_ptr(), n, label.as_ptr().cast(), label.len(), &pf, l.as_mut_ptr().cast(), r.as_mut_ptr().cast(),
                                                 &mut accepted, &mut failed, stream))?;
     Ok((Verdict { accepted: accepted != 0, failed_check: failed }, l, r))
+}
+
+/// `lurk_hip_spartan_kzg_verify_pairing_dev`: the verifier that DECIDES - [`verify`] and then `e(L, H) e(-R, [tau]H) == 1` in the library
+/// against `vk`.  `Ok(true)`: the proof is valid.
+/// # Safety
+/// As [`verify`].
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn verify_pairing(shape: &R1csShape, num_cons: usize, num_vars: usize, x: &[u8], u: &[u8; 32], comm_w: &[u8; 96], comm_e: &[u8; 96], label: &[u8],
+                             proof: &Proof, vk: &VerifierKey, stream: *mut c_void) -> Result<bool, Error> {
+    if !proof.well_sized(num_cons, num_vars) || x.len() % 32 != 0 {
+        return Ok(false);
+    }
+    let pf = proof.as_ffi();
+    let (mut accepted, mut failed): (c_int, c_int) = (0, 0);
+    check(lurk_hip_spartan_kzg_verify_pairing_dev(shape.as_ptr(), num_cons, num_vars, x.len() / 32, x.as_ptr().cast(), u.as_ptr().cast(), comm_w.as_ptr().cast(),
+                                                  comm_e.as_ptr().cast(), label.as_ptr().cast(), label.len(), &pf, vk.tau_h.as_ptr().cast(), &mut accepted, &mut failed,
+                                                  stream))?;
+    Ok(accepted != 0)
+}
+
+/// `lurk_hip_spartan_kzg_verify_pairing_batch_dev`: [`verify_batch`] and the pairing check.  `Ok(true)`: the proof is valid.
+/// # Safety
+/// As [`verify_batch`].
+pub unsafe fn verify_pairing_batch(instances: &[lurk_hip_spartan_instance], label: &[u8], proof: &BatchProof, vk: &VerifierKey, stream: *mut c_void)
+                                   -> Result<bool, Error> {
+    if !proof.well_sized(instances) {
+        return Ok(false);
+    }
+    let pf = proof.as_ffi();
+    let (mut accepted, mut failed): (c_int, c_int) = (0, 0);
+    check(lurk_hip_spartan_kzg_verify_pairing_batch_dev(instances.as_ptr(), instances.len(), label.as_ptr().cast(), label.len(), &pf, vk.tau_h.as_ptr().cast(),
+                                                        &mut accepted, &mut failed, stream))?;
+    Ok(accepted != 0)
 }
 
 /// `lurk_hip_fold_padded_dev`: `d_out[j] = sum_k c_k (j < lens[k] ? d_vecs[k][j] : 0)` for `j < n_out` in one launch.
