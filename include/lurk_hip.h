@@ -73,7 +73,7 @@ const char* lurk_hip_version(void);
  * that reports >= n until a revision says otherwise.  4: the verifiers - lurk_hip_r1cs_sparse_mle_dev, lurk_hip_ipa_s_vector_dev,
  * lurk_hip_sumcheck_verify, lurk_hip_ipa_verify_dev, lurk_hip_spartan_verify_dev, lurk_hip_spartan_verify_batch_dev (additions only);
  * later additions under the same number (a binding probes for them by symbol): lurk_hip_r1cs_transpose_dev, lurk_hip_r1cs_read,
- * lurk_hip_grid_cus.
+ * lurk_hip_grid_cus, the four lurk_hip_trie_circuit_* calls.
  * 3: lurk_hip_slot_constraints_size / lurk_hip_slot_constraints,
  * lurk_hip_frames_r1cs_create, lurk_hip_r1cs_is_sat_dev (additions only).  2 (round 6): lurk_hip_msm_ctx_info's *precomputed is a boolean (the key's form comes from lurk_hip_msm_ctx_form),
  * LURK_MSM_SLOTS is 6, LURK_MSM_SUBMIT_FOLLOW, the parameter blocks lurk_hip_ro_params / lurk_hip_ck_params, lurk_hip_scratch_trim.
@@ -599,6 +599,62 @@ int lurk_hip_frames_r1cs_create(lurk_hip_r1cs** shape, int field_id, size_t num_
                                 size_t frame_len, size_t num_vars, size_t num_io, size_t extra_cons, const uint64_t* xa_indptr,
                                 const uint64_t* xa_indices, const void* xa_data, const uint64_t* xb_indptr, const uint64_t* xb_indices,
                                 const void* xb_data, const uint64_t* xc_indptr, const uint64_t* xc_indices, const void* xc_data);
+
+/* ---- the trie coprocessor's step circuits: witness on the device, rows, resident shape --------------------------------------------
+ * LookupCoprocessor and InsertCoprocessor are NIVC step circuits whose bodies are Trie::synthesize_lookup and Trie::synthesize_insert
+ * (/root/reference/src/coprocessor/trie/mod.rs:652-714, 802-880).  These calls cover exactly those two functions, given allocated_root, key
+ * (and value): the block of W they allocate and the rows they enforce.  The wrappers around them (synthesize_*_aux: the
+ * allocated_root_value allocation, implies_equal under not_dummy, the AllocatedPtr tags, the globals) stay with the host, as the non-slot
+ * body of a frame does, and arrive as extra_cons.  Arity 8, H = 1 .. 85, fields LURK_FIELD_PALLAS_FP, _PALLAS_FQ and _BN254_FR.
+ * LOOKUP block, local columns in allocation order; B = lurk_hip_slot_witness_size(LURK_SLOT_BIT_DECOMP) (301 / 298 / 354 for field 0 / 1 /
+ * 2), size = 1 + B + 403 H:
+ *     0                      allocated_root
+ *     1 .. B                 the bit-decomposition slot block of the key (synthesize_path, :611-629), as lurk_hip_slot_witness* writes it
+ *     1 + B + 403 i + ...    level i = 0 .. H - 1, root level first: the hash8 slot block of path preimage i (396: [8 preimage | 387 S-box
+ *                            aux | digest]), then the seven picks of select (/root/reference/src/circuit/gadgets/constraints.rs:334-391):
+ *                            three rounds of 4, 2 and 1 picks, round r on the digit's bit 2 - r, pick (r, j) taking a = state[half + j],
+ *                            b = state[j]; a pick's value is a copy of one of its inputs
+ *   The digit of level i is key bits 3 (H - 1 - i) .. + 2; bits at and above the field's NUM_BITS are Boolean::Constant(false) (BN254 at
+ *   H = 85 only: bit 254).  result_col (`found`) is the last pick of level H - 1.
+ * LOOKUP rows, emission order, Rb + 396 H of them (Rb = the bit-decomposition slot's rows): that slot's rows; then per level the 388
+ * hash8 slot rows, hashed * 1 = next (enforce_equal, constraints.rs:14-31; next = the root at level 0, else the previous level's last pick)
+ * and seven pick rows (b - a) * cond = (b - c), B an empty row where cond is the constant false.
+ * INSERT = the lookup block and rows (synthesize_insert_at_path runs the lookup first), then value_col - one element for the new value -
+ * and, from the leaf level upward (synthesize_modify_value_at_path, :846-880), the hash8 slot block (396) and rows (388) of that level's new
+ * preimage: size = size_lookup + 1 + 396 H, Rb + 784 H rows, result_col = the last digest (the new root).  As in the reference, no row
+ * ties a new preimage's entries to the old preimage, to the value or to the digest below it: synthesize_modify_value_at_path allocates
+ * them with those values and enforces nothing.
+ * Rows follow the slot rows' contract: columns ascending within a row, no coefficient that reduces to zero, an empty linear combination
+ * is an empty CSR row, local column `size` is the constant ONE.  The two inner gadgets are the slot gadgets' rows relocated. */
+#define LURK_TRIE_CIRCUIT_LOOKUP 0
+#define LURK_TRIE_CIRCUIT_INSERT 1
+/* host only.  value_col: the new value's column (insert); not written, and may be NULL, for a lookup.  Every other output is required. */
+int lurk_hip_trie_circuit_size(int field_id, int height, int op, size_t* size, size_t* num_cons, size_t* nnz_a, size_t* nnz_b, size_t* nnz_c,
+                               size_t* result_col, size_t* value_col);
+/* host only: the rows as three CSR matrices {indptr (num_cons + 1), indices, data (32 B Montgomery)}; every output is required */
+int lurk_hip_trie_circuit_constraints(int field_id, int height, int op, uint64_t* a_indptr, uint64_t* a_indices, void* a_data, uint64_t* b_indptr,
+                                      uint64_t* b_indices, void* b_data, uint64_t* c_indptr, uint64_t* c_indices, void* c_data);
+/* A resident shape of n_blocks such circuits, block b's rows relocated to columns first + b * stride (rows block-major), ONE mapped to
+ * column num_vars (the u position of z = [W | u | X]); the caller's extra_cons rows over the num_vars + 1 + num_io columns (nine CSR
+ * pointers, all NULL when extra_cons == 0) are appended unchanged.  Refusals before any allocation and the result - an ordinary
+ * lurk_hip_r1cs - as for lurk_hip_frames_r1cs_create. */
+int lurk_hip_trie_circuit_r1cs_create(lurk_hip_r1cs** shape, int field_id, int height, int op, size_t n_blocks, size_t first, size_t stride,
+                                      size_t num_vars, size_t num_io, size_t extra_cons, const uint64_t* xa_indptr, const uint64_t* xa_indices,
+                                      const void* xa_data, const uint64_t* xb_indptr, const uint64_t* xb_indices, const void* xb_data,
+                                      const uint64_t* xc_indptr, const uint64_t* xc_indices, const void* xc_data);
+/* The blocks of m circuits, written as 32-byte Montgomery values: block i at d_w[d_offsets[i]] (device array) or, with d_offsets == NULL,
+ * at d_w[first + i * stride].  Inputs are canonical 32 B on the device, as the trie calls leave them: lurk_hip_trie_prove_lookup_dev's
+ * d_paths as d_old_paths; lurk_hip_trie_prove_insert_dev's and lurk_hip_trie_insert_chain_dev's d_old_paths / d_new_paths (m * H * 8
+ * elements, root level first).  Block i's root is d_roots32[i * root_stride], root_stride 0 (one root for every block) or 1.  For a
+ * CHAIN the root of block i is the root of T_i: the caller passes [root(T_0), then lurk_hip_trie_insert_chain_dev's d_roots32[0 .. m - 2]]
+ * with root_stride 1.  For a lookup d_new_values32 and d_new_paths must be NULL.
+ * The call does not judge the proof: it writes what synthesis would allocate from these inputs, and a wrong proof gives a W the rows do
+ * not accept.  Inputs are not checked to be reduced.  Work: m H hash8 traces (2 m H for an insert), each reading its preimage from the
+ * path buffer, in two launches whatever m and H.  Refused before any launch: an unknown field, op or height, a NULL buffer with m > 0,
+ * m > 2^28, a stride shorter than a block.  Does not synchronise. */
+int lurk_hip_trie_circuit_witness_dev(int field_id, int height, int op, const void* d_roots32, size_t root_stride, const void* d_keys32,
+                                      const void* d_new_values32, const void* d_old_paths, const void* d_new_paths, size_t m, void* d_w,
+                                      const uint64_t* d_offsets, size_t first, size_t stride, void* stream);
 
 /* ---- NTT ---------------------------------------------------------------------------------
  * No reference counterpart: radix-2 NTT over a Pasta field, natural order in

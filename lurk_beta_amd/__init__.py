@@ -23,6 +23,7 @@ from . import spartan_kzg  # noqa: E402,F401
 from .spartan_kzg import BatchedSpartanKzgProver, BatchedSpartanKzgVerifier, SpartanKzgProver, SpartanKzgVerifier  # noqa: E402
 from . import params  # noqa: E402,F401
 from .trie import DeviceTrie, Trie, verify_insert, verify_lookup  # noqa: E402
+from . import trie_circuit  # noqa: E402,F401
 from .witness import MultiFrameWitness, slot_constraints, slot_witness, slot_witness_size  # noqa: E402
 from .store_resident import DeviceStore  # noqa: E402
 

@@ -143,6 +143,11 @@ SIGNATURES = {
     "lurk_hip_slot_constraints_size": (c_int, [c_int, c_int] + [ctypes.POINTER(c_size_t)] * 4),
     "lurk_hip_slot_constraints": (c_int, [c_int, c_int] + [c_void_p] * 9),
     "lurk_hip_frames_r1cs_create": (c_int, [ctypes.POINTER(c_void_p), c_int, c_size_t, ctypes.POINTER(c_size_t), c_size_t, c_size_t, c_size_t, c_size_t, c_size_t] + [c_void_p] * 9),
+    "lurk_hip_trie_circuit_size": (c_int, [c_int, c_int, c_int] + [ctypes.POINTER(c_size_t)] * 7),
+    "lurk_hip_trie_circuit_constraints": (c_int, [c_int, c_int, c_int] + [c_void_p] * 9),
+    "lurk_hip_trie_circuit_r1cs_create": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_size_t, c_size_t, c_size_t, c_size_t, c_size_t, c_size_t] + [c_void_p] * 9),
+    "lurk_hip_trie_circuit_witness_dev": (c_int, [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                                  c_size_t, c_void_p]),
     "lurk_hip_witness_blocks_dev": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_int, c_size_t, c_size_t, c_void_p]),
     "lurk_hip_ntt": (c_int, [c_int, c_void_p, c_uint, c_int]),
     "lurk_hip_ntt_dev": (c_int, [c_int, c_void_p, c_uint, c_int, c_void_p]),

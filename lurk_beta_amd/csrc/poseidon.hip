@@ -15,12 +15,9 @@
 #include "poseidon.cuh"
 #include "poseidon29.cuh"
 #include "poseidon_params.hpp"
+#include "poseidon_trace.cuh"
 
 namespace lurk {
-
-constexpr int POSEIDON_BLOCK = 256;
-constexpr size_t POSEIDON_WIDE_MAX = 8192;  // batches up to this size run one state across T lanes (latency), larger ones one per lane
-enum : int { PF_IN_MONT = 1, PF_OUT_MONT = 2 };
 
 template <class P, int T>
 __global__ __launch_bounds__(POSEIDON_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void poseidon_batch_kernel(const uint4* __restrict__ pre, uint4* __restrict__ out,
@@ -60,16 +57,6 @@ __global__ __launch_bounds__(POSEIDON_BLOCK) __attribute__((amdgpu_waves_per_eu(
 //   partial round  x = sbox(s_0) is broadcast; lane e forms its term of the sparse row (x n00 | s_e v_e), the T
 //                  reduced terms are summed across the group into lane 0; lane e >= 1 adds x w_e to its element
 // ~450 product-times per hash instead of ~1 600.  Same constants, same image, bit-identical digests.
-template <class P>
-__device__ __forceinline__ F29<P> grp_fetch(const F29<P>& v, int src_lane) {
-    F29<P> r;
-#pragma unroll
-    for (int k = 0; k < 9; k++) r.l[k] = __shfl(v.l[k], src_lane);
-    return r;
-}
-
-constexpr int POSEIDON_WIDE_BLOCK = 256;
-
 template <class P, int T>
 __global__ __launch_bounds__(POSEIDON_WIDE_BLOCK) void poseidon_wide_kernel(const uint4* __restrict__ pre, uint4* __restrict__ out, size_t n,
                                                                               const uint4* __restrict__ img, int img_vec4, int rf, int rp,
@@ -158,147 +145,7 @@ __global__ __launch_bounds__(POSEIDON_WIDE_BLOCK) void poseidon_wide_kernel(cons
 // (block of slot i at element d_offsets[i], or first + i * stride), so the ~85 % of W that is Poseidon trace never
 // crosses PCIe.  Same two kernel shapes as the batch hasher: T lanes per hash for the small batches of a folding step
 // (every lane emits the triple of its own S-box), one hash per lane for large ones.
-template <class P>
-__device__ __forceinline__ void trace_store(Fe<P>* __restrict__ w, size_t idx, const F29<P>& v) {
-    const Fe<P> d = f29_to_mont256<P>(v);
-    uint4* dst = reinterpret_cast<uint4*>(w + idx);
-    dst[0] = make_uint4(d.l[0], d.l[1], d.l[2], d.l[3]);
-    dst[1] = make_uint4(d.l[4], d.l[5], d.l[6], d.l[7]);
-}
-struct TraceDst {
-    void* w;                  // Fe<P>*: the witness vector
-    const uint64_t* offsets;  // per-slot element offsets, or null
-    size_t first, stride;     // ... then first + (i / group) * group_stride + (i % group) * stride
-    size_t group = ~(size_t)0, group_stride = 0;  // slots per frame and frame length (frame-major slot numbering)
-    __device__ __forceinline__ size_t base(size_t i) const {
-        return offsets ? (size_t)offsets[i] : first + (i / group) * group_stride + (i % group) * stride;
-    }
-};
-
-template <class P, int T>
-__global__ __launch_bounds__(POSEIDON_WIDE_BLOCK) void poseidon_trace_wide_kernel(const uint4* __restrict__ pre, size_t n, const uint4* __restrict__ img,
-                                                                                    int img_vec4, int rf, int rp, int flags, TraceDst dst) {
-    extern __shared__ uint4 lds[];
-    for (int i = threadIdx.x; i < img_vec4; i += POSEIDON_WIDE_BLOCK) lds[i] = img[i];
-    __syncthreads();
-    const uint32_t* C = reinterpret_cast<const uint32_t*>(lds);
-    const PoseidonLayout<T> L(rf, rp);
-    const uint32_t* mont2 = C + (size_t)L.total() * P29_STRIDE;
-    const uint32_t* post = mont2 + P29_STRIDE;
-    constexpr int G = 64 / T, A = T - 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool in_group = lane < G * T;
-    const int g = in_group ? lane / T : 0, e = in_group ? lane % T : 0;
-    const int base = g * T;
-    const size_t h = ((size_t)blockIdx.x * (POSEIDON_WIDE_BLOCK / 64) + wave) * G + g;
-    const bool live = in_group && h < n;
-    Fe<P>* w = (Fe<P>*)dst.w;
-    const size_t wb = live ? dst.base(h) : 0;
-
-    F29<P> s;
-    if (e == 0) {
-        s = ld_const29<P>(C);
-    } else {
-        Fe<P> x = fe_zero<P>();
-        if (live) {
-            const uint4* src = pre + (h * A + (e - 1)) * 2;
-            uint4 lo = src[0], hi = src[1];
-            x.l[0] = lo.x; x.l[1] = lo.y; x.l[2] = lo.z; x.l[3] = lo.w;
-            x.l[4] = hi.x; x.l[5] = hi.y; x.l[6] = hi.z; x.l[7] = hi.w;
-        }
-        s = (flags & PF_IN_MONT) ? f29_from_mont256<P>(x) : poseidon29_from_canonical<P>(x.l, mont2);
-        if (live) trace_store<P>(w, wb + (e - 1), s);  // the preimage opens the block
-    }
-    int sbox = 0;  // S-boxes before the current round
-    auto sbox_emit = [&](const F29<P>& l, int idx, bool mine) {
-        const F29<P> l2 = f29_sqr<P>(l), l4 = f29_sqr<P>(l2), l5 = f29_mul<P>(l4, l);
-        if (mine) {
-            const size_t o = wb + A + 3 * (size_t)idx;
-            trace_store<P>(w, o, l2);
-            trace_store<P>(w, o + 1, l4);
-            trace_store<P>(w, o + 2, f29_add<P>(l5, ld_const29<P>(post + (size_t)idx * P29_STRIDE)));
-        }
-        return l5;
-    };
-    auto full_round = [&](const uint32_t* rc, const uint32_t* mat) {
-        s = sbox_emit(f29_carry<P>(f29_add<P>(s, ld_const29<P>(rc + e * P29_STRIDE))), sbox + e, live);
-        sbox += T;
-        Dot29<P> acc;
-        dot29_init<P>(acc);
-#pragma unroll
-        for (int i = 0; i < T; i++) {
-            if (T > 5 && i == 4) dot29_carry<P>(acc);
-            dot29_mac<P>(acc, grp_fetch<P>(s, base + i), ld_const29<P>(mat + (e * T + i) * P29_STRIDE));
-        }
-        s = dot29_finish<P>(acc);
-    };
-    const uint32_t* mds = C + L.mds() * P29_STRIDE;
-#pragma unroll 1
-    for (int r = 0; r < L.h; r++) full_round(C + (L.rc1() + r * T) * P29_STRIDE, r == L.h - 1 ? C + L.pre() * P29_STRIDE : mds);
-#pragma unroll 1
-    for (int p = 0; p < rp; p++) {
-        const uint32_t* sp = C + (L.sp() + p * (2 * T - 1)) * P29_STRIDE;
-        const F29<P> xl = sbox_emit(f29_carry<P>(f29_add<P>(s, ld_const29<P>(C + (L.pk() + p) * P29_STRIDE))), sbox, live && e == 0);
-        sbox += 1;
-        const F29<P> x = grp_fetch<P>(xl, base);
-        F29<P> a;
-#pragma unroll
-        for (int k = 0; k < 9; k++) a.l[k] = e == 0 ? x.l[k] : s.l[k];
-        F29<P> term = f29_mul<P>(a, ld_const29<P>(sp + e * P29_STRIDE));
-#pragma unroll
-        for (int off = 1; off < T; off <<= 1) {
-#pragma unroll
-            for (int k = 0; k < 9; k++) {
-                uint32_t t = __shfl_down(term.l[k], off);
-                if (e + off < T) term.l[k] += t;
-            }
-            if (off == 2 || off * 2 >= T) term = f29_carry<P>(term);
-        }
-        const F29<P> upd = f29_carry<P>(f29_add<P>(s, f29_mul<P>(x, ld_const29<P>(sp + (T - 1 + e) * P29_STRIDE))));
-#pragma unroll
-        for (int k = 0; k < 9; k++) s.l[k] = e == 0 ? term.l[k] : upd.l[k];
-    }
-#pragma unroll 1
-    for (int r = 0; r < L.h; r++) full_round(r == 0 ? C + L.after() * P29_STRIDE : C + (L.rc2() + (r - 1) * T) * P29_STRIDE, mds);
-    if (live && e == 1) trace_store<P>(w, wb + A + 3 * (size_t)sbox, s);  // the digest closes the block
-}
-
-template <class P, int T>
-__global__ __launch_bounds__(POSEIDON_BLOCK) void poseidon_trace_batch_kernel(const uint4* __restrict__ pre, size_t n, const uint4* __restrict__ img,
-                                                                                int img_vec4, int rf, int rp, int flags, TraceDst dst) {
-    extern __shared__ uint4 lds[];
-    for (int i = threadIdx.x; i < img_vec4; i += POSEIDON_BLOCK) lds[i] = img[i];
-    __syncthreads();
-    const uint32_t* C = reinterpret_cast<const uint32_t*>(lds);
-    const PoseidonLayout<T> L(rf, rp);
-    const uint32_t* mont2 = C + (size_t)L.total() * P29_STRIDE;
-    const uint32_t* post = mont2 + P29_STRIDE;
-    constexpr int A = T - 1;
-    Fe<P>* w = (Fe<P>*)dst.w;
-    for (size_t h = (size_t)blockIdx.x * POSEIDON_BLOCK + threadIdx.x; h < n; h += (size_t)gridDim.x * POSEIDON_BLOCK) {
-        const size_t wb = dst.base(h);
-        F29<P> s[T];
-        s[0] = ld_const29<P>(C);
-        const uint4* src = pre + h * (A * 2);
-#pragma unroll
-        for (int i = 0; i < A; i++) {
-            uint4 lo = src[2 * i], hi = src[2 * i + 1];
-            Fe<P> x;
-            x.l[0] = lo.x; x.l[1] = lo.y; x.l[2] = lo.z; x.l[3] = lo.w;
-            x.l[4] = hi.x; x.l[5] = hi.y; x.l[6] = hi.z; x.l[7] = hi.w;
-            s[i + 1] = (flags & PF_IN_MONT) ? f29_from_mont256<P>(x) : poseidon29_from_canonical<P>(x.l, mont2);
-            trace_store<P>(w, wb + i, s[i + 1]);
-        }
-        auto emit = [&](int sbox, const F29<P>& l2, const F29<P>& l4, const F29<P>& l5k) {
-            const size_t o = wb + A + 3 * (size_t)sbox;
-            trace_store<P>(w, o, l2);
-            trace_store<P>(w, o + 1, l4);
-            trace_store<P>(w, o + 2, l5k);
-        };
-        poseidon29_permute_trace<P, T>(s, C, post, rf, rp, emit);
-        trace_store<P>(w, wb + A + 3 * ((size_t)T * rf + rp), s[1]);
-    }
-}
+// The two trace kernels and TraceDst, which places a slot's block, are in poseidon_trace.cuh (trie_circuit.hip instantiates them too).
 
 // Bit-decomposition slots: bellpepper's AllocatedNum::to_bits_le_strict as allocate_img_for_slot runs it
 // (/root/reference/src/lem/circuit.rs:236-238).  The allocation order depends only on the field: walking the bits of p - 1
@@ -354,34 +201,12 @@ static BitDecompProgram make_bit_decomp_program() {
 }
 
 template <class P>
-__global__ __launch_bounds__(128) void bit_decomp_trace_kernel(const Fe<P>* __restrict__ vals, size_t n, const uint32_t* __restrict__ code, int ncode,
+__global__ __launch_bounds__(BIT_DECOMP_BLOCK) void bit_decomp_trace_kernel(const Fe<P>* __restrict__ vals, size_t n, const uint32_t* __restrict__ code, int ncode,
                                                                  const uint32_t* __restrict__ masks, int in_mont, TraceDst dst) {
     __shared__ uint32_t v[8];
     Fe<P>* w = (Fe<P>*)dst.w;
     const Fe<P> one = fe_one<P>(), zero = fe_zero<P>();
-    for (size_t i = blockIdx.x; i < n; i += gridDim.x) {
-        const size_t wb = dst.base(i);
-        if (threadIdx.x == 0) {
-            const Fe<P> x = vals[i];
-            const Fe<P> c = in_mont ? fe_from_mont<P>(x) : x;
-            for (int k = 0; k < 8; k++) v[k] = c.l[k];
-            w[wb] = in_mont ? x : fe_to_mont<P>(x);
-        }
-        __syncthreads();
-        for (int j = threadIdx.x; j < ncode; j += 128) {
-            const uint32_t cd = code[j];
-            bool on;
-            if (cd & 0x100u) {
-                const uint32_t* m = masks + (size_t)(cd & 0xffu) * 8;
-                on = true;
-                for (int k = 0; k < 8; k++) on = on && ((v[k] & m[k]) == m[k]);
-            } else {
-                on = (v[cd >> 5] >> (cd & 31)) & 1u;
-            }
-            w[wb + 1 + j] = on ? one : zero;
-        }
-        __syncthreads();
-    }
+    for (size_t i = blockIdx.x; i < n; i += gridDim.x) bit_decomp_trace_block<P>(vals + i, in_mont, w, dst.base(i), code, ncode, masks, v, one, zero);
 }
 
 // ---- per-(field, arity) constants, generated on the host once and kept in HBM ---------------
@@ -500,13 +325,13 @@ static void launch_trace(const void* d_pre, size_t n, PoseidonConsts& pc, int fl
     const size_t lds_bytes = (size_t)img_vec4 * 16;
     ProfScope ps("poseidon_trace", s);
     if (n <= POSEIDON_WIDE_MAX) {
-        auto wide = poseidon_trace_wide_kernel<P, T>;
+        auto wide = poseidon_trace_wide_kernel<P, T, TraceDst>;
         allow_dynamic_lds((const void*)wide, (int)lds_bytes);
         constexpr size_t per_block = (size_t)(POSEIDON_WIDE_BLOCK / 64) * (64 / T);
         hipLaunchKernelGGL(wide, dim3(div_up(n, per_block)), dim3(POSEIDON_WIDE_BLOCK), lds_bytes, s, (const uint4*)d_pre, n, img, img_vec4, pc.rf,
                            pc.rp, flags, dst);
     } else {
-        auto kern = poseidon_trace_batch_kernel<P, T>;
+        auto kern = poseidon_trace_batch_kernel<P, T, TraceDst>;
         allow_dynamic_lds((const void*)kern, (int)lds_bytes);
         unsigned blocks = div_up(n, POSEIDON_BLOCK), cap = grid_cap(2);
         if (blocks > cap) blocks = cap;
@@ -541,27 +366,29 @@ static BitDecompDev& bit_decomp_program(int field_id) {
     }
     return *it->second;
 }
+// the program on the current device, uploaded once per device
+static BitDecompView bit_decomp_on_device(BitDecompDev& bd) {
+    const int dev = current_device();
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = bd.dev.find(dev);
+    if (it == bd.dev.end()) {
+        DevBuf code(bd.host.code.size() * 4), masks(bd.host.masks.size() * 4 + 32);
+        LURK_HIP_CHECK(hipMemcpy(code.p, bd.host.code.data(), bd.host.code.size() * 4, hipMemcpyHostToDevice));
+        if (!bd.host.masks.empty()) LURK_HIP_CHECK(hipMemcpy(masks.p, bd.host.masks.data(), bd.host.masks.size() * 4, hipMemcpyHostToDevice));
+        it = bd.dev.emplace(dev, std::make_pair(std::move(code), std::move(masks))).first;
+    }
+    return BitDecompView{it->second.first.as<uint32_t>(), it->second.second.as<uint32_t>(), (int)bd.host.code.size()};
+}
+BitDecompView bit_decomp_view(int field_id) { return bit_decomp_on_device(bit_decomp_program(field_id)); }
+
 template <class P>
 static void launch_bit_decomp(BitDecompDev& bd, const void* d_vals, size_t n, int in_mont, const TraceDst& dst, hipStream_t s) {
     if (n == 0) return;
-    const int dev = current_device();
-    std::pair<DevBuf, DevBuf>* bufs;
-    {
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = bd.dev.find(dev);
-        if (it == bd.dev.end()) {
-            DevBuf code(bd.host.code.size() * 4), masks(bd.host.masks.size() * 4 + 32);
-            LURK_HIP_CHECK(hipMemcpy(code.p, bd.host.code.data(), bd.host.code.size() * 4, hipMemcpyHostToDevice));
-            if (!bd.host.masks.empty()) LURK_HIP_CHECK(hipMemcpy(masks.p, bd.host.masks.data(), bd.host.masks.size() * 4, hipMemcpyHostToDevice));
-            it = bd.dev.emplace(dev, std::make_pair(std::move(code), std::move(masks))).first;
-        }
-        bufs = &it->second;
-    }
+    const BitDecompView bv = bit_decomp_on_device(bd);
     ProfScope ps("bit_decomp_trace", s);
     unsigned blocks = n < 65535 ? (unsigned)n : 65535u;
-    hipLaunchKernelGGL((bit_decomp_trace_kernel<P>), dim3(blocks), dim3(128), 0, s, (const Fe<P>*)d_vals, n, bufs->first.as<uint32_t>(),
-                       (int)bd.host.code.size(), bufs->second.as<uint32_t>(), in_mont, dst);
+    hipLaunchKernelGGL((bit_decomp_trace_kernel<P>), dim3(blocks), dim3(BIT_DECOMP_BLOCK), 0, s, (const Fe<P>*)d_vals, n, bv.code, bv.ncode, bv.masks, in_mont, dst);
     LURK_HIP_CHECK(hipGetLastError());
 }
 

@@ -165,7 +165,7 @@ static void is_sat(const R1csShape& sh, const void* d_z, const void* d_e, uint64
 // ---- the slot gadgets' rows ------------------------------------------------------------------------------------
 static bool slot_is_hash_type(int slot_type) { return slot_type == 3 || slot_type == 4 || slot_type == 6 || slot_type == 8; }
 
-static const SlotCircuit& slot_circuit(int field_id, int slot_type) {
+const SlotCircuit& slot_circuit(int field_id, int slot_type) {  // also trie_circuit.hip
     LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
     LURK_REQUIRE(slot_is_hash_type(slot_type) || slot_type == LURK_SLOT_BIT_DECOMP, "unknown slot type");
     static std::mutex mu;

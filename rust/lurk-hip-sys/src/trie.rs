@@ -134,3 +134,77 @@ pub fn path_digits(field_id: c_int, height: usize, keys: &[Element]) -> Result<V
     check(unsafe { lurk_hip_trie_path_digits(field_id, height as c_int, keys.as_ptr().cast(), keys.len(), out.as_mut_ptr()) })?;
     Ok(out)
 }
+
+/// Which of the trie coprocessor's two step circuits: the body of `Trie::synthesize_lookup` (`:652-714`) or of `Trie::synthesize_insert`
+/// (`:802-880`) - `include/lurk_hip.h`, "the trie coprocessor's step circuits".
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum TrieCircuit {
+    Lookup = 0,
+    Insert = 1,
+}
+
+/// `lurk_hip_trie_circuit_size`: the block's elements, its rows and their non-zeros, and where the result (and, for an insert, the new
+/// value) sits in the block.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct TrieCircuitSize {
+    pub size: usize,
+    pub num_cons: usize,
+    pub nnz: [usize; 3],
+    pub result_col: usize,
+    pub value_col: Option<usize>,
+}
+
+/// Host only.
+pub fn trie_circuit_size(field_id: c_int, height: usize, op: TrieCircuit) -> Result<TrieCircuitSize, Error> {
+    let (mut size, mut rows, mut na, mut nb, mut nc, mut result, mut value) = (0usize, 0usize, 0usize, 0usize, 0usize, 0usize, 0usize);
+    check(unsafe { lurk_hip_trie_circuit_size(field_id, height as c_int, op as c_int, &mut size, &mut rows, &mut na, &mut nb, &mut nc, &mut result, &mut value) })?;
+    Ok(TrieCircuitSize { size, num_cons: rows, nnz: [na, nb, nc], result_col: result, value_col: (op == TrieCircuit::Insert).then_some(value) })
+}
+
+/// The circuit's rows: A, B, C over the block's local columns; local column `size` is the constant ONE.  Host only.
+pub fn trie_circuit_constraints(field_id: c_int, height: usize, op: TrieCircuit) -> Result<[SlotMatrix; 3], Error> {
+    let sz = trie_circuit_size(field_id, height, op)?;
+    let mk = |nnz: usize| SlotMatrix { indptr: vec![0u64; sz.num_cons + 1], indices: vec![0u64; nnz], data: vec![0u8; nnz * 32] };
+    let (mut a, mut b, mut c) = (mk(sz.nnz[0]), mk(sz.nnz[1]), mk(sz.nnz[2]));
+    check(unsafe {
+        lurk_hip_trie_circuit_constraints(field_id, height as c_int, op as c_int, a.indptr.as_mut_ptr(), a.indices.as_mut_ptr(), a.data.as_mut_ptr().cast(),
+                                          b.indptr.as_mut_ptr(), b.indices.as_mut_ptr(), b.data.as_mut_ptr().cast(), c.indptr.as_mut_ptr(), c.indices.as_mut_ptr(),
+                                          c.data.as_mut_ptr().cast())
+    })?;
+    Ok([a, b, c])
+}
+
+/// A resident shape of `n_blocks` circuits at columns `first + b * stride`, ONE at column `num_vars` (`lurk_hip_trie_circuit_r1cs_create`);
+/// `extra` = the caller's further rows (the `synthesize_*_aux` wrappers and whatever else the step circuit holds), appended.
+#[allow(clippy::too_many_arguments)]
+pub fn trie_circuit_shape(field_id: c_int, height: usize, op: TrieCircuit, n_blocks: usize, first: usize, stride: usize, num_vars: usize, num_io: usize,
+                          extra: Option<(Csr, Csr, Csr)>) -> Result<R1csShape, Error> {
+    let mut p = core::ptr::null_mut();
+    let null = core::ptr::null::<u64>();
+    check(unsafe {
+        match extra {
+            Some((a, b, c)) => lurk_hip_trie_circuit_r1cs_create(&mut p, field_id, height as c_int, op as c_int, n_blocks, first, stride, num_vars, num_io,
+                                                                 a.indptr.len().saturating_sub(1), a.indptr.as_ptr(), a.indices.as_ptr(), a.data.as_ptr().cast(),
+                                                                 b.indptr.as_ptr(), b.indices.as_ptr(), b.data.as_ptr().cast(), c.indptr.as_ptr(), c.indices.as_ptr(),
+                                                                 c.data.as_ptr().cast()),
+            None => lurk_hip_trie_circuit_r1cs_create(&mut p, field_id, height as c_int, op as c_int, n_blocks, first, stride, num_vars, num_io, 0, null, null,
+                                                      null.cast(), null, null, null.cast(), null, null, null.cast()),
+        }
+    })?;
+    Ok(R1csShape(p))
+}
+
+/// The blocks of `m` circuits written into the resident witness `d_w` (`lurk_hip_trie_circuit_witness_dev`): block `i` at `d_offsets[i]`, or
+/// at `first + i * stride` when `d_offsets` is null.  `one_root`: `d_roots` holds one root for every block, otherwise one per block - for a
+/// chain `[root(T_0), roots[0 .. m - 2]]` of `insert_chain`.  A lookup passes null for `d_new_values` and `d_new_paths`.  The proof is not
+/// judged; does not synchronise.
+/// # Safety
+/// device buffers of canonical elements as the trie calls leave them; `d_w` holds every block
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn trie_circuit_witness_dev(field_id: c_int, height: usize, op: TrieCircuit, d_roots: *const c_void, one_root: bool, d_keys: *const c_void,
+                                       d_new_values: *const c_void, d_old_paths: *const c_void, d_new_paths: *const c_void, m: usize, d_w: *mut c_void,
+                                       d_offsets: *const u64, first: usize, stride: usize, stream: *mut c_void) -> Result<(), Error> {
+    check(lurk_hip_trie_circuit_witness_dev(field_id, height as c_int, op as c_int, d_roots, usize::from(!one_root), d_keys, d_new_values, d_old_paths, d_new_paths, m,
+                                            d_w, d_offsets, first, stride, stream))
+}
