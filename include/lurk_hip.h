@@ -73,7 +73,7 @@ const char* lurk_hip_version(void);
  * that reports >= n until a revision says otherwise.  4: the verifiers - lurk_hip_r1cs_sparse_mle_dev, lurk_hip_ipa_s_vector_dev,
  * lurk_hip_sumcheck_verify, lurk_hip_ipa_verify_dev, lurk_hip_spartan_verify_dev, lurk_hip_spartan_verify_batch_dev (additions only);
  * later additions under the same number (a binding probes for them by symbol): lurk_hip_r1cs_transpose_dev, lurk_hip_r1cs_read,
- * lurk_hip_grid_cus, the four lurk_hip_trie_circuit_* calls.
+ * lurk_hip_grid_cus, the four lurk_hip_trie_circuit_* calls, the nine lurk_hip_trie_nodes_* calls.
  * 3: lurk_hip_slot_constraints_size / lurk_hip_slot_constraints,
  * lurk_hip_frames_r1cs_create, lurk_hip_r1cs_is_sat_dev (additions only).  2 (round 6): lurk_hip_msm_ctx_info's *precomputed is a boolean (the key's form comes from lurk_hip_msm_ctx_form),
  * LURK_MSM_SLOTS is 6, LURK_MSM_SUBMIT_FOLLOW, the parameter blocks lurk_hip_ro_params / lurk_hip_ck_params, lurk_hip_scratch_trim.
@@ -446,6 +446,65 @@ int lurk_hip_trie_verify_lookup_dev(int field_id, int height, const void* d_root
 int lurk_hip_trie_verify_insert_dev(int field_id, int height, const void* d_old_roots32, const void* d_new_roots32, size_t root_stride, const void* d_keys32,
                                     const void* d_old_values32, const void* d_new_values32, const void* d_old_paths, const void* d_new_paths, size_t m,
                                     uint32_t* d_codes, uint64_t* n_failed, void* stream);
+
+/* ---- root-addressed tries: the trie's child map resident on the device ------------------------------------------------------
+ * The reference's trie is addressed by its ROOT: every version of every trie lives in one child map, digest -> 8-element preimage
+ * (InversePoseidonCache::a8, /root/reference/src/hash.rs:116-166, written by register_hash, src/coprocessor/trie/mod.rs:453-458), the
+ * coprocessors rebuild a trie from a root (Trie::new_with_root, :566-576) and walk the map from it (prove_lookup_at_path, :725-743).
+ * lurk_hip_trie_nodes is that map for one (field, height) in device memory: content-addressed and append-only (registering a digest
+ * that is present is a no-op; nothing is ever removed, so a root stays valid), arity 8, height 1 .. 85, the three fields of the trie
+ * calls, canonical 32-byte elements, paths laid out as the trie calls lay them out (m * H * 8 elements, root level first).
+ *
+ * The store is an open-addressing table with a power-of-two slot count: a 64-bit tag (0 = empty), the 32 B digest and the 256 B
+ * preimage per slot, 296 B per slot, at most half the slots taken.  Before a batch would take more than half, the table is rebuilt at
+ * the next sufficient power of two (one allocation, one re-insert launch, one free); an allocation that fails is LURK_HIP_ERR_OOM with
+ * the store unchanged.  A trie of 2^16 keys at H = 85 has about 5.6 M nodes: 2^24 slots, 4.97 GB (against 178 MB for the handle, which
+ * holds ONE version; every further version of that trie adds at most H nodes per update).  n_nodes is exact: the number of distinct
+ * digests registered, whatever the batches held.  LURK_TRIE_NODES_TAG_BITS keeps fewer tag bits, for tests.
+ *
+ * Calls that register (create, register_dev, add_trie, prove_insert_dev with register_new, insert_chain_dev) synchronise `stream` - the
+ * host learns n_nodes - and must not run while another call on the same store is in flight; get_dev, prove_lookup_dev and
+ * prove_insert_dev without register_new only read, and may run side by side on several streams.  Every call requires the store's device
+ * to be the calling thread's current one and refuses otherwise with nothing launched. */
+typedef struct lurk_hip_trie_nodes lurk_hip_trie_nodes;
+/* init_empty (:464-481): the H preimages of the empty chain are registered, n_nodes == height.  reserve_nodes: how many nodes the table
+ * should hold before it first grows (0 = the minimum). */
+int lurk_hip_trie_nodes_create(lurk_hip_trie_nodes** ns, int field_id, int height, size_t reserve_nodes);
+int lurk_hip_trie_nodes_destroy(lurk_hip_trie_nodes* ns);
+/* any output may be NULL; host only */
+int lurk_hip_trie_nodes_info(const lurk_hip_trie_nodes* ns, int* field_id, int* height, size_t* n_nodes, size_t* slots, int* device);
+/* register_hash for a batch: hash8 of `count` preimages (count * 8 elements; the batch hasher's permutation), every (digest, preimage)
+ * inserted, the digests written to d_digests_out when it is non-NULL.  A preimage element that is not reduced refuses the call before
+ * anything is hashed: "preimage element <i> is not reduced" (i counts elements, lowest first). */
+int lurk_hip_trie_nodes_register_dev(lurk_hip_trie_nodes* ns, const void* d_preimages, size_t count, void* d_digests_out, void* stream);
+/* Every node of a built handle (same field and height), with no hash computed: the digests are read from the handle's level arrays and
+ * the preimages gathered from the level below.  At most n * H - sum(shared digits of neighbouring keys) nodes; n = 0 adds nothing. */
+int lurk_hip_trie_nodes_add_trie(lurk_hip_trie_nodes* ns, const lurk_hip_trie* trie, void* stream);
+/* InversePoseidonCache::get for m digests: d_preimages m * 8 elements, d_found[j] 1 or 0; a digest that is not in the store gives a
+ * zero row.  Stream-ordered: does not synchronise. */
+int lurk_hip_trie_nodes_get_dev(const lurk_hip_trie_nodes* ns, const void* d_digests32, size_t m, void* d_preimages, uint32_t* d_found, void* stream);
+/* new_with_root + prove_lookup per query: query i walks from d_roots32[i * root_stride] (root_stride 0 = one root for every query, 1 =
+ * one per query; roots of several versions may be mixed).  d_status[i]: 0 = found (d_paths and d_values32 as
+ * lurk_hip_trie_prove_lookup_dev writes them); k + 1 = the node expected at level k is not in the store (Error::MissingPreimage, :738):
+ * rows k .. H - 1 of that path and the value are then zero.  *n_missing (host, may be NULL) = the number of non-zero statuses; the walk is
+ * stream-ordered and the call waits for it only when n_missing is non-NULL.  Keys and roots that are not reduced are refused by name before
+ * anything is launched (that check copies them to the host and waits for `stream`). */
+int lurk_hip_trie_nodes_prove_lookup_dev(const lurk_hip_trie_nodes* ns, const void* d_roots32, size_t root_stride, const void* d_keys32, size_t m, void* d_paths,
+                                         void* d_values32, uint32_t* d_status, uint64_t* n_missing, void* stream);
+/* m independent new_with_root + prove_insert (:751-800), query i at its own root: outputs as lurk_hip_trie_prove_insert_dev, d_status and
+ * n_missing as above; a query with a non-zero status writes zero rows to d_new_paths and a zero new root, and registers nothing.
+ * register_new != 0: the m * H new nodes are registered from the hashes just computed (nothing is hashed twice), every new root is
+ * addressable when the call returns, and the call synchronises.  register_new == 0: the store is unchanged. */
+int lurk_hip_trie_nodes_prove_insert_dev(lurk_hip_trie_nodes* ns, const void* d_roots32, size_t root_stride, const void* d_keys32, const void* d_new_values32,
+                                         size_t m, void* d_old_paths, void* d_new_paths, void* d_old_values32, void* d_new_roots32, uint32_t* d_status,
+                                         uint64_t* n_missing, int register_new, void* stream);
+/* lurk_hip_trie_insert_chain_dev with T_0 named by a root (root32_host: 32 canonical bytes in HOST memory): update i is applied to T_i and
+ * leaves T_{i + 1}; outputs as there, each may be NULL.  All m keys are walked in T_0 first; a miss refuses the whole call with
+ * LURK_HIP_ERR_INVALID_ARG, "update <i>: missing preimage at level <k>" (lowest i), nothing hashed or registered (the old-path and
+ * old-value buffers are then unspecified).  Otherwise every new node of every T_i is registered: all m roots d_roots32[i] are addressable,
+ * the result is d_roots32[m - 1]. */
+int lurk_hip_trie_nodes_insert_chain_dev(lurk_hip_trie_nodes* ns, const void* root32_host, const void* d_keys32, const void* d_values32, size_t m,
+                                         void* d_old_paths, void* d_new_paths, void* d_old_values32, void* d_roots32, void* stream);
 
 /* ---- store hydration -----------------------------------------------------------------------
  * Replaces the recursive, node-by-node hashing of StoreCore::hydrate_z_cache / hash_ptr

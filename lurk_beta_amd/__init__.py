@@ -22,7 +22,7 @@ from .spartan import BatchedSpartanProver, BatchedSpartanVerifier, SpartanProver
 from . import spartan_kzg  # noqa: E402,F401
 from .spartan_kzg import BatchedSpartanKzgProver, BatchedSpartanKzgVerifier, SpartanKzgProver, SpartanKzgVerifier  # noqa: E402
 from . import params  # noqa: E402,F401
-from .trie import DeviceTrie, Trie, verify_insert, verify_lookup  # noqa: E402
+from .trie import DeviceTrie, DeviceTrieNodes, Trie, verify_insert, verify_lookup  # noqa: E402
 from . import trie_circuit  # noqa: E402,F401
 from .witness import MultiFrameWitness, slot_constraints, slot_witness, slot_witness_size  # noqa: E402
 from .store_resident import DeviceStore  # noqa: E402
@@ -31,7 +31,7 @@ __all__ = [
     "CommitmentKey", "MultiCommitmentKey", "msm", "point_sum", "point_to_affine", "ntt", "R1CSShape", "fold_vec", "fold_vecs", "fold_padded", "FoldingContext", "NivcFoldingContext", "nifs_challenge", "nova_ro_squeeze", "point_mul", "public_io", "MultiFrameWitness", "slot_constraints", "slot_witness", "slot_witness_size",
     "SpartanProver", "BatchedSpartanProver", "SpartanVerifier", "BatchedSpartanVerifier",
     "SpartanKzgProver", "BatchedSpartanKzgProver", "SpartanKzgVerifier", "BatchedSpartanKzgVerifier",
-    "Trie", "DeviceTrie", "verify_lookup", "verify_insert", "DeviceStore",
+    "Trie", "DeviceTrie", "DeviceTrieNodes", "verify_lookup", "verify_insert", "DeviceStore",
     "LurkHipError", "PoseidonCache", "HashArity", "poseidon_batch", "poseidon_tree8", "poseidon_constants",
     "FIELD_PALLAS_FP", "FIELD_PALLAS_FQ", "FIELD_BN254_FR", "FIELD_BN254_FQ", "CURVE_PALLAS", "CURVE_VESTA", "CURVE_BN254", "CURVE_GRUMPKIN",
 ]

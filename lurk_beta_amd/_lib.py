@@ -125,6 +125,17 @@ SIGNATURES = {
     "lurk_hip_trie_prove_lookup_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "lurk_hip_trie_prove_insert_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lurk_hip_trie_insert_chain_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p]),
+    "lurk_hip_trie_nodes_create": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_size_t]),
+    "lurk_hip_trie_nodes_destroy": (c_int, [c_void_p]),
+    "lurk_hip_trie_nodes_info": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
+                                         ctypes.POINTER(c_int)]),
+    "lurk_hip_trie_nodes_register_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lurk_hip_trie_nodes_add_trie": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "lurk_hip_trie_nodes_get_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "lurk_hip_trie_nodes_prove_lookup_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_u64), c_void_p]),
+    "lurk_hip_trie_nodes_prove_insert_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     ctypes.POINTER(c_u64), c_int, c_void_p]),
+    "lurk_hip_trie_nodes_insert_chain_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lurk_hip_trie_verify_lookup_dev": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_u64), c_void_p]),
     "lurk_hip_trie_verify_insert_dev": (c_int, [c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
                                                 ctypes.POINTER(c_u64), c_void_p]),

@@ -20,21 +20,17 @@
 //                             per proof, the first failing check latched and the chain run to its end
 //   trie_chain_*_kernel       a chain of m DEPENDENT inserts in O(H) launches (see "the chain" below): the updates ordered per depth by
 //                             (prefix, sequence index), then one hashing launch per depth, bottom-up, one update per lane
+//
+// What the root-addressed child map (trie_nodes.hip) shares with this unit lives in trie_common.cuh: element loads and stores, the digit and
+// range helpers, TrieHasher and the image staging, the handle, the host checks, and trie_chain_run - the chain's ordering and level launches.
 #include <memory>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "common.hpp"
-#include "dispatch.hpp"
-#include "poseidon.cuh"
-#include "poseidon29.cuh"
+#include "trie_common.cuh"
 
 namespace lurk {
-
-constexpr int TRIE_BLOCK = 256;
-constexpr int TRIE_MAX_HEIGHT = 85;  // 3 * 85 = 255 path bits: lurk-beta's StandardTrie (:43)
-constexpr int TRIE_T = 9;            // arity 8
 
 enum : unsigned { TRIE_BAD_NOT_REDUCED = 1, TRIE_BAD_OUT_OF_ORDER = 2, TRIE_BAD_DUPLICATE = 3 };
 
@@ -42,88 +38,6 @@ struct TrieStatus {
     unsigned long long first_bad;  // (index << 2 | kind) of the lowest offending key, all ones if none
     unsigned int max_shared;       // the most digits two neighbouring keys share: phase 2 starts at that depth
     unsigned int pad;
-};
-
-struct TrieView {
-    const uint32_t* keys;   // n x 8 words, canonical, strictly increasing path values
-    const uint4* values;    // n x 32 B
-    uint4* levels;          // H disjoint arrays of n x 32 B: level d at levels + d * n * 2
-    const uint4* empty;     // (H + 1) x 32 B: empty[h] = root of the empty subtree of height h (empty[0] = 0, the empty element)
-    const uint8_t* shared;  // shared[i] = digits key i shares with key i - 1 (i >= 1)
-    size_t n;
-    int height;
-};
-
-template <class P>
-__device__ __forceinline__ Fe<P> ld_fe(const uint4* p) {
-    const uint4 lo = p[0], hi = p[1];
-    Fe<P> x;
-    x.l[0] = lo.x; x.l[1] = lo.y; x.l[2] = lo.z; x.l[3] = lo.w;
-    x.l[4] = hi.x; x.l[5] = hi.y; x.l[6] = hi.z; x.l[7] = hi.w;
-    return x;
-}
-template <class P>
-__device__ __forceinline__ void st_fe(uint4* p, const Fe<P>& d) {
-    p[0] = make_uint4(d.l[0], d.l[1], d.l[2], d.l[3]);
-    p[1] = make_uint4(d.l[4], d.l[5], d.l[6], d.l[7]);
-}
-
-// digit d (0 = top) of the path of height `height`, from the key's eight 32-bit words in memory
-LURK_HD int trie_key_digit(const uint32_t* key, int height, int d) {
-    const int bit = 3 * (height - 1 - d), w = bit >> 5, sh = bit & 31;
-    uint32_t v = key[w] >> sh;
-    if (sh > 29) v |= key[w + 1] << (32 - sh);  // bit <= 252: a digit that straddles two words starts below word 7
-    return (int)(v & 7u);
-}
-// word w of the mask of a value's low `nbits` bits / of everything from bit `lowbit` up
-LURK_HD uint32_t trie_low_mask(int w, int nbits) {
-    const int r = nbits - 32 * w;
-    return r >= 32 ? 0xffffffffu : r <= 0 ? 0u : ((1u << r) - 1u);
-}
-LURK_HD uint32_t trie_high_mask(int w, int lowbit) { return ~trie_low_mask(w, lowbit); }
-
-// do the keys a (registers) and b (memory) share their top d digits?
-__device__ __forceinline__ bool trie_same_prefix(const uint32_t* a, const uint32_t* b, int height, int d) {
-    const uint4 lo = reinterpret_cast<const uint4*>(b)[0], hi = reinterpret_cast<const uint4*>(b)[1];
-    const uint32_t bw[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    uint32_t diff = 0;
-#pragma unroll
-    for (int w = 0; w < 8; w++) diff |= (a[w] ^ bw[w]) & trie_low_mask(w, 3 * height) & trie_high_mask(w, 3 * (height - d));
-    return diff == 0;
-}
-
-// within [lo, hi), a range of keys that share their top d digits: the first key whose digit d is >= c
-__device__ __forceinline__ size_t trie_digit_lower_bound(const uint32_t* keys, size_t lo, size_t hi, int height, int d, int c) {
-    while (lo < hi) {
-        const size_t mid = lo + ((hi - lo) >> 1);
-        if (trie_key_digit(keys + mid * 8, height, d) < c) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// ---- the hash: one state per lane, the constant image in LDS ---------------------------------------------------------------------------
-// only the permutation's part of the image is staged (the slot-witness post keys that follow it are not read here): 59 KiB at arity 8
-static int trie_image_vec4(int rf, int rp) { return (PoseidonLayout<TRIE_T>(rf, rp).total() + 1) * (P29_STRIDE / 4); }
-
-__device__ __forceinline__ void trie_stage_image(uint4* lds, const uint4* __restrict__ img, int img_vec4) {
-    for (int i = threadIdx.x; i < img_vec4; i += TRIE_BLOCK) lds[i] = img[i];
-    __syncthreads();
-}
-
-template <class P>
-struct TrieHasher {
-    const uint32_t* C;
-    const uint32_t* mont2;
-    int rf, rp;
-    __device__ __forceinline__ TrieHasher(const uint4* lds, int rf_, int rp_)
-        : C(reinterpret_cast<const uint32_t*>(lds)), mont2(C + (size_t)PoseidonLayout<TRIE_T>(rf_, rp_).total() * P29_STRIDE), rf(rf_), rp(rp_) {}
-    __device__ __forceinline__ F29<P> tag() const { return ld_const29<P>(C); }
-    __device__ __forceinline__ F29<P> in(const Fe<P>& x) const { return poseidon29_from_canonical<P>(x.l, mont2); }
-    __device__ __forceinline__ Fe<P> run(F29<P>* s) const {
-        poseidon29_permute<P, TRIE_T>(s, C, rf, rp);
-        return poseidon29_to_canonical<P>(s[1]);
-    }
 };
 
 // ---- order check -----------------------------------------------------------------------------------------------------------------------
@@ -602,46 +516,6 @@ __global__ __launch_bounds__(TRIE_BLOCK) void trie_chain_merge_kernel(const uint
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
-static void require_trie_field(int field_id) {
-    with_field(field_id, [](auto) {});  // "unknown field id"
-}
-static void require_trie_height(int height) {
-    LURK_REQUIRE(height >= 1 && height <= TRIE_MAX_HEIGHT, "trie height must be 1 .. 85 (3 bits of the key per level)");
-}
-
-// empty[h] for h = 0 .. 85 (canonical, 4 x u64 each), by the library's host Poseidon: once per field
-static const std::vector<uint64_t>& trie_empty_roots(int field_id) {
-    static std::mutex mu;
-    static std::map<int, std::vector<uint64_t>> cache;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(field_id);
-    if (it == cache.end()) {
-        std::vector<uint64_t> er((TRIE_MAX_HEIGHT + 1) * 4, 0);
-        for (int hgt = 1; hgt <= TRIE_MAX_HEIGHT; hgt++) {
-            uint64_t pre[8 * 4];
-            for (int j = 0; j < 8; j++) memcpy(pre + 4 * j, er.data() + 4 * (hgt - 1), 32);
-            nested_ok(lurk_hip_poseidon_hash_host(field_id, 8, pre, 1, er.data() + 4 * hgt));
-        }
-        it = cache.emplace(field_id, std::move(er)).first;
-    }
-    return it->second;
-}
-
-struct TrieLaunch {  // what every hashing launch needs
-    const uint4* img;
-    int vec4, rf, rp;
-    size_t lds_bytes;
-    TrieLaunch(int field_id, hipStream_t s) {
-        const PoseidonImageView v = poseidon_image_view(field_id, 8, s);
-        img = (const uint4*)v.img;
-        rf = v.rf;
-        rp = v.rp;
-        vec4 = trie_image_vec4(rf, rp);
-        LURK_REQUIRE(vec4 <= v.vec4, "the Poseidon image is shorter than its layout");
-        lds_bytes = (size_t)vec4 * 16;
-    }
-};
-
 static std::string trie_refusal(const char* what, unsigned long long first_bad) {
     const unsigned long long i = first_bad >> 2;
     const std::string k = what + std::string(" ") + std::to_string(i);
@@ -652,35 +526,87 @@ static std::string trie_refusal(const char* what, unsigned long long first_bad) 
     }
 }
 
-// a verify call's device-resident keys / values, checked on the host before anything is launched: copies, no kernel
-template <class P>
-static void require_reduced_dev(const void* d_elems, size_t m, const char* what, std::vector<uint32_t>& host, hipStream_t s) {
-    host.resize(m * 8);
-    LURK_HIP_CHECK(hipMemcpyAsync(host.data(), d_elems, m * 32, hipMemcpyDeviceToHost, s));
-    LURK_HIP_CHECK(hipStreamSynchronize(s));
-    for (size_t i = 0; i < m; i++)
-        if (fe_canonical_ge_mod<P>(host.data() + i * 8))
-            throw HipFailure{LURK_HIP_ERR_INVALID_ARG, std::string(what) + " " + std::to_string(i) + " is not reduced modulo the field order"};
+// the chain's ordering and hashing launches (trie_common.cuh): shared by lurk_hip_trie_insert_chain_dev and the root-addressed chain
+void trie_chain_run(int field_id, int H, const void* d_keys32, const void* d_values32, size_t m, uint4* oldp, bool store_old, void* d_new_paths,
+                    void* d_old_values32, void* d_roots32, const std::function<void()>& walk, TrieChainScratch& sc, hipStream_t s) {
+    with_field(field_id, [&](auto F) {
+        using P = decltype(F);
+        const uint32_t* keys = (const uint32_t*)d_keys32;
+        const unsigned grid = div_up(m, TRIE_BLOCK);
+        // scratch: the orders (2 x 4 B per update and depth that is split, H at the most), two rows of new hashes, the sort's storage, and the
+        // preimages of T_0 when the caller does not take the old paths
+        sc.orders.alloc(2 * (size_t)H * m * 4);
+        sc.work.alloc(4 * m * 4);
+        sc.hashes.alloc(2 * m * 32);
+        sc.flag.alloc(4);
+        sc.m = m;
+        DevBuf &work = sc.work, &hashes = sc.hashes, &flag = sc.flag, &temp = sc.temp;
+        uint32_t *skey_in = work.as<uint32_t>(), *entry_in = skey_in + m, *label = skey_in + 2 * m, *aux = skey_in + 3 * m;
+        auto ord_at = [&](int e) { return sc.ord_at(e); };
+        auto skey_at = [&](int e) { return sc.skey_at(e); };
+        unsigned end_bit = 4;
+        while (end_bit < 32 && ((size_t)1 << end_bit) < 8 * m) end_bit++;
+        size_t sort_bytes = 0, scan_bytes = 0;
+        LURK_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, skey_in, skey_in, entry_in, entry_in, (unsigned)m, 0, end_bit, s));
+        LURK_HIP_CHECK(rocprim::inclusive_scan(nullptr, scan_bytes, aux, aux, m, rocprim::plus<uint32_t>(), s));
+        temp.alloc(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
+        LURK_HIP_CHECK(hipMemsetAsync(label, 0, m * 4, s));
+
+        // the orders, top-down: split depth d while one of its nodes holds two path values
+        int& D = sc.D;
+        D = 0;
+        {
+            ProfScope ps("trie_chain_order", s);
+            for (; D < H; D++) {
+                LURK_HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
+                hipLaunchKernelGGL(trie_chain_key_kernel, dim3(grid), dim3(TRIE_BLOCK), 0, s, keys, D ? ord_at(D) : (const uint32_t*)nullptr, label, m, H, D, skey_in,
+                                   entry_in, flag.as<uint32_t>());
+                LURK_HIP_CHECK(hipGetLastError());
+                uint32_t mixed = 0;
+                LURK_HIP_CHECK(hipMemcpyAsync(&mixed, flag.p, 4, hipMemcpyDeviceToHost, s));
+                LURK_HIP_CHECK(hipStreamSynchronize(s));
+                if (!mixed) break;
+                size_t bytes = temp.bytes;
+                LURK_HIP_CHECK(rocprim::radix_sort_pairs(temp.p, bytes, skey_in, skey_at(D + 1), entry_in, ord_at(D + 1), (unsigned)m, 0, end_bit, s));
+                hipLaunchKernelGGL(trie_chain_label_kernel, dim3(grid), dim3(TRIE_BLOCK), 0, s, skey_at(D + 1), m, label);
+                LURK_HIP_CHECK(hipGetLastError());
+            }
+        }
+        walk();
+        // the hashes, bottom-up
+        const TrieLaunch L(field_id, s);
+        auto kern = trie_chain_level_kernel<P>;
+        allow_dynamic_lds((const void*)kern, (int)L.lds_bytes);
+        const uint4* below = (const uint4*)d_values32;
+        {
+            ProfScope ps("trie_chain_levels", s);
+            for (int d = H - 1; d >= 0; d--) {
+                TrieChainLevel a;
+                a.keys = keys;
+                const int e = d + 1 < D ? d + 1 : D;
+                a.ord = e ? ord_at(e) : nullptr;
+                a.skey = d + 1 <= D ? skey_at(e) : nullptr;
+                a.label = label;
+                a.below = below;
+                a.here = d == 0 && d_roots32 ? (uint4*)d_roots32 : hashes.as<uint4>() + (size_t)(d & 1) * m * 2;
+                a.old_paths = oldp;
+                a.new_paths = (uint4*)d_new_paths;
+                a.old_values = (uint4*)d_old_values32;
+                a.m = m;
+                a.height = H;
+                a.d = d;
+                a.store_old = store_old ? 1 : 0;
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(TRIE_BLOCK), L.lds_bytes, s, a, L.img, L.vec4, L.rf, L.rp);
+                LURK_HIP_CHECK(hipGetLastError());
+                below = a.here;
+            }
+        }
+    });
 }
 
 }  // namespace lurk
 
 using namespace lurk;
-
-struct lurk_hip_trie {
-    int field_id = 0, height = 0, device = 0;
-    size_t n = 0;
-    DevBuf keys, values, levels, empty, shared;
-    uint64_t root[4] = {0, 0, 0, 0};
-    TrieView view() const {
-        return TrieView{keys.as<uint32_t>(), values.as<uint4>(), levels.as<uint4>(), empty.as<uint4>(), shared.as<uint8_t>(), n, height};
-    }
-};
-
-static void require_trie_here(const lurk_hip_trie* t) {
-    LURK_REQUIRE(t, "null trie handle");
-    LURK_REQUIRE(current_device() == t->device, "the trie lives on another device than the calling thread's current one");
-}
 
 extern "C" {
 
@@ -928,85 +854,35 @@ int lurk_hip_trie_insert_chain_dev(const lurk_hip_trie* t, const void* d_keys32,
         }
         with_field(t->field_id, [&](auto F) {
             using P = decltype(F);
-            {
-                std::vector<uint32_t> host;  // nothing is launched or allocated on the device before both have passed
-                require_reduced_dev<P>(d_keys32, m, "key", host, s);
-                require_reduced_dev<P>(d_values32, m, "value", host, s);
-            }
+            std::vector<uint32_t> host;  // nothing is launched or allocated on the device before both have passed
+            require_reduced_dev<P>(d_keys32, m, "key", host, s);
+            require_reduced_dev<P>(d_values32, m, "value", host, s);
+        });
+        {
             const uint32_t* keys = (const uint32_t*)d_keys32;
             const unsigned grid = div_up(m, TRIE_BLOCK);
-            // scratch: the orders (2 x 4 B per update and depth that is split, H at the most), two rows of new hashes, the sort's storage, and the
-            // preimages of T_0 when the caller does not take the old paths
-            DevBuf orders(2 * (size_t)H * m * 4), work(4 * m * 4), hashes(2 * m * 32), flag(4), old_scratch, value_scratch;
-            uint32_t *skey_in = work.as<uint32_t>(), *entry_in = skey_in + m, *label = skey_in + 2 * m, *aux = skey_in + 3 * m;
-            auto ord_at = [&](int e) { return orders.as<uint32_t>() + (size_t)(2 * (e - 1)) * m; };       // e = 1 .. D
-            auto skey_at = [&](int e) { return orders.as<uint32_t>() + (size_t)(2 * (e - 1) + 1) * m; };
-            unsigned end_bit = 4;
-            while (end_bit < 32 && ((size_t)1 << end_bit) < 8 * m) end_bit++;
-            size_t sort_bytes = 0, scan_bytes = 0;
-            LURK_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, skey_in, skey_in, entry_in, entry_in, (unsigned)m, 0, end_bit, s));
-            LURK_HIP_CHECK(rocprim::inclusive_scan(nullptr, scan_bytes, aux, aux, m, rocprim::plus<uint32_t>(), s));
-            DevBuf temp(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
+            // the preimages of T_0 when the caller does not take the old paths
+            DevBuf old_scratch, value_scratch;
             if (!d_old_paths) old_scratch.alloc(path_bytes);
             if (!d_old_values32) value_scratch.alloc(m * 32);
             uint4* oldp = d_old_paths ? (uint4*)d_old_paths : old_scratch.as<uint4>();
-            LURK_HIP_CHECK(hipMemsetAsync(label, 0, m * 4, s));
-
-            // the orders, top-down: split depth d while one of its nodes holds two path values
-            int D = 0;
-            {
-                ProfScope ps("trie_chain_order", s);
-                for (; D < H; D++) {
-                    LURK_HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, s));
-                    hipLaunchKernelGGL(trie_chain_key_kernel, dim3(grid), dim3(TRIE_BLOCK), 0, s, keys, D ? ord_at(D) : (const uint32_t*)nullptr, label, m, H, D, skey_in,
-                                       entry_in, flag.as<uint32_t>());
-                    LURK_HIP_CHECK(hipGetLastError());
-                    uint32_t mixed = 0;
-                    LURK_HIP_CHECK(hipMemcpyAsync(&mixed, flag.p, 4, hipMemcpyDeviceToHost, s));
-                    LURK_HIP_CHECK(hipStreamSynchronize(s));
-                    if (!mixed) break;
-                    size_t bytes = temp.bytes;
-                    LURK_HIP_CHECK(rocprim::radix_sort_pairs(temp.p, bytes, skey_in, skey_at(D + 1), entry_in, ord_at(D + 1), (unsigned)m, 0, end_bit, s));
-                    hipLaunchKernelGGL(trie_chain_label_kernel, dim3(grid), dim3(TRIE_BLOCK), 0, s, skey_at(D + 1), m, label);
-                    LURK_HIP_CHECK(hipGetLastError());
-                }
-            }
-            // the preimages of T_0 along every update's path (and, for now, the values of T_0)
             const TrieView v = t->view();
-            {
-                ProfScope ps("trie_chain_walk", s);
-                hipLaunchKernelGGL((trie_prove_lookup_kernel<P>), dim3(grid), dim3(TRIE_BLOCK), 0, s, v, keys, m, oldp,
-                                   d_old_values32 ? (uint4*)d_old_values32 : value_scratch.as<uint4>());
-                LURK_HIP_CHECK(hipGetLastError());
-            }
-            // the hashes, bottom-up
-            const TrieLaunch L(t->field_id, s);
-            auto kern = trie_chain_level_kernel<P>;
-            allow_dynamic_lds((const void*)kern, (int)L.lds_bytes);
-            const uint4* below = (const uint4*)d_values32;
-            {
-                ProfScope ps("trie_chain_levels", s);
-                for (int d = H - 1; d >= 0; d--) {
-                    TrieChainLevel a;
-                    a.keys = keys;
-                    const int e = d + 1 < D ? d + 1 : D;
-                    a.ord = e ? ord_at(e) : nullptr;
-                    a.skey = d + 1 <= D ? skey_at(e) : nullptr;
-                    a.label = label;
-                    a.below = below;
-                    a.here = d == 0 && d_roots32 ? (uint4*)d_roots32 : hashes.as<uint4>() + (size_t)(d & 1) * m * 2;
-                    a.old_paths = oldp;
-                    a.new_paths = (uint4*)d_new_paths;
-                    a.old_values = (uint4*)d_old_values32;
-                    a.m = m;
-                    a.height = H;
-                    a.d = d;
-                    a.store_old = d_old_paths ? 1 : 0;
-                    hipLaunchKernelGGL(kern, dim3(grid), dim3(TRIE_BLOCK), L.lds_bytes, s, a, L.img, L.vec4, L.rf, L.rp);
+            // the preimages of T_0 along every update's path (and, for now, the values of T_0)
+            auto walk = [&] {
+                with_field(t->field_id, [&](auto F) {
+                    using P = decltype(F);
+                    ProfScope ps("trie_chain_walk", s);
+                    hipLaunchKernelGGL((trie_prove_lookup_kernel<P>), dim3(grid), dim3(TRIE_BLOCK), 0, s, v, keys, m, oldp,
+                                       d_old_values32 ? (uint4*)d_old_values32 : value_scratch.as<uint4>());
                     LURK_HIP_CHECK(hipGetLastError());
-                    below = a.here;
-                }
-            }
+                });
+            };
+            TrieChainScratch sc;
+            trie_chain_run(t->field_id, H, d_keys32, d_values32, m, oldp, d_old_paths != nullptr, d_new_paths, d_old_values32, d_roots32, walk, sc, s);
+            const int D = sc.D;
+            uint32_t *skey_in = sc.work.as<uint32_t>(), *entry_in = skey_in + m, *label = skey_in + 2 * m, *aux = skey_in + 3 * m;
+            DevBuf& temp = sc.temp;
+            auto ord_at = [&](int e) { return sc.ord_at(e); };
             if (out_trie) {
                 // T_m's pairs: the last update of every path value (ord[D] is in path order) merged with the pairs of t that none replaces
                 const uint32_t* ord = D ? ord_at(D) : nullptr;
@@ -1036,7 +912,7 @@ int lurk_hip_trie_insert_chain_dev(const lurk_hip_trie* t, const void* d_keys32,
                 nested_ok(lurk_hip_trie_build_dev(&grown, t->field_id, H, mkeys.p, mvalues.p, total, stream));
             }
             LURK_HIP_CHECK(hipStreamSynchronize(s));
-        });
+        }
         if (out_trie) *out_trie = grown;
     });
 }

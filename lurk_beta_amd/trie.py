@@ -7,7 +7,10 @@ Mirrors ``coprocessor::trie::Trie<F, ARITY, HEIGHT>`` (/root/reference/src/copro
 the reference's ``children``/inverse cache (:453-458).
 
 ``DeviceTrie`` is the bulk form over the library's device-resident trie (include/lurk_hip.h, "the sparse Poseidon trie"): one
-build for all pairs, proofs and verification for batches of keys, nothing hashed node by node from the host."""
+build for all pairs, proofs and verification for batches of keys, nothing hashed node by node from the host.
+
+``DeviceTrieNodes`` is ``children`` itself on the device (include/lurk_hip.h, "root-addressed tries"): every version of every trie in
+one content-addressed table, looked up, inserted into and chained from a ROOT, as the coprocessors do with ``Trie::new_with_root``."""
 from __future__ import annotations
 
 import ctypes
@@ -269,6 +272,131 @@ class DeviceTrie:
         # a handle that was never closed gives its device memory back when it is collected; nothing can be raised from here.  A closed
         # one has nothing left to give back, whenever the collector gets to it (a closed trie kept alive by a traceback is collected
         # at some later collection, not when its last name goes)
+        if getattr(self, "_h", None) is None:
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceTrieNodes:
+    """The trie's child map (``Trie.children``, the reference's inverse Poseidon cache) resident on the GPU (lurk_hip_trie_nodes): every
+    version of every trie of one (field, height), addressed by ROOT.  What ``Trie::new_with_root`` and a host-side root -> handle table
+    were for: a root goes in as an element, the walk happens on the device.  Elements cross as for ``DeviceTrie``."""
+
+    def __init__(self, handle, field_id: int, height: int):
+        self._h, self.field_id, self.height = handle, field_id, height
+
+    @classmethod
+    def create(cls, field_id: int, height: int = 85, reserve_nodes: int = 0) -> "DeviceTrieNodes":
+        """``init_empty``: the store holds the ``height`` nodes of the empty chain."""
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().lurk_hip_trie_nodes_create(ctypes.byref(h), field_id, height, reserve_nodes))
+        return cls(h, field_id, height)
+
+    def info(self) -> dict:
+        f, hgt, dev = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        n, slots = ctypes.c_size_t(), ctypes.c_size_t()
+        _lib.check(_lib.load().lurk_hip_trie_nodes_info(self._h, ctypes.byref(f), ctypes.byref(hgt), ctypes.byref(n), ctypes.byref(slots), ctypes.byref(dev)))
+        return {"field_id": f.value, "height": hgt.value, "n_nodes": n.value, "slots": slots.value, "device": dev.value}
+
+    @property
+    def n_nodes(self) -> int:
+        return self.info()["n_nodes"]
+
+    def register(self, preimages, stream=None):
+        """``register_hash`` for a batch: preimages (count, 8, 4) or a flat list of ints -> digests (count, 4), a device tensor"""
+        import torch
+
+        dp = _elems(preimages)
+        count = dp.numel() // 32
+        digests = torch.empty((count, 4), dtype=torch.int64, device="cuda")
+        _lib.check(_lib.load().lurk_hip_trie_nodes_register_dev(self._h, _lib.ptr(dp) if count else None, count, _lib.ptr(digests), _lib.ptr(stream)))
+        return digests
+
+    def add_trie(self, trie: DeviceTrie, stream=None):
+        """Every node of a built ``DeviceTrie``; nothing is hashed."""
+        _lib.check(_lib.load().lurk_hip_trie_nodes_add_trie(self._h, trie._h, _lib.ptr(stream)))
+
+    def get(self, digests, stream=None):
+        """-> (preimages (m, 8, 4), found (m,) int32), device tensors; a digest that is not in the store gives a zero row"""
+        import torch
+
+        dd = _elems(digests)
+        m = dd.numel() // 4
+        pre = torch.empty((m, 8, 4), dtype=torch.int64, device="cuda")
+        found = torch.empty(max(m, 1), dtype=torch.int32, device="cuda")
+        _lib.check(_lib.load().lurk_hip_trie_nodes_get_dev(self._h, _lib.ptr(dd), m, _lib.ptr(pre), _lib.ptr(found), _lib.ptr(stream)))
+        return pre, found[:m]
+
+    @staticmethod
+    def _stride(dr, m: int) -> int:
+        return 0 if dr.numel() == 4 and m != 1 else 1
+
+    def prove_lookup(self, roots, keys, stream=None):
+        """``roots``: one root for every key (a single element) or one per key -> (paths (m, H, 8, 4), values (m, 4), status (m,) int32,
+        n_missing); status k + 1 = the node expected at level k is not in the store"""
+        import torch
+
+        dr, dk = _elems(roots), _elems(keys)
+        m = dk.numel() // 4
+        paths = torch.empty((m, self.height, 8, 4), dtype=torch.int64, device="cuda")
+        values = torch.empty((m, 4), dtype=torch.int64, device="cuda")
+        status = torch.empty(max(m, 1), dtype=torch.int32, device="cuda")
+        missing = ctypes.c_uint64()
+        _lib.check(_lib.load().lurk_hip_trie_nodes_prove_lookup_dev(self._h, _lib.ptr(dr), self._stride(dr, m), _lib.ptr(dk), m, _lib.ptr(paths), _lib.ptr(values),
+                                                                    _lib.ptr(status), ctypes.byref(missing), _lib.ptr(stream)))
+        return paths, values, status[:m], missing.value
+
+    def prove_insert(self, roots, keys, values, *, register_new=True, stream=None):
+        """m independent insertions, each at its own root -> (old paths, new paths, old values, new roots, status, n_missing); with
+        ``register_new`` every new root is addressable afterwards"""
+        import torch
+
+        dr, dk, dv = _elems(roots), _elems(keys), _elems(values)
+        m = dk.numel() // 4
+        old = torch.empty((m, self.height, 8, 4), dtype=torch.int64, device="cuda")
+        new = torch.empty_like(old)
+        old_values = torch.empty((m, 4), dtype=torch.int64, device="cuda")
+        new_roots = torch.empty((m, 4), dtype=torch.int64, device="cuda")
+        status = torch.empty(max(m, 1), dtype=torch.int32, device="cuda")
+        missing = ctypes.c_uint64()
+        _lib.check(_lib.load().lurk_hip_trie_nodes_prove_insert_dev(self._h, _lib.ptr(dr), self._stride(dr, m), _lib.ptr(dk), _lib.ptr(dv), m, _lib.ptr(old),
+                                                                    _lib.ptr(new), _lib.ptr(old_values), _lib.ptr(new_roots), _lib.ptr(status),
+                                                                    ctypes.byref(missing), 1 if register_new else 0, _lib.ptr(stream)))
+        return old, new, old_values, new_roots, status[:m], missing.value
+
+    def insert_chain(self, root: int, keys, values, *, paths=True, stream=None):
+        """A chain of dependent insertions that starts at the trie named by ``root`` (a Python int) -> (old paths, new paths, old values,
+        roots); every ``roots[i]`` is addressable afterwards and the result is ``roots[-1]``"""
+        import torch
+
+        dk, dv = _elems(keys), _elems(values)
+        m = dk.numel() // 4 if hasattr(dk, "numel") else 0
+        old = torch.empty((m, self.height, 8, 4), dtype=torch.int64, device="cuda") if paths else None
+        new = torch.empty_like(old) if paths else None
+        old_values = torch.empty((m, 4), dtype=torch.int64, device="cuda")
+        roots = torch.empty((m, 4), dtype=torch.int64, device="cuda")
+        root32 = _limbs([int(root)])
+        _lib.check(_lib.load().lurk_hip_trie_nodes_insert_chain_dev(self._h, _lib.ptr(root32), _lib.ptr(dk) if m else None, _lib.ptr(dv) if m else None, m,
+                                                                    _lib.ptr(old) if paths else None, _lib.ptr(new) if paths else None, _lib.ptr(old_values),
+                                                                    _lib.ptr(roots), _lib.ptr(stream)))
+        return old, new, old_values, roots
+
+    def close(self):
+        """Frees the table (296 B per slot).  Idempotent; the handle is unusable afterwards."""
+        h, self._h = self._h, None
+        if h:
+            _lib.check(_lib.load().lurk_hip_trie_nodes_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
         if getattr(self, "_h", None) is None:
             return
         try:

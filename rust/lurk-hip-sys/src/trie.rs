@@ -4,6 +4,7 @@
 //! * [`DeviceTrie`] - the opaque handle: one bulk build from pairs sorted by path value, then `prove_lookup` / `prove_insert` for batches
 //!   of keys, `insert_chain` for a sequence of dependent insertions, and the two verifiers for batches of proofs, all on device buffers
 //!   (raw pointers, as everywhere in this crate);
+//! * [`TrieNodes`] - the child map of every version of the trie, addressed by root: `new_with_root` on the device;
 //! * [`LookupProof`] / [`InsertProof`] - shaped like the reference's (`:339-369`): a `preimage_path` of `HEIGHT` preimages of `ARITY`
 //!   elements, root level first.  [`LookupProof::from_flat`] cuts them out of a batch copied back to the host, and `flat` is what a
 //!   verifier call takes.
@@ -101,6 +102,87 @@ impl DeviceTrie {
 impl Drop for DeviceTrie {
     fn drop(&mut self) {
         unsafe { lurk_hip_trie_destroy(self.handle) };
+    }
+}
+
+/// The trie's child map on the device (`lurk_hip_trie_nodes`; `include/lurk_hip.h`, "root-addressed tries"): every version of every trie of
+/// one (field, height), content-addressed and append-only.  What `Trie::new_with_root` (`:566-576`) and a host-side root -> handle table
+/// were for: a root goes in as an element and the walk happens on the device.
+pub struct TrieNodes {
+    handle: *mut lurk_hip_trie_nodes,
+}
+unsafe impl Send for TrieNodes {}
+
+/// How many queries of a root-addressed call met a node that is not in the store (`Error::MissingPreimage`); `d_status` says which.
+pub struct Missing {
+    pub n_missing: u64,
+}
+
+impl TrieNodes {
+    /// `init_empty`: the store holds the `height` nodes of the empty chain.
+    pub fn create(field_id: c_int, height: usize, reserve_nodes: usize) -> Result<Self, Error> {
+        let mut handle = core::ptr::null_mut();
+        check(unsafe { lurk_hip_trie_nodes_create(&mut handle, field_id, height as c_int, reserve_nodes) })?;
+        Ok(Self { handle })
+    }
+    /// (field id, height, nodes, slots, device)
+    pub fn info(&self) -> Result<(c_int, usize, usize, usize, c_int), Error> {
+        let (mut field, mut height, mut n, mut slots, mut device) = (0, 0, 0usize, 0usize, 0);
+        check(unsafe { lurk_hip_trie_nodes_info(self.handle, &mut field, &mut height, &mut n, &mut slots, &mut device) })?;
+        Ok((field, height as usize, n, slots, device))
+    }
+    /// `register_hash` for `count` preimages; `d_digests_out` may be null.  Synchronises `stream`.
+    /// # Safety
+    /// device buffers: `count * 8` elements in, `count` digests out
+    pub unsafe fn register_dev(&mut self, d_preimages: *const c_void, count: usize, d_digests_out: *mut c_void, stream: *mut c_void) -> Result<(), Error> {
+        check(lurk_hip_trie_nodes_register_dev(self.handle, d_preimages, count, d_digests_out, stream))
+    }
+    /// Every node of a built trie of the same field and height; nothing is hashed.  Synchronises `stream`.
+    pub fn add_trie(&mut self, trie: &DeviceTrie, stream: *mut c_void) -> Result<(), Error> {
+        check(unsafe { lurk_hip_trie_nodes_add_trie(self.handle, trie.handle, stream) })
+    }
+    /// `InversePoseidonCache::get` for `m` digests.  Does not synchronise.
+    /// # Safety
+    /// device buffers: `m` digests in; `m * 8` elements and `m` u32 out
+    pub unsafe fn get_dev(&self, d_digests: *const c_void, m: usize, d_preimages: *mut c_void, d_found: *mut u32, stream: *mut c_void) -> Result<(), Error> {
+        check(lurk_hip_trie_nodes_get_dev(self.handle, d_digests, m, d_preimages, d_found, stream))
+    }
+    /// `new_with_root` + `prove_lookup` per query.  `one_root`: `d_roots` holds one root for every query, otherwise one per query.
+    /// `count_missing` waits for the walk and reports how many statuses are non-zero.
+    /// # Safety
+    /// device buffers: roots and `m` keys in; `m * height * 8` path elements, `m` values and `m` u32 statuses out
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn prove_lookup_dev(&self, d_roots: *const c_void, one_root: bool, d_keys: *const c_void, m: usize, d_paths: *mut c_void, d_values: *mut c_void,
+                                   d_status: *mut u32, count_missing: bool, stream: *mut c_void) -> Result<Option<Missing>, Error> {
+        let mut n_missing = 0u64;
+        let out = if count_missing { &mut n_missing as *mut u64 } else { core::ptr::null_mut() };
+        check(lurk_hip_trie_nodes_prove_lookup_dev(self.handle, d_roots, usize::from(!one_root), d_keys, m, d_paths, d_values, d_status, out, stream))?;
+        Ok(count_missing.then_some(Missing { n_missing }))
+    }
+    /// `m` independent `new_with_root` + `prove_insert`; with `register_new` every new root is addressable when the call returns.
+    /// # Safety
+    /// device buffers as `DeviceTrie::prove_insert_dev`, and `m` u32 statuses out
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn prove_insert_dev(&mut self, d_roots: *const c_void, one_root: bool, d_keys: *const c_void, d_new_values: *const c_void, m: usize,
+                                   d_old_paths: *mut c_void, d_new_paths: *mut c_void, d_old_values: *mut c_void, d_new_roots: *mut c_void, d_status: *mut u32,
+                                   register_new: bool, stream: *mut c_void) -> Result<Missing, Error> {
+        let mut n_missing = 0u64;
+        check(lurk_hip_trie_nodes_prove_insert_dev(self.handle, d_roots, usize::from(!one_root), d_keys, d_new_values, m, d_old_paths, d_new_paths, d_old_values,
+                                                   d_new_roots, d_status, &mut n_missing, c_int::from(register_new), stream))?;
+        Ok(Missing { n_missing })
+    }
+    /// A chain of `m` dependent insertions that starts at the trie named by `root`; every root it leaves is addressable afterwards.
+    /// # Safety
+    /// device buffers as `DeviceTrie::insert_chain_dev`; each output may be null
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn insert_chain_dev(&mut self, root: &Element, d_keys: *const c_void, d_values: *const c_void, m: usize, d_old_paths: *mut c_void,
+                                   d_new_paths: *mut c_void, d_old_values: *mut c_void, d_roots: *mut c_void, stream: *mut c_void) -> Result<(), Error> {
+        check(lurk_hip_trie_nodes_insert_chain_dev(self.handle, root.as_ptr().cast(), d_keys, d_values, m, d_old_paths, d_new_paths, d_old_values, d_roots, stream))
+    }
+}
+impl Drop for TrieNodes {
+    fn drop(&mut self) {
+        unsafe { lurk_hip_trie_nodes_destroy(self.handle) };
     }
 }
 
