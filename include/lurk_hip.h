@@ -38,8 +38,9 @@ extern "C" {
 #define LURK_FIELD_PALLAS_FQ 1 /* pasta_curves::Fq  = pallas::Scalar = vesta::Base  */
 #define LURK_FIELD_BN254_FR 2  /* halo2curves::bn256::Fr (the field of every KAT in the reference) */
 #define LURK_FIELD_BN254_FQ 3  /* halo2curves::bn256::Fq = grumpkin::Fr: the BN254 base field.  Offered where a commitment needs it
-                                * (the MSM contexts, the point helpers, lurk_hip_synth_scalars_dev); every other entry point that
-                                * takes a field id refuses it */
+                                * (the MSM contexts, the point helpers, lurk_hip_synth_scalars_dev) and as the field of a shape made by
+                                * lurk_hip_r1cs_create_for_curve(LURK_CURVE_GRUMPKIN) - what a folding context on Grumpkin runs over;
+                                * every other entry point that takes a field id as an argument refuses it */
 
 /* curve ids (CurveCycleEquipped engines, /root/reference/src/proof/nova.rs:40-71) */
 #define LURK_CURVE_PALLAS 0
@@ -48,13 +49,14 @@ extern "C" {
  * Fq with scalars in Fr, Grumpkin is y^2 = x^3 - 17 over Fr with scalars in Fq.  Layouts as halo2curves `repr-c` has them, recalled
  * [MEM] and unpinned like the Pasta ones: affine {x, y} 64 B Montgomery with (0, 0) for the identity, Jacobian {x, y, z} 96 B.
  * Offered: every lurk_hip_msm_* / lurk_hip_msm_ctx_* / lurk_hip_msm_multi_* commitment path, the point helpers,
- * lurk_hip_synth_bases_dev (generators (1, 2) and (1, sqrt(-16))) and lurk_hip_fold_ctx_* on BN254 with a caller-supplied challenge;
+ * lurk_hip_synth_bases_dev (generators (1, 2) and (1, sqrt(-16))) and lurk_hip_fold_ctx_* on both curves with a caller-supplied
+ * challenge (Grumpkin over a shape from lurk_hip_r1cs_create_for_curve: its scalar field is LURK_FIELD_BN254_FQ);
  * on BN254 G1 alone the HyperKZG opening argument (lurk_hip_hyperkzg_prove_dev, lurk_hip_hyperkzg_pairing_inputs) and the powers-of-tau
  * test key (lurk_hip_synth_kzg_bases_dev), which refuse Grumpkin and the Pasta curves by name, and the compressing SNARK whose opening
  * is that argument (lurk_hip_spartan_kzg_prove*_dev, lurk_hip_spartan_kzg_verify*_dev; the Pasta / IPA calls keep refusing BN254).
  * Refused by name (non-zero, the curve named in lurk_hip_last_error()): lurk_hip_msm_ctx_from_label and the other hash-to-curve calls,
  * lurk_hip_msm_ctx_fold_key_dev, the IPA / Spartan / verify calls, lurk_hip_fold_step, _set_pp_digest, _challenge and
- * lurk_hip_nifs_* (no Poseidon constants over Fq yet), and a folding context on Grumpkin. */
+ * lurk_hip_nifs_* (no Poseidon constants over either base field of this cycle yet). */
 #define LURK_CURVE_BN254 2
 #define LURK_CURVE_GRUMPKIN 3
 
@@ -73,7 +75,7 @@ const char* lurk_hip_version(void);
  * that reports >= n until a revision says otherwise.  4: the verifiers - lurk_hip_r1cs_sparse_mle_dev, lurk_hip_ipa_s_vector_dev,
  * lurk_hip_sumcheck_verify, lurk_hip_ipa_verify_dev, lurk_hip_spartan_verify_dev, lurk_hip_spartan_verify_batch_dev (additions only);
  * later additions under the same number (a binding probes for them by symbol): lurk_hip_r1cs_transpose_dev, lurk_hip_r1cs_read,
- * lurk_hip_grid_cus, the four lurk_hip_trie_circuit_* calls, the nine lurk_hip_trie_nodes_* calls.
+ * lurk_hip_grid_cus, the four lurk_hip_trie_circuit_* calls, the nine lurk_hip_trie_nodes_* calls, lurk_hip_r1cs_create_for_curve.
  * 3: lurk_hip_slot_constraints_size / lurk_hip_slot_constraints,
  * lurk_hip_frames_r1cs_create, lurk_hip_r1cs_is_sat_dev (additions only).  2 (round 6): lurk_hip_msm_ctx_info's *precomputed is a boolean (the key's form comes from lurk_hip_msm_ctx_form),
  * LURK_MSM_SLOTS is 6, LURK_MSM_SUBMIT_FOLLOW, the parameter blocks lurk_hip_ro_params / lurk_hip_ck_params, lurk_hip_scratch_trim.
@@ -737,6 +739,19 @@ int lurk_hip_r1cs_create(lurk_hip_r1cs** shape, int field_id, size_t num_cons, s
                          const void* a_data, const uint64_t* b_indptr, const uint64_t* b_indices,
                          const void* b_data, const uint64_t* c_indptr, const uint64_t* c_indices,
                          const void* c_data);
+/* The same shape over the SCALAR field of `curve` (Pallas: LURK_FIELD_PALLAS_FQ, Vesta: LURK_FIELD_PALLAS_FP, BN254:
+ * LURK_FIELD_BN254_FR, Grumpkin: LURK_FIELD_BN254_FQ): validation, dictionary and long-row list are lurk_hip_r1cs_create's.  The one
+ * way to a shape over the BN254 base field - lurk_hip_r1cs_create keeps refusing field id 3 - for the circuit a folding context on
+ * Grumpkin folds (the default cycle's secondary half).  lurk_hip_r1cs_dims reports the field id.  A shape over LURK_FIELD_BN254_FQ is
+ * served by lurk_hip_r1cs_multiply_vec(_dev), lurk_hip_r1cs_cross_term(_dev), lurk_hip_r1cs_cross_term_cached_dev,
+ * lurk_hip_r1cs_is_sat_dev, lurk_hip_r1cs_read, _info, _dims, _device, _destroy and lurk_hip_fold_ctx_create(_multi); everything else
+ * that takes a shape (lurk_hip_r1cs_transpose_dev, lurk_hip_r1cs_sparse_mle_dev, the compressing provers and verifiers) refuses it with
+ * nothing launched.  An unknown curve id is refused by name. */
+int lurk_hip_r1cs_create_for_curve(lurk_hip_r1cs** shape, int curve, size_t num_cons, size_t num_vars,
+                                   size_t num_io, const uint64_t* a_indptr, const uint64_t* a_indices,
+                                   const void* a_data, const uint64_t* b_indptr, const uint64_t* b_indices,
+                                   const void* b_data, const uint64_t* c_indptr, const uint64_t* c_indices,
+                                   const void* c_data);
 int lurk_hip_r1cs_destroy(lurk_hip_r1cs* shape);
 int lurk_hip_r1cs_dims(const lurk_hip_r1cs* shape, int* field_id, size_t* num_cons, size_t* num_vars, size_t* num_io);
 int lurk_hip_r1cs_info(const lurk_hip_r1cs* shape, size_t* nnz_a, size_t* nnz_b, size_t* nnz_c,
@@ -758,7 +773,8 @@ int lurk_hip_r1cs_device(const lurk_hip_r1cs* shape, int* device); /* the device
  * three matrices - twice that matrix's resident entry array - plus the sort's own storage (histograms and look-back state, a few per
  * cent of the entry array) and 8 B per 256 rows of the result.
  * Refused with LURK_HIP_ERR_INVALID_ARG before anything is allocated or launched, *out = NULL: a NULL shape or out, num_cons = 0,
- * rows_t non-zero and below ncols, rows_t >= 2^32, a source that is not resident on the calling thread's current device.  An
+ * rows_t non-zero and below ncols, rows_t >= 2^32, a source that is not resident on the calling thread's current device, a source over
+ * LURK_FIELD_BN254_FQ (nothing downstream of a transpose is offered over that field).  An
  * allocation that fails returns LURK_HIP_ERR_OOM and leaves nothing behind. */
 int lurk_hip_r1cs_transpose_dev(const lurk_hip_r1cs* shape, size_t rows_t, lurk_hip_r1cs** out, void* stream);
 /* Matrix `which` (0 = A, 1 = B, 2 = C) of a resident shape as the CSR lurk_hip_r1cs_create takes: indptr num_cons + 1 entries, indices
@@ -818,7 +834,9 @@ int lurk_hip_fold_padded_dev(int field_id, int count, const void* const* d_vecs,
  * What RecursiveSNARK::prove_step (/root/reference/src/proof/nova.rs:282-295, SuperNova /root/reference/src/proof/
  * supernova.rs:231-244) runs per curve through arecibo's NIFS::prove, with the running pair (z1 = [W1 | u1 | X1], E1)
  * resident in HBM from step to step.  A prover holds one context per curve: Pallas (primary, the Lurk step circuit) and
- * Vesta (secondary).  shape and key are borrowed (same curve / scalar field, created on the same device) and must outlive
+ * Vesta (secondary), or on lurk-beta's default cycle BN254 (primary) and Grumpkin (secondary, over a shape from
+ * lurk_hip_r1cs_create_for_curve).  On the BN254 cycle the caller derives r itself: lurk_hip_fold_step, _set_pp_digest and
+ * _challenge refuse both curves by name and leave an open step usable.  shape and key are borrowed (same curve / scalar field, created on the same device) and must outlive
  * the context; the context uses the key's async slots (W2: 0 and 2 alternately, T: 1, late ranges: 3).  The challenge r is a
  * Poseidon sponge over the OTHER field of the cycle absorbing the two commitments `begin` returns, hence two halves (a caller
  * with its own transcript uses them; lurk_hip_fold_step below runs begin, the library's own transcript and finish in one call):

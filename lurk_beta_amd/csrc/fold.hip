@@ -26,8 +26,23 @@
 
 #include "common.hpp"
 #include "dispatch.hpp"
+#include "r1cs_bn254fq.hpp"
 #include "r1cs_shape.cuh"
 
+// Fields.  The kernels below are templates over the field pack.  This unit instantiates them over the three fields of with_field; over
+// Bn254Fq (the BN254 base field: Grumpkin's scalar field) they are instantiated by fold_bn254fq.hip, which includes this file under
+// LURK_FOLD_BN254FQ_TU and defines the *_bn254fq functions of r1cs_bn254fq.hpp - this unit only calls those.
+// The lazy-accumulation bounds for p = BN254_P (0x30644e72...d87cfd47, 2^253.6: above BN254_R by 2^127, below both Pasta moduli).  Every
+// bound of the row code is an UPPER bound that p enters through p < 2^254.1 alone, so each carries over to the smaller modulus as stated:
+//   dot29_mac        columns of products of tight limbs (< 2^58 each, 9 per term and column): 45 products + the reduction's 10 terms
+//                    < 55 * 2^58 < 2^64.  Independent of p; row_mac normalises every fourth term (36 products per column in between).
+//   32 (-u) 2^256    fe_neg returns a canonical value < p; f29_from_mont256 shifts by 5: tight, < 32 p < 2^258.6 (< 2^259 as stated).
+//   r1cs_row         a term is coefficient (canonical, < p) x element (< 32 p) / 2^261 < p^2 / 2^256 < 2^251.2 (< 2^253 as stated); 64
+//                    terms and the re-entered partial sum stay < 2^259 + p, a group's 256-entry sum < 256 * 2^252 + 16 p < 2^261; and
+//                    dot29_finish returns < A / 2^261 + p, tight.  f29_to_mont256: (a r256 + m p) / 2^261 < 2 p for a < 2^261, which
+//                    fe_cond_sub2 + fe_cond_sub bring below p.
+// What does depend on the modulus is the FORM of the product: Bn254Fq is not 1 mod 2^29, so f29_p1_form is false and f29_mul30 /
+// dot29_finish take the general rows (field29_mul_asm_bn254fq.cuh, f29_reduce) - the signed / p1 rows of field29.cuh are not reachable.
 namespace lurk {
 
 
@@ -386,7 +401,7 @@ static void upload_matrix(R1csShape& sh, int which, const uint64_t* indptr, cons
             it = ids.emplace(key, id).first;
             dict_words.resize(dict_words.size() + P29_STRIDE);
             uint32_t* rec = dict_words.data() + (size_t)id * P29_STRIDE;
-            with_field(sh.field_id, [&](auto F) { dict_record<decltype(F)>(key.w, rec); });
+            with_scalar_field(sh.field_id, [&](auto F) { dict_record<decltype(F)>(key.w, rec); });
         }
         ent[k] = make_uint2((uint32_t)indices[k], it->second);
     }
@@ -498,6 +513,63 @@ static void fold_padded(int count, const void* const* vecs, const size_t* lens, 
     LURK_HIP_CHECK(hipGetLastError());
 }
 
+#ifdef LURK_FOLD_BN254FQ_TU  // fold_bn254fq.hip: the instantiations over the BN254 base field, a code object of their own
+void multiply_vec_bn254fq(const R1csShape& sh, const void* d_z, void* az, void* bz, void* cz, hipStream_t s) { multiply_vec<Bn254Fq>(sh, d_z, az, bz, cz, s); }
+void cross_term_bn254fq(const R1csShape& sh, const void* d_z1, const void* d_z2, void* d_t, hipStream_t s) { cross_term<Bn254Fq>(sh, d_z1, d_z2, d_t, s); }
+void cross_term_cached_bn254fq(const R1csShape& sh, const void* d_z2, void* az1, void* bz1, void* cz1, const void* u1_32, const void* prev_a, const void* prev_b,
+                               const void* prev_c, const void* r_prev32, void* d_t, void* az2, void* bz2, void* cz2, hipStream_t s) {
+    cross_term_cached<Bn254Fq>(sh, d_z2, az1, bz1, cz1, u1_32, prev_a, prev_b, prev_c, r_prev32, d_t, az2, bz2, cz2, s);
+}
+void fold_vecs_bn254fq(int count, const void* const* a, const void* const* b, const size_t* n, void* const* out, const void* r32, hipStream_t s) {
+    fold_vecs<Bn254Fq>(count, a, b, n, out, r32, s);
+}
+void fold_vec_bn254fq(const void* a, const void* b, const void* r32, size_t n, void* out, hipStream_t s) { fold_vec<Bn254Fq>(a, b, r32, n, out, s); }
+
+}  // namespace lurk
+#else
+// lurk_hip_r1cs_create and lurk_hip_r1cs_create_for_curve: the caller has checked field_id
+static void r1cs_create_over(lurk_hip_r1cs** out, int field_id, size_t num_cons, size_t num_vars, size_t num_io, const uint64_t* a_indptr,
+                             const uint64_t* a_indices, const void* a_data, const uint64_t* b_indptr, const uint64_t* b_indices, const void* b_data,
+                             const uint64_t* c_indptr, const uint64_t* c_indices, const void* c_data) {
+    LURK_REQUIRE(num_vars + 1 + num_io < ((size_t)1 << 32), "z has more than 2^32 - 1 entries");
+    auto h = std::make_unique<lurk_hip_r1cs>();
+    R1csShape& sh = h->sh;
+    sh.field_id = field_id;
+    sh.num_cons = num_cons;
+    sh.num_vars = num_vars;
+    sh.num_io = num_io;
+    LURK_HIP_CHECK(hipGetDevice(&sh.device));
+    std::unordered_map<Key32, uint32_t, Key32Hash> ids;
+    std::vector<uint32_t> dict_words;
+    const size_t ncols = num_vars + 1 + num_io;
+    upload_matrix(sh, 0, a_indptr, a_indices, a_data, ncols, ids, dict_words);
+    upload_matrix(sh, 1, b_indptr, b_indices, b_data, ncols, ids, dict_words);
+    upload_matrix(sh, 2, c_indptr, c_indices, c_data, ncols, ids, dict_words);
+    sh.dict_size = ids.size();
+    {   // closing record: the Montgomery one (1 * 2^256 mod p as the ABI stores it)
+        dict_words.resize(dict_words.size() + P29_STRIDE);
+        uint32_t* rec = dict_words.data() + sh.dict_size * P29_STRIDE;
+        uint64_t one[4];
+        with_scalar_field(field_id, [&](auto F) {
+            Fe<decltype(F)> o = fe_one<decltype(F)>();
+            memcpy(one, o.l, 32);
+            dict_record<decltype(F)>(one, rec);
+        });
+    }
+    {   // rows the lane-per-row kernels leave to the wave-per-row ones
+        std::vector<uint32_t> lr;
+        for (size_t i = 0; i < num_cons; i++)
+            if (a_indptr[i + 1] - a_indptr[i] > FOLD_LONG || b_indptr[i + 1] - b_indptr[i] > FOLD_LONG || c_indptr[i + 1] - c_indptr[i] > FOLD_LONG)
+                lr.push_back((uint32_t)i);
+        sh.n_long = lr.size();
+        sh.long_rows.alloc(lr.size() * 4);
+        if (!lr.empty()) LURK_HIP_CHECK(hipMemcpy(sh.long_rows.p, lr.data(), lr.size() * 4, hipMemcpyHostToDevice));
+    }
+    sh.dict.alloc(dict_words.size() * 4);
+    if (!dict_words.empty()) LURK_HIP_CHECK(hipMemcpy(sh.dict.p, dict_words.data(), dict_words.size() * 4, hipMemcpyHostToDevice));
+    *out = h.release();
+}
+
 }  // namespace lurk
 
 using namespace lurk;
@@ -511,43 +583,18 @@ int lurk_hip_r1cs_create(lurk_hip_r1cs** out, int field_id, size_t num_cons, siz
         LURK_REQUIRE(out, "null output handle");
         *out = nullptr;
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
-        LURK_REQUIRE(num_vars + 1 + num_io < ((size_t)1 << 32), "z has more than 2^32 - 1 entries");
-        auto h = std::make_unique<lurk_hip_r1cs>();
-        R1csShape& sh = h->sh;
-        sh.field_id = field_id;
-        sh.num_cons = num_cons;
-        sh.num_vars = num_vars;
-        sh.num_io = num_io;
-        LURK_HIP_CHECK(hipGetDevice(&sh.device));
-        std::unordered_map<Key32, uint32_t, Key32Hash> ids;
-        std::vector<uint32_t> dict_words;
-        const size_t ncols = num_vars + 1 + num_io;
-        upload_matrix(sh, 0, a_indptr, a_indices, a_data, ncols, ids, dict_words);
-        upload_matrix(sh, 1, b_indptr, b_indices, b_data, ncols, ids, dict_words);
-        upload_matrix(sh, 2, c_indptr, c_indices, c_data, ncols, ids, dict_words);
-        sh.dict_size = ids.size();
-        {   // closing record: the Montgomery one (1 * 2^256 mod p as the ABI stores it)
-            dict_words.resize(dict_words.size() + P29_STRIDE);
-            uint32_t* rec = dict_words.data() + sh.dict_size * P29_STRIDE;
-            uint64_t one[4];
-            with_field(field_id, [&](auto F) {
-                Fe<decltype(F)> o = fe_one<decltype(F)>();
-                memcpy(one, o.l, 32);
-                dict_record<decltype(F)>(one, rec);
-            });
-        }
-        {   // rows the lane-per-row kernels leave to the wave-per-row ones
-            std::vector<uint32_t> lr;
-            for (size_t i = 0; i < num_cons; i++)
-                if (a_indptr[i + 1] - a_indptr[i] > FOLD_LONG || b_indptr[i + 1] - b_indptr[i] > FOLD_LONG || c_indptr[i + 1] - c_indptr[i] > FOLD_LONG)
-                    lr.push_back((uint32_t)i);
-            sh.n_long = lr.size();
-            sh.long_rows.alloc(lr.size() * 4);
-            if (!lr.empty()) LURK_HIP_CHECK(hipMemcpy(sh.long_rows.p, lr.data(), lr.size() * 4, hipMemcpyHostToDevice));
-        }
-        sh.dict.alloc(dict_words.size() * 4);
-        if (!dict_words.empty()) LURK_HIP_CHECK(hipMemcpy(sh.dict.p, dict_words.data(), dict_words.size() * 4, hipMemcpyHostToDevice));
-        *out = h.release();
+        r1cs_create_over(out, field_id, num_cons, num_vars, num_io, a_indptr, a_indices, a_data, b_indptr, b_indices, b_data, c_indptr, c_indices, c_data);
+    });
+}
+
+int lurk_hip_r1cs_create_for_curve(lurk_hip_r1cs** out, int curve, size_t num_cons, size_t num_vars, size_t num_io, const uint64_t* a_indptr,
+                                   const uint64_t* a_indices, const void* a_data, const uint64_t* b_indptr, const uint64_t* b_indices, const void* b_data,
+                                   const uint64_t* c_indptr, const uint64_t* c_indices, const void* c_data) {
+    return guarded([&] {
+        LURK_REQUIRE(out, "null output handle");
+        *out = nullptr;
+        r1cs_create_over(out, curve_scalar_field_id(curve), num_cons, num_vars, num_io, a_indptr, a_indices, a_data, b_indptr, b_indices, b_data, c_indptr, c_indices,
+                         c_data);
     });
 }
 
@@ -591,7 +638,8 @@ int lurk_hip_r1cs_multiply_vec_dev(const lurk_hip_r1cs* shape, const void* d_z, 
         LURK_REQUIRE(shape && d_z && d_az && d_bz && d_cz, "null argument");
         DeviceGuard dg(shape->sh.device);
         const R1csShape& sh = shape->sh;
-        with_field(sh.field_id, [&](auto F) { multiply_vec<decltype(F)>(sh, d_z, d_az, d_bz, d_cz, (hipStream_t)stream); });
+        if (sh.field_id == LURK_FIELD_BN254_FQ) multiply_vec_bn254fq(sh, d_z, d_az, d_bz, d_cz, (hipStream_t)stream);
+        else with_field(sh.field_id, [&](auto F) { multiply_vec<decltype(F)>(sh, d_z, d_az, d_bz, d_cz, (hipStream_t)stream); });
     });
 }
 
@@ -600,7 +648,8 @@ int lurk_hip_r1cs_cross_term_dev(lurk_hip_r1cs* shape, const void* d_z1, const v
         LURK_REQUIRE(shape && d_z1 && d_z2 && d_t, "null argument");
         DeviceGuard dg(shape->sh.device);
         const R1csShape& sh = shape->sh;
-        with_field(sh.field_id, [&](auto F) { cross_term<decltype(F)>(sh, d_z1, d_z2, d_t, (hipStream_t)stream); });
+        if (sh.field_id == LURK_FIELD_BN254_FQ) cross_term_bn254fq(sh, d_z1, d_z2, d_t, (hipStream_t)stream);
+        else with_field(sh.field_id, [&](auto F) { cross_term<decltype(F)>(sh, d_z1, d_z2, d_t, (hipStream_t)stream); });
     });
 }
 
@@ -614,6 +663,11 @@ int lurk_hip_r1cs_cross_term_cached_dev(lurk_hip_r1cs* shape, const void* d_z2, 
         LURK_REQUIRE(!prev || (d_az2_prev != d_az2 && d_bz2_prev != d_bz2 && d_cz2_prev != d_cz2), "the previous products are read while the new ones are written: two buffers");
         DeviceGuard dg(shape->sh.device);
         const R1csShape& sh = shape->sh;
+        if (sh.field_id == LURK_FIELD_BN254_FQ) {
+            cross_term_cached_bn254fq(sh, d_z2, d_az1, d_bz1, d_cz1, u1_32_mont, d_az2_prev, d_bz2_prev, d_cz2_prev, r_prev32_mont, d_t, d_az2, d_bz2, d_cz2,
+                                      (hipStream_t)stream);
+            return;
+        }
         with_field(sh.field_id, [&](auto F) {
             cross_term_cached<decltype(F)>(sh, d_z2, d_az1, d_bz1, d_cz1, u1_32_mont, d_az2_prev, d_bz2_prev, d_cz2_prev, r_prev32_mont, d_t, d_az2, d_bz2, d_cz2,
                                            (hipStream_t)stream);
@@ -621,20 +675,34 @@ int lurk_hip_r1cs_cross_term_cached_dev(lurk_hip_r1cs* shape, const void* d_z2, 
     });
 }
 
+}  // extern "C"
+
+// The body of lurk_hip_fold_vecs_dev over the scalar fields of all four curves (r1cs_bn254fq.hpp): a folding context calls it directly.
+// (Defined here, where the public call always stood: the order in which this unit instantiates its kernels, and with it its code object, stays.)
+namespace lurk {
+void fold_vecs_scalar_field(int field_id, int count, const void* const* d_a, const void* const* d_b, const size_t* n, void* const* d_out, const void* r32_mont,
+                            hipStream_t s) {
+    LURK_REQUIRE(count >= 0 && count <= FOLD_VECS_MAX, "at most 8 vectors per launch");
+    LURK_REQUIRE(count == 0 || (d_a && d_b && n && d_out), "null argument");
+    LURK_REQUIRE(r32_mont, "null challenge");
+    size_t blocks = 0;
+    for (int k = 0; k < count; k++) {
+        LURK_REQUIRE(n[k] == 0 || (d_a[k] && d_b[k] && d_out[k]), "null buffer");
+        blocks += div_up(n[k], (size_t)FOLD_BLOCK * FOLD_VEC_E);
+    }
+    LURK_REQUIRE(blocks < ((size_t)1 << 31), "too many elements for one launch");
+    if (field_id == LURK_FIELD_BN254_FQ) fold_vecs_bn254fq(count, d_a, d_b, n, d_out, r32_mont, s);
+    else with_field(field_id, [&](auto F) { fold_vecs<decltype(F)>(count, d_a, d_b, n, d_out, r32_mont, s); });
+}
+}  // namespace lurk
+
+extern "C" {
+
 int lurk_hip_fold_vecs_dev(int field_id, int count, const void* const* d_a, const void* const* d_b, const size_t* n, void* const* d_out,
                            const void* r32_mont, void* stream) {
     return guarded([&] {
-        LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
-        LURK_REQUIRE(count >= 0 && count <= FOLD_VECS_MAX, "at most 8 vectors per launch");
-        LURK_REQUIRE(count == 0 || (d_a && d_b && n && d_out), "null argument");
-        LURK_REQUIRE(r32_mont, "null challenge");
-        size_t blocks = 0;
-        for (int k = 0; k < count; k++) {
-            LURK_REQUIRE(n[k] == 0 || (d_a[k] && d_b[k] && d_out[k]), "null buffer");
-            blocks += div_up(n[k], (size_t)FOLD_BLOCK * FOLD_VEC_E);
-        }
-        LURK_REQUIRE(blocks < ((size_t)1 << 31), "too many elements for one launch");
-        with_field(field_id, [&](auto F) { fold_vecs<decltype(F)>(count, d_a, d_b, n, d_out, r32_mont, (hipStream_t)stream); });
+        LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");  // (the fourth field is a folding context's alone: step.hip)
+        fold_vecs_scalar_field(field_id, count, d_a, d_b, n, d_out, r32_mont, (hipStream_t)stream);
     });
 }
 
@@ -703,13 +771,26 @@ int lurk_hip_fold_vec(int field_id, const void* a, const void* b, const void* r3
     });
 }
 
+}  // extern "C"
+
+// the body of lurk_hip_fold_vec_dev, likewise
+namespace lurk {
+void fold_vec_scalar_field(int field_id, const void* d_a, const void* d_b, const void* r32_mont, size_t n, void* d_out, hipStream_t s) {
+    LURK_REQUIRE(n == 0 || (d_a && d_b && d_out), "null buffer");
+    LURK_REQUIRE(r32_mont, "null challenge");
+    if (field_id == LURK_FIELD_BN254_FQ) fold_vec_bn254fq(d_a, d_b, r32_mont, n, d_out, s);
+    else with_field(field_id, [&](auto F) { fold_vec<decltype(F)>(d_a, d_b, r32_mont, n, d_out, s); });
+}
+}  // namespace lurk
+
+extern "C" {
+
 int lurk_hip_fold_vec_dev(int field_id, const void* d_a, const void* d_b, const void* r32_mont, size_t n, void* d_out, void* stream) {
     return guarded([&] {
         LURK_REQUIRE(field_id >= 0 && field_id <= 2, "unknown field id");
-        LURK_REQUIRE(n == 0 || (d_a && d_b && d_out), "null buffer");
-        LURK_REQUIRE(r32_mont, "null challenge");
-        with_field(field_id, [&](auto F) { fold_vec<decltype(F)>(d_a, d_b, r32_mont, n, d_out, (hipStream_t)stream); });
+        fold_vec_scalar_field(field_id, d_a, d_b, r32_mont, n, d_out, (hipStream_t)stream);
     });
 }
 
 }  // extern "C"
+#endif  // LURK_FOLD_BN254FQ_TU

@@ -21,6 +21,7 @@
 #include <memory>
 
 #include "dispatch.hpp"
+#include "r1cs_bn254fq.hpp"
 #include "r1cs_shape.cuh"
 #include "slot_circuit.hpp"
 
@@ -162,6 +163,14 @@ static void is_sat(const R1csShape& sh, const void* d_z, const void* d_e, uint64
     *first_unsat = plan.host[3];
 }
 
+#ifdef LURK_SAT_BN254FQ_TU  // r1cs_sat_bn254fq.hip: the instantiation over the BN254 base field, a code object of its own (the row bounds
+                            // for this modulus: fold.hip); this unit reaches it through r1cs_bn254fq.hpp only
+void is_sat_bn254fq(const R1csShape& sh, const void* d_z, const void* d_e, uint64_t* n_unsat, uint64_t* first_unsat, hipStream_t s) {
+    is_sat<Bn254Fq>(sh, d_z, d_e, n_unsat, first_unsat, s);
+}
+
+}  // namespace lurk
+#else
 // ---- the slot gadgets' rows ------------------------------------------------------------------------------------
 static bool slot_is_hash_type(int slot_type) { return slot_type == 3 || slot_type == 4 || slot_type == 6 || slot_type == 8; }
 
@@ -298,8 +307,10 @@ int lurk_hip_r1cs_is_sat_dev(const lurk_hip_r1cs* shape, const void* d_z, const 
         LURK_REQUIRE(shape && d_z && n_unsat && first_unsat, "null argument");
         const R1csShape& sh = shape->sh;
         LURK_REQUIRE(current_device() == sh.device, "the shape is resident on another device than the current one");
-        with_field(sh.field_id, [&](auto F) { is_sat<decltype(F)>(sh, d_z, d_e, n_unsat, first_unsat, (hipStream_t)stream); });
+        if (sh.field_id == LURK_FIELD_BN254_FQ) is_sat_bn254fq(sh, d_z, d_e, n_unsat, first_unsat, (hipStream_t)stream);
+        else with_field(sh.field_id, [&](auto F) { is_sat<decltype(F)>(sh, d_z, d_e, n_unsat, first_unsat, (hipStream_t)stream); });
     });
 }
 
 }  // extern "C"
+#endif  // LURK_SAT_BN254FQ_TU

@@ -166,6 +166,8 @@ int lurk_hip_r1cs_transpose_dev(const lurk_hip_r1cs* shape, size_t rows_t, lurk_
     return guarded([&] {
         LURK_REQUIRE(shape && out, "null argument");
         const R1csShape& src = shape->sh;
+        // a shape over the BN254 base field (lurk_hip_r1cs_create_for_curve on Grumpkin) folds; nothing that takes a transpose is offered over it
+        LURK_REQUIRE(src.field_id != LURK_FIELD_BN254_FQ, "lurk_hip_r1cs_transpose_dev is not offered for a shape over the BN254 base field (Grumpkin's scalar field)");
         const size_t ncols = src.num_vars + 1 + src.num_io, lim = (size_t)1 << 32;
         LURK_REQUIRE(src.num_cons > 0, "a shape without rows has no transpose (num_cons = 0)");
         LURK_REQUIRE(src.num_cons < lim, "more than 2^32 - 1 rows");
@@ -277,7 +279,7 @@ int lurk_hip_r1cs_read(const lurk_hip_r1cs* shape, int which, uint64_t* indptr, 
         std::vector<uint32_t> words(sh.dict_size * P29_STRIDE);
         if (!words.empty()) LURK_HIP_CHECK(hipMemcpy(words.data(), sh.dict.p, words.size() * 4, hipMemcpyDeviceToHost));
         std::vector<uint64_t> values(sh.dict_size * 4);
-        with_field(sh.field_id, [&](auto F) {
+        with_scalar_field(sh.field_id, [&](auto F) {
             for (size_t id = 0; id < sh.dict_size; id++) dict_value<decltype(F)>(words.data() + id * P29_STRIDE, values.data() + 4 * id);
         });
         char* out = (char*)data32_mont;  // no alignment promise

@@ -10,7 +10,10 @@
 // The transcript sits in the middle, so the entry point has two halves: `begin` (both commitments in flight on the key's
 // async slots, the cross term between them; returns when the two 96-byte commitments are on the host) and `finish(r)`.
 // The running pair (z1 = [W1 | u1 | X1], E1) never leaves HBM; a step's W2 may already be there (lurk_hip_slot_witness_dev).
-// A prover holds two of these contexts: Pallas (primary: the Lurk step circuit) and Vesta (secondary: ~10^4 constraints).
+// A prover holds two of these contexts: Pallas (primary: the Lurk step circuit) and Vesta (secondary: ~10^4 constraints) - or, on
+// lurk-beta's default cycle, BN254 and Grumpkin, with the challenge supplied by the caller.  A context's field is its curve's scalar
+// field; on Grumpkin that is the BN254 base field, which no entry point that takes a field id serves: the context reaches its host
+// helpers through with_scalar_field and its folds through fold_vecs_scalar_field (r1cs_bn254fq.hpp), never through the public calls.
 #include <chrono>
 #include <memory>
 #include <vector>
@@ -18,6 +21,7 @@
 #include "common.hpp"
 #include "dispatch.hpp"
 #include "nifs_pre.hpp"
+#include "r1cs_bn254fq.hpp"
 
 namespace lurk {
 
@@ -162,11 +166,12 @@ struct lurk_hip_fold_ctx {
 
 namespace lurk {
 
-// the calls that need the random oracle over the curve's base field: Poseidon constants over the BN254 base field do not exist yet
+// the calls that need the random oracle over the curve's base field: the transcript's Poseidon constants exist over neither base field
+// of the BN254 / Grumpkin cycle yet
 static void require_transcript(const lurk_hip_fold_ctx* c, const char* what) {
-    if (c->curve == LURK_CURVE_BN254)
-        throw HipFailure{LURK_HIP_ERR_INVALID_ARG, std::string(what) + " is not offered on BN254 (no random oracle over its base field yet): derive r on the host and call "
-                                                                       "lurk_hip_fold_step_finish"};
+    if (c->curve == LURK_CURVE_BN254 || c->curve == LURK_CURVE_GRUMPKIN)
+        throw HipFailure{LURK_HIP_ERR_INVALID_ARG, std::string(what) + " is not offered on " + curve_name(c->curve) +
+                                                       " (no random oracle over its base field yet): derive r on the host and call lurk_hip_fold_step_finish"};
 }
 
 // [u | X] <- [u1 + r | X1 + r X2] on the host (1 + num_io elements; u2 = 1)
@@ -198,7 +203,7 @@ static void fold_instance_settle(lurk_hip_fold_ctx* c) {
     nested_ok(lurk_hip_point_mul(c->curve, pair + 12, c->open_ct, c->owed_r, 1));
     nested_ok(lurk_hip_point_sum(c->curve, new_e, pair, 2));
     std::vector<uint64_t> new_ux = c->ux;
-    with_field(c->field_id, [&](auto F) { fold_ux_host<decltype(F)>(new_ux, c->open_x2, c->owed_r); });
+    with_scalar_field(c->field_id, [&](auto F) { fold_ux_host<decltype(F)>(new_ux, c->open_x2, c->owed_r); });
     memcpy(c->comm_w, new_w, 96);
     memcpy(c->comm_e, new_e, 96);
     c->ux.swap(new_ux);
@@ -436,7 +441,7 @@ static void fold_begin(lurk_hip_fold_ctx* c, const lurk_hip_w2_patch* patches, s
         LURK_HIP_CHECK(hipHostMalloc((void**)&c->pin, need + need / 2, hipHostMallocDefault));
         c->pin_cap = need + need / 2;
     }
-    with_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
+    with_scalar_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
     if (c->num_io) memcpy(c->pin + 32, x2_mont, c->num_io * 32);
     LURK_HIP_CHECK(hipMemcpyAsync(z2 + c->num_vars * 32, c->pin, (1 + c->num_io) * 32, hipMemcpyHostToDevice, c->stage_stream[b]));
     const bool late_own_key = patched && fold_late_key(c, patches, n_patches, patched, c->stage_stream[b]);
@@ -600,7 +605,7 @@ static void fold_begin_multi(lurk_hip_fold_ctx* c, const void* w2, int on_device
         LURK_HIP_CHECK(hipHostMalloc((void**)&c->pin, need * 2, hipHostMallocDefault));
         c->pin_cap = need * 2;
     }
-    with_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
+    with_scalar_field(c->field_id, [&](auto F) { mont_one<decltype(F)>(c->pin); });
     if (c->num_io) memcpy(c->pin + 32, x2_mont, c->num_io * 32);
     LURK_HIP_CHECK(hipMemcpyAsync(z2 + c->num_vars * 32, c->pin, need, hipMemcpyHostToDevice, c->stage_stream[0]));
     LURK_HIP_CHECK(hipEventRecord(c->staged_ev[b], c->stage_stream[0]));
@@ -647,7 +652,7 @@ static void fold_finish(lurk_hip_fold_ctx* c, const void* r32_mont) {
         // off the chain: the next cross term reads the cached products (folded inside its own launch) and u (a kernel argument), not z or E
         LURK_HIP_CHECK(hipStreamWaitEvent(c->fold_stream, c->t_ev, 0));  // T of this step is complete (the cross term ran on the context's stream)
         LURK_HIP_CHECK(hipStreamWaitEvent(c->fold_stream, c->staged_ev[c->open_buf], 0));  // ... and so is z2 (staged on its own stream)
-        nested_ok(lurk_hip_fold_vecs_dev(c->field_id, 2, a, b, n, o, r32_mont, c->fold_stream));
+        fold_vecs_scalar_field(c->field_id, 2, a, b, n, o, r32_mont, c->fold_stream);
         LURK_HIP_CHECK(hipEventRecord(c->folded_ev[c->open_buf], c->fold_stream));
         LURK_HIP_CHECK(hipEventRecord(c->efold_ev[c->tcur], c->fold_stream));
         LURK_HIP_CHECK(hipEventRecord(c->zfold_ev, c->fold_stream));
@@ -656,9 +661,9 @@ static void fold_finish(lurk_hip_fold_ctx* c, const void* r32_mont) {
         c->abc_buf = c->tcur;
         c->abc_pending = true;
         c->tcur ^= 1;
-        with_field(c->field_id, [&](auto F) { host_add_mont<decltype(F)>(c->u_host, r32_mont); });  // u <- u + r u2, u2 = 1 (a fresh instance is strict)
+        with_scalar_field(c->field_id, [&](auto F) { host_add_mont<decltype(F)>(c->u_host, r32_mont); });  // u <- u + r u2, u2 = 1 (a fresh instance is strict)
     } else {
-        nested_ok(lurk_hip_fold_vecs_dev(c->field_id, 2, a, b, n, o, r32_mont, c->stream));
+        fold_vecs_scalar_field(c->field_id, 2, a, b, n, o, r32_mont, c->stream);
         LURK_HIP_CHECK(hipEventRecord(c->folded_ev[c->open_buf], c->stream));
     }
     c->folded_valid[c->open_buf] = true;
@@ -678,19 +683,18 @@ extern "C" {
 static void fold_ctx_create(lurk_hip_fold_ctx** out, int curve, lurk_hip_r1cs* shape, lurk_hip_msm_ctx* key, lurk_hip_msm_multi* mkey) {
     LURK_REQUIRE(out && shape && (key || mkey), "null argument");
     *out = nullptr;
-    // Grumpkin's scalar field is the BN254 base field: fold.hip has no kernels over it
-    LURK_REQUIRE(curve != LURK_CURVE_GRUMPKIN, "a folding context is not offered on Grumpkin (the folding kernels do not cover its scalar field, the BN254 base field)");
-    LURK_REQUIRE(curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA || curve == LURK_CURVE_BN254, "unknown curve id");
+    LURK_REQUIRE(curve >= LURK_CURVE_PALLAS && curve <= LURK_CURVE_GRUMPKIN, "unknown curve id");
     auto c = std::make_unique<lurk_hip_fold_ctx>();
     c->curve = curve;
     int shape_field = 0;
     nested_ok(lurk_hip_r1cs_dims(shape, &shape_field, &c->num_cons, &c->num_vars, &c->num_io));
-    c->field_id = curve == LURK_CURVE_PALLAS ? LURK_FIELD_PALLAS_FQ : curve == LURK_CURVE_VESTA ? LURK_FIELD_PALLAS_FP : LURK_FIELD_BN254_FR;  // the curve's scalar field
+    c->field_id = curve_scalar_field_id(curve);  // (Grumpkin: the BN254 base field, a shape from lurk_hip_r1cs_create_for_curve)
     {   // four curves share the 64-byte point layout: a key over another curve would commit to garbage without a word
         const int key_curve = key ? msm_ctx_table_view(key).curve : msm_multi_curve(mkey);
         LURK_REQUIRE(key_curve == curve, std::string("the commitment key is over ") + curve_name(key_curve) + ", not " + curve_name(curve));
     }
-    LURK_REQUIRE(shape_field == c->field_id, "the shape is not over this curve's scalar field");
+    LURK_REQUIRE(shape_field == c->field_id, std::string("the shape is over ") + field_name(shape_field) + ", not over " + field_name(c->field_id) + ", the scalar field of " +
+                                                 curve_name(curve));
     c->shape = shape;
     c->key = key;
     c->mkey = mkey;
@@ -739,7 +743,7 @@ static void fold_ctx_create(lurk_hip_fold_ctx** out, int curve, lurk_hip_r1cs* s
         }
     }
     c->ux.assign(4 * (1 + c->num_io), 0);
-    if (curve != LURK_CURVE_BN254) {  // the transcript's width-25 Poseidon constants are generated on first use (~0.15 s): now, not inside the first step
+    if (curve == LURK_CURVE_PALLAS || curve == LURK_CURVE_VESTA) {  // the transcript's width-25 Poseidon constants are generated on first use (~0.15 s): now, not inside the first step
         uint64_t one[4] = {1, 0, 0, 0}, out[4];
         nested_ok(lurk_hip_nova_ro_squeeze(c->field_id == LURK_FIELD_PALLAS_FQ ? LURK_FIELD_PALLAS_FP : LURK_FIELD_PALLAS_FQ, one, 1, 128, out));
     }

@@ -18,21 +18,30 @@ class R1CSShape:
     usize column indices into z = [W | u | X], 32-byte Montgomery values) kept resident on the GPU."""
 
     def __init__(self, field_id: int, num_cons: int, num_vars: int, num_io: int, A, B, C):
-        lib = _lib.load()
         self.field_id, self.num_cons, self.num_vars, self.num_io = field_id, num_cons, num_vars, num_io
-        args = []
-        self._keep = []
-        for indptr, indices, data in (A, B, C):
+        self._h = self._create(_lib.load().lurk_hip_r1cs_create, field_id, num_cons, num_vars, num_io, (A, B, C))
+        self._keep = None  # the library copied everything
+
+    @staticmethod
+    def _create(create, field_or_curve: int, num_cons: int, num_vars: int, num_io: int, matrices):
+        args, keep = [], []
+        for indptr, indices, data in matrices:
             ip = np.ascontiguousarray(indptr, dtype=np.uint64)
             ix = np.ascontiguousarray(indices, dtype=np.uint64)
             dv = np.ascontiguousarray(data, dtype=np.uint64)
             if ip.size != num_cons + 1 or ix.size * 4 != dv.size:
                 raise ValueError("malformed CSR matrix")
-            self._keep += [ip, ix, dv]
+            keep += [ip, ix, dv]
             args += [_lib.ptr(ip), _lib.ptr(ix), _lib.ptr(dv)]
-        self._h = ctypes.c_void_p()
-        _lib.check(lib.lurk_hip_r1cs_create(ctypes.byref(self._h), field_id, num_cons, num_vars, num_io, *args))
-        self._keep = None  # the library copied everything
+        h = ctypes.c_void_p()
+        _lib.check(create(ctypes.byref(h), field_or_curve, num_cons, num_vars, num_io, *args))
+        return h
+
+    @classmethod
+    def for_curve(cls, curve: int, num_cons: int, num_vars: int, num_io: int, A, B, C) -> "R1CSShape":
+        """The same shape over the SCALAR field of ``curve`` (``lurk_hip_r1cs_create_for_curve``): the one way to a shape over the BN254
+        base field, Grumpkin's scalar field, which ``FoldingContext(CURVE_GRUMPKIN, shape, key)`` folds.  ``field_id`` reports the field."""
+        return cls._wrap(cls._create(_lib.load().lurk_hip_r1cs_create_for_curve, curve, num_cons, num_vars, num_io, (A, B, C)))
 
     @classmethod
     def _wrap(cls, handle) -> "R1CSShape":

@@ -224,6 +224,14 @@ class R1CSShape {
         check(lurk_hip_r1cs_create(&h_, field, num_cons, num_vars, num_io, a.indptr.data(), a.indices.data(), a.data.data(), b.indptr.data(),
                                    b.indices.data(), b.data.data(), c.indptr.data(), c.indices.data(), c.data.data()));
     }
+    // the same shape over the scalar field of `curve` (lurk_hip_r1cs_create_for_curve): the way to a shape over the BN254 base field,
+    // which FoldingContext(LURK_CURVE_GRUMPKIN, shape, key) folds; fold() is not offered over that field
+    static R1CSShape for_curve(int curve, size_t num_cons, size_t num_vars, size_t num_io, const SparseMatrix& a, const SparseMatrix& b, const SparseMatrix& c) {
+        lurk_hip_r1cs* h = nullptr;
+        check(lurk_hip_r1cs_create_for_curve(&h, curve, num_cons, num_vars, num_io, a.indptr.data(), a.indices.data(), a.data.data(), b.indptr.data(),
+                                             b.indices.data(), b.data.data(), c.indptr.data(), c.indices.data(), c.data.data()));
+        return R1CSShape(h);
+    }
     ~R1CSShape() { lurk_hip_r1cs_destroy(h_); }
     R1CSShape(const R1CSShape&) = delete;
     // (A z, B z, C z)

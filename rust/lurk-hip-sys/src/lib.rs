@@ -226,6 +226,17 @@ impl R1csShape {
         })?;
         Ok(Self(p))
     }
+    /// The same shape over the SCALAR field of `curve` (`lurk_hip_r1cs_create_for_curve`): the one way to a shape over the BN254 base
+    /// field, Grumpkin's scalar field, which `FoldingContext::new(LURK_CURVE_GRUMPKIN, ..)` folds.
+    pub fn for_curve(curve: c_int, num_cons: usize, num_vars: usize, num_io: usize, a: Csr, b: Csr, c: Csr) -> Result<Self, Error> {
+        let mut p = core::ptr::null_mut();
+        check(unsafe {
+            lurk_hip_r1cs_create_for_curve(&mut p, curve, num_cons, num_vars, num_io, a.indptr.as_ptr(), a.indices.as_ptr(), a.data.as_ptr().cast(),
+                                           b.indptr.as_ptr(), b.indices.as_ptr(), b.data.as_ptr().cast(), c.indptr.as_ptr(), c.indices.as_ptr(),
+                                           c.data.as_ptr().cast())
+        })?;
+        Ok(Self(p))
+    }
     /// The slot rows of a MultiFrame at the layout `lurk_hip_frames_witness_dev` writes (`lurk_hip_frames_r1cs_create`): `counts5` per frame
     /// in (hash4, hash6, hash8, commitment, bit_decomp) order, ONE at column `num_vars`; `extra` = the caller's further rows (A, B, C over the
     /// same columns), appended after the slot rows.  The slot rows' order relative to the rest of lurk-beta's real circuit is unpinned: for
